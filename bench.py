@@ -29,6 +29,15 @@ bench line:
   3lr  configs[3]: 1024^3, 12-channel long-range affinities (N=1)
   4    configs[4]: 1024^3 high fragmentation (cell 5, ~5e7 edges), strong
        scaling like config 2
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.
+``--full`` adds what takes runs of its own: the CPU baseline (configs 1, 2, 0)
+and, for configs[0], the CPU-layout process mode, the thread mode and the
+compute-only / roofline pass; without it those keys of the line are null.
+``--dump-outputs DIR`` writes what the last timed step returned (edges, nodes,
+features; a fixed seeded row sample of tables above the dump budget) as float64
+``DIR/<name>.npy``: the inputs depend on the arguments alone, so two builds can
+be compared output for output.
 """
 from __future__ import annotations
 
@@ -69,12 +78,20 @@ def parse():
     p.add_argument('--size', type=int, default=None, help='cube edge (voxels; per GPU for weak scaling)')
     p.add_argument('--cell', type=int, default=None)
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--full', action='store_true',
+                   help='after the headline measurement also run what takes runs of its own: the CPU baseline '
+                        '(configs 1, 2 and 0) and, for configs[0], the CPU-layout and thread-mode workflows and the '
+                        'compute-only / roofline pass; without it those keys of the line are null')
+    p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                   help='after the timed steps, write what the last timed step returned (edges, nodes, features) as '
+                        'float64 DIR/<name>.npy; tables larger than the dump budget are written as a fixed seeded '
+                        'sample of their rows (DUMP_MAX_ROWS / DUMP_MAX_NODES)')
     p.add_argument('--cpu-baseline-planes', type=int, default=None,
-                   help='z-planes of the volume timed with the C oracle (0 = skip; default: 512 of '
+                   help='--full: z-planes of the volume timed with the C oracle (0 = skip; default: 512 of '
                         'configs[1], 256 of configs[2] = 1.07 G voxels)')
     p.add_argument('--cpu-threads', type=int, default=min(16, os.cpu_count() or 1),
-                   help='worker processes of the CPU baseline (the GPU box allots 16 cores per GPU)')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+                   help='--full: worker processes of the CPU baseline (16 cores are allotted per GPU)')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
     # rehearsal of the N>1 path on a one-GPU box: every rank on one device,
     # exchange over gloo (the driver's multi-GPU runs use the defaults: RCCL,
     # device = LOCAL_RANK)
@@ -112,6 +129,56 @@ def pmc_traffic_per_launch(config='1'):
         except Exception:
             continue
     return None, None, None
+
+
+# --dump-outputs budget: 2^18 sampled edge rows (edges 4 MiB + features 20 MiB
+# as float64) and 2^21 sampled nodes (16 MiB) -- under 64 MB in all; with R
+# ranks each rank writes 1/R of it
+DUMP_MAX_ROWS = 1 << 18
+DUMP_MAX_NODES = 1 << 21
+DUMP_SEED = 0x5eed
+
+
+def sample_rows(n, max_rows, seed=DUMP_SEED):
+    """Sorted row indices of a fixed, seeded sample of ``max_rows`` of ``n``
+    rows (a function of n, max_rows and seed alone), or None = every row."""
+    if n <= max_rows:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, size=max_rows, replace=False))
+
+
+def dump_outputs(dirname, edges, nodes, features, counts, suffix=''):
+    """Write the (sampled) tables of the last timed step as float64
+    ``<name><suffix>.npy`` (labels are exact in float64 below 2^53) and
+    ``counts`` = the full (edges, nodes) table lengths.  Returns the shapes."""
+    os.makedirs(dirname, exist_ok=True)
+    shapes = {}
+    for name, a in (('edges', edges), ('nodes', nodes), ('features', features), ('counts', counts)):
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        np.save(os.path.join(dirname, name + suffix + '.npy'), a)
+        shapes[name + suffix] = list(a.shape)
+    return shapes
+
+
+def dump_result(dirname, res, world=1, rank=0):
+    """--dump-outputs of the whole-volume step: rows of the device-resident
+    result (rag.Result, or this rank's shard of a dist.DistResult) are sampled
+    on the device, so only the sample crosses to the host."""
+    import torch
+
+    def take(t, idx):
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.to(torch.float64).cpu().numpy()
+    e = res.edges_torch_i64()
+    rows = sample_rows(e.shape[0], DUMP_MAX_ROWS // world)
+    edges = take(e, rows)
+    del e
+    features = take(res.features_torch(), rows)
+    n = res.node_shard if hasattr(res, 'node_shard') else res.nodes_torch()
+    counts = [int(res.n_edges), int(n.shape[0])]
+    nodes = take(n, sample_rows(n.shape[0], DUMP_MAX_NODES // world))
+    return dump_outputs(dirname, edges, nodes, features, counts, '_rank%d' % rank if world > 1 else '')
 
 
 def cpu_baseline(labels_t, bnd_t, planes, workers):
@@ -236,11 +303,12 @@ CONFIG0_PROC_LAYOUTS = {'gpu': dict(graph=1, features=1, merge=1),
 def bench_config0(args):
     """BASELINE configs[0]: the per-block drop-in path, N5 in -> N5 out.
 
-    Two job models over the same N5 input: ``processes`` (the reference's --
-    LocalTask runs every job as its own process, cluster_tasks.py:528-550;
-    this is ``value``) and ``threads`` (every job on a thread of this process,
-    sharing the device state and the decoded-chunk cache), then the
-    device-only time of the same per-block calls."""
+    ``value``: the ``processes`` job model (the reference's -- LocalTask runs
+    every job as its own process, cluster_tasks.py:528-550).  With ``--full``,
+    over the same N5 input: the same with the CPU layout's job counts,
+    ``threads`` (every job on a thread of this process, sharing the device
+    state and the decoded-chunk cache), the CPU baseline, then the device-only
+    time of the same per-block calls."""
     import multiprocessing as mp
     import shutil
     import tempfile
@@ -259,7 +327,7 @@ def bench_config0(args):
         with ProcessPoolExecutor(1, mp_context=mp.get_context('spawn')) as ex:
             in_bytes = ex.submit(_config0_write_inputs, inp, shape, block, cell, args.seed).result()
 
-        def step(k, mode, jobs):
+        def step(k, mode, jobs, dump=None):
             # every step starts from cold decode caches (thread mode: the bench
             # process's cache would otherwise still hold the input of the last step)
             from cluster_tools_amd import _lib
@@ -275,22 +343,34 @@ def bench_config0(args):
             for key in ('s0/sub_features', 's0/sub_features_stats', 'features', 's0/sub_graphs'):
                 p = os.path.join(out, key)
                 out_bytes[key] = sum(os.path.getsize(os.path.join(r, fn)) for r, _, fs in os.walk(p) for fn in fs)
+            dump_s = 0.0
+            if dump:   # --dump-outputs: the step's N5 outputs, read back before the step's directory goes
+                c0 = time.perf_counter()
+                with n5.File(out, 'r') as f:
+                    edges, nodes, feats = f['graph']['edges'][:], f['graph']['nodes'][:], f['features'][:]
+                rows, nrows = sample_rows(edges.shape[0], DUMP_MAX_ROWS), sample_rows(nodes.shape[0], DUMP_MAX_NODES)
+                dumped.update(dump_outputs(dump, edges if rows is None else edges[rows],
+                                           nodes if nrows is None else nodes[nrows],
+                                           feats if rows is None else feats[rows],
+                                           [edges.shape[0], nodes.shape[0]]))
+                dump_s = time.perf_counter() - c0
             shutil.rmtree(out)
-            return t.stages, n_edges
+            return t.stages, n_edges, dump_s
 
         out_bytes = {}   # on-disk bytes of the outputs (last step)
+        dumped = {}      # --dump-outputs: name -> shape of the arrays written
         # a step is a whole workflow run (seconds): at most 1 warm-up + 3 steps
         args.warmup, args.steps = min(args.warmup, 1), max(1, min(args.steps, 3))
 
-        def measure(mode, jobs, base):
+        def measure(mode, jobs, base, dump=None):
             for k in range(args.warmup):
                 step(base + k, mode, jobs)
             times, stages, feat_prof = [], {}, {}
             from cluster_tools_amd import ndist
             for k in range(args.steps):
                 t0 = time.perf_counter()
-                st, n_edges = step(base + 100 + k, mode, jobs)
-                times.append(time.perf_counter() - t0)
+                st, n_edges, dump_s = step(base + 100 + k, mode, jobs, dump if k == args.steps - 1 else None)
+                times.append(time.perf_counter() - t0 - dump_s)
                 for key, v in st.items():
                     stages[key] = stages.get(key, 0.0) + v / args.steps
                 if mode == 'threads':   # the (single) block-feature job's split, in this process
@@ -309,61 +389,94 @@ def bench_config0(args):
         layout = dict(CONFIG0_PROC_LAYOUTS['gpu'])
         if args.c0_jobs:
             layout = dict(zip(('graph', 'features', 'merge'), (int(v) for v in args.c0_jobs.split(','))))
-        ms_p, stages_p, _, n_edges = measure('processes', layout, 0)
-        proc_split = split()
-        ms_c, stages_c, _, _ = measure('processes', CONFIG0_PROC_LAYOUTS['cpu_layout'], 500)
-        proc_split_c = split()
-        ms_t, stages_t, feat_prof, _ = measure('threads', dict(graph=16, features=1, merge=4), 1000)
 
-        cpu = None if args.no_cpu_baseline else cpu_baseline_config0(inp, d, shape, block, args.cpu_threads)
-        from cluster_tools_amd import _lib, n5, rag
-        from cluster_tools_amd.blocking import blocking
-        torch.cuda.set_device(0 if args.device is None else args.device)
-        _lib.init_device(0 if args.device is None else args.device)
-        with n5.File(inp, 'r') as f:
-            lt = torch.from_numpy(f['seg'][:].view(np.int64)).cuda()
-            bt = torch.from_numpy(f['bnd'][:]).cuda()
-        # compute only: the same per-block calls on device-resident inputs
-        blk = blocking([0, 0, 0], list(shape), list(block))
-        descs, lo = [], 0
-        arrays = []
-        for b in range(blk.numberOfBlocks):
-            bb = blk.getBlock(b)
-            rb = [max(x - 1, 0) for x in bb.begin]
-            sl = tuple(slice(x, y) for x, y in zip(rb, bb.end))
-            shp = [y - x for x, y in zip(rb, bb.end)]
-            descs.append(dict(label_offset=lo, data_offset=lo, shape=shp,
-                              own=([x - r for x, r in zip(bb.begin, rb)], [y - r for y, r in zip(bb.end, rb)]),
-                              graph=([0, 0, 0], shp)))
-            arrays.append(sl)
-            lo += int(np.prod(shp))
-        la = torch.cat([lt[sl].reshape(-1) for sl in arrays])
-        da = torch.cat([bt[sl].reshape(-1) for sl in arrays])
-        del lt, bt
-        rag.set_profiling(True)
-        for _ in range(2):
-            rag.rag_blocks_arena(la, descs)
-            rag.rag_blocks_arena(la, descs, da, keep_stats=True)
-        torch.cuda.synchronize()
-        c0 = time.perf_counter()
-        n_rep = 5
-        scan_ms, dev_ms = [], []
-        for _ in range(n_rep):
-            rag.rag_blocks_arena(la, descs)
-            g = rag.last_timings()['total']
-            rag.rag_blocks_arena(la, descs, da, keep_stats=True, nodes=False)
-            tm = rag.last_timings()
-            scan_ms.append(tm['scan'])
-            dev_ms.append(g + tm['total'])
-        torch.cuda.synchronize()
-        wall_s = (time.perf_counter() - c0) / n_rep
-        compute_s = float(np.mean(dev_ms)) * 1e-3
-        rag.set_profiling(False)
+        def config0_full():
+            # --full: the other job layouts, the CPU baseline and the compute-only / roofline pass
+            ms_c, stages_c, _, _ = measure('processes', CONFIG0_PROC_LAYOUTS['cpu_layout'], 500)
+            proc_split_c = split()
+            ms_t, stages_t, feat_prof, _ = measure('threads', dict(graph=16, features=1, merge=4), 1000)
+
+            cpu = None if args.no_cpu_baseline else cpu_baseline_config0(inp, d, shape, block, args.cpu_threads)
+            from cluster_tools_amd import _lib, n5, rag
+            from cluster_tools_amd.blocking import blocking
+            torch.cuda.set_device(0 if args.device is None else args.device)
+            _lib.init_device(0 if args.device is None else args.device)
+            with n5.File(inp, 'r') as f:
+                lt = torch.from_numpy(f['seg'][:].view(np.int64)).cuda()
+                bt = torch.from_numpy(f['bnd'][:]).cuda()
+            # compute only: the same per-block calls on device-resident inputs
+            blk = blocking([0, 0, 0], list(shape), list(block))
+            descs, lo = [], 0
+            arrays = []
+            for b in range(blk.numberOfBlocks):
+                bb = blk.getBlock(b)
+                rb = [max(x - 1, 0) for x in bb.begin]
+                sl = tuple(slice(x, y) for x, y in zip(rb, bb.end))
+                shp = [y - x for x, y in zip(rb, bb.end)]
+                descs.append(dict(label_offset=lo, data_offset=lo, shape=shp,
+                                  own=([x - r for x, r in zip(bb.begin, rb)], [y - r for y, r in zip(bb.end, rb)]),
+                                  graph=([0, 0, 0], shp)))
+                arrays.append(sl)
+                lo += int(np.prod(shp))
+            la = torch.cat([lt[sl].reshape(-1) for sl in arrays])
+            da = torch.cat([bt[sl].reshape(-1) for sl in arrays])
+            del lt, bt
+            rag.set_profiling(True)
+            for _ in range(2):
+                rag.rag_blocks_arena(la, descs)
+                rag.rag_blocks_arena(la, descs, da, keep_stats=True)
+            torch.cuda.synchronize()
+            c0 = time.perf_counter()
+            n_rep = 5
+            scan_ms, dev_ms = [], []
+            for _ in range(n_rep):
+                rag.rag_blocks_arena(la, descs)
+                g = rag.last_timings()['total']
+                rag.rag_blocks_arena(la, descs, da, keep_stats=True, nodes=False)
+                tm = rag.last_timings()
+                scan_ms.append(tm['scan'])
+                dev_ms.append(g + tm['total'])
+            torch.cuda.synchronize()
+            wall_s = (time.perf_counter() - c0) / n_rep
+            compute_s = float(np.mean(dev_ms)) * 1e-3
+            rag.set_profiling(False)
+            scan_avg = float(np.mean(scan_ms))
+            alg = lo * 12                                   # the feature scan reads every block array (+ halo) once
+            traffic, traffic_src, _ = pmc_traffic_per_launch('0') if not args.cell else (None, None, None)
+            return {
+                'process_mode_cpu_layout': {
+                    'value': round(V / (ms_c * 1e-3) / 1e9, 4), 'unit': 'Gvoxels/s', 'ms_per_step': round(ms_c, 2),
+                    'jobs': CONFIG0_PROC_LAYOUTS['cpu_layout'],
+                    'stage_s': {k: round(v, 4) for k, v in stages_c.items()},
+                    'process_split_last_step': proc_split_c,
+                    'what': 'process mode with the job counts of the CPU layout (one graph job per core): every job '
+                            'process creates and tears down a device context'},
+                'thread_mode': {
+                    'value': round(V / (ms_t * 1e-3) / 1e9, 4), 'unit': 'Gvoxels/s', 'ms_per_step': round(ms_t, 2),
+                    'stage_s': {k: round(v, 4) for k, v in stages_t.items()},
+                    'block_features_split_s': {k: round(v, 4) for k, v in feat_prof.items()},
+                    'what': 'the same workflow with every job on a thread of the bench process (16 graph jobs; '
+                            'jobs share the device state and the decoded-chunk cache)'},
+                'compute_only': {
+                    'value': round(V / compute_s / 1e9, 4), 'unit': 'Gvoxels/s', 'ms': round(compute_s * 1e3, 3),
+                    'with_d2h_ms': round(wall_s * 1e3, 3),
+                    'what': 'device time (HIP events) of the ctg_rag_blocks graph call + feature call over '
+                            'the 50 block arrays (device-resident, halo planes included); with_d2h = wall '
+                            'time including the copies of the per-block results to host memory'},
+                'roofline': {
+                    'bound': 'hbm', 'kernel': 'k_face_scan (batched blocks, features)',
+                    'kernel_ms': round(scan_avg, 4), 'algorithmic_bytes': alg,
+                    'achieved': round(alg / (scan_avg * 1e-3) / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                    'frac': round(alg / (scan_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'traffic': traffic,
+                    'traffic_source': traffic_src},
+                'cpu_baseline': cpu,
+            }
+
+        ms_p, stages_p, _, n_edges = measure('processes', layout, 0, args.dump_outputs)
+        proc_split = split()
+        extra = config0_full() if args.full else {}
     finally:
         shutil.rmtree(d, ignore_errors=True)
-    scan_avg = float(np.mean(scan_ms))
-    alg = lo * 12                                   # the feature scan reads every block array (+ halo) once
-    traffic, traffic_src, _ = pmc_traffic_per_launch('0') if not args.cell else (None, None, None)
     line = {
         'metric': 'Gvoxels/s RAG+edge features (per-block drop-in path, gzip N5 in -> N5 out, uint64 labels, '
                   'float32 boundary map)',
@@ -382,31 +495,14 @@ def bench_config0(args):
                    'stats_compression': os.environ.get('CTG_STATS_COMPRESSION', 'gzip')},
         'stage_s': {k: round(v, 4) for k, v in stages_p.items()},
         'process_split_last_step': proc_split,
-        'process_mode_cpu_layout': {'value': round(V / (ms_c * 1e-3) / 1e9, 4), 'unit': 'Gvoxels/s',
-                                    'ms_per_step': round(ms_c, 2), 'jobs': CONFIG0_PROC_LAYOUTS['cpu_layout'],
-                                    'stage_s': {k: round(v, 4) for k, v in stages_c.items()},
-                                    'process_split_last_step': proc_split_c,
-                                    'what': 'process mode with the job counts of the CPU layout (one graph job '
-                                            'per core): every job process creates and tears down a device '
-                                            'context'},
-        'thread_mode': {'value': round(V / (ms_t * 1e-3) / 1e9, 4), 'unit': 'Gvoxels/s', 'ms_per_step': round(ms_t, 2),
-                        'stage_s': {k: round(v, 4) for k, v in stages_t.items()},
-                        'block_features_split_s': {k: round(v, 4) for k, v in feat_prof.items()},
-                        'what': 'the same workflow with every job on a thread of the bench process (16 graph jobs; '
-                                'jobs share the device state and the decoded-chunk cache)'},
-        'compute_only': {'value': round(V / compute_s / 1e9, 4), 'unit': 'Gvoxels/s',
-                         'ms': round(compute_s * 1e3, 3),
-                         'with_d2h_ms': round(wall_s * 1e3, 3),
-                         'what': 'device time (HIP events) of the ctg_rag_blocks graph call + feature call over '
-                                 'the 50 block arrays (device-resident, halo planes included); with_d2h = wall '
-                                 'time including the copies of the per-block results to host memory'},
-        'roofline': {'bound': 'hbm', 'kernel': 'k_face_scan (batched blocks, features)',
-                     'kernel_ms': round(scan_avg, 4), 'algorithmic_bytes': alg,
-                     'achieved': round(alg / (scan_avg * 1e-3) / 1e9, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': round(alg / (scan_avg * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'traffic': traffic,
-                     'traffic_source': traffic_src},
-        'cpu_baseline': cpu,
+        'process_mode_cpu_layout': extra.get('process_mode_cpu_layout'),
+        'thread_mode': extra.get('thread_mode'),
+        'compute_only': extra.get('compute_only'),
+        'roofline': extra.get('roofline'),
+        'cpu_baseline': extra.get('cpu_baseline'),
     }
+    if dumped:
+        line['outputs'] = {'path': args.dump_outputs, 'arrays': dumped}
     print(json.dumps(line), flush=True)
 
 
@@ -422,6 +518,8 @@ def launch_plan(args, env, device_count):
     n = int(args.gpus)
     if n < 1:
         return 'error', '--gpus must be >= 1'
+    if args.steps < 1 or args.warmup < 0:
+        return 'error', '--steps must be >= 1 and --warmup >= 0 (ms_per_step is the mean over the timed steps)'
     world = env.get('WORLD_SIZE')
     multi_cfg = WORKLOADS[args.config][2] is None and args.config != '0'
     if n > 1 and not multi_cfg:
@@ -622,13 +720,17 @@ def main():
                       'what': 'dist.gather_to_host of the last step\'s shards on rank 0, then graph/{nodes,edges} '
                               '+ features N5 datasets as MergeSubGraphs / MergeEdgeFeatures write them'}
 
+    dumped = None
+    if args.dump_outputs:   # the last timed step's result, outside the timed region
+        dumped = dump_result(args.dump_outputs, res, world, rank)
+
     line = None
     if rank == 0:
         cpu = None
         planes = args.cpu_baseline_planes
         if planes is None:
             planes = {'1': 512, '2': 256}.get(args.config, 0)
-        if not args.no_cpu_baseline and planes > 0 and world == 1 and args.config in ('1', '2'):
+        if args.full and not args.no_cpu_baseline and planes > 0 and world == 1 and args.config in ('1', '2'):
             v, info = cpu_baseline(lab, bnd, min(planes, S), args.cpu_threads)
             cpu = {'value': round(v, 6), 'unit': 'Gvoxels/s', 'cores': info['threads'], 'kind': 'port',
                    'sample': info['sample'] + ', %.2f s slowest worker (best of 3), oracle/ctg_oracle.c scalar C restatement '
@@ -676,6 +778,8 @@ def main():
         }
         if output is not None:
             line['output'] = output
+        if dumped is not None:
+            line['outputs'] = {'path': args.dump_outputs, 'arrays': dumped}
         print(json.dumps(line), flush=True)
     res.free()
     if use_dist:

@@ -249,6 +249,36 @@ def test_bench_launch_plan():
     assert plan(['--gpus', '0'], {}, 1)[0] == 'error'
 
 
+def test_bench_plain_run_options():
+    """A plain run asks for none of the extra measurements: --full and
+    --dump-outputs are off unless given."""
+    bench = _bench()
+    a = _bench_args(bench, ['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    a = _bench_args(bench, ['--full', '--dump-outputs', 'somewhere'])
+    assert a.full and a.dump_outputs == 'somewhere'
+
+
+def test_bench_dump_sample_is_fixed_and_float64(tmp_path):
+    """--dump-outputs: the row sample is a function of the table length alone
+    (sorted, without repeats, every row when the table fits), and the arrays
+    are written as float64 <name>.npy within the 64 MB budget."""
+    bench = _bench()
+    assert bench.sample_rows(50, 50) is None
+    idx = bench.sample_rows(1000, 50)
+    assert idx.shape == (50,) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 1000
+    np.testing.assert_array_equal(idx, bench.sample_rows(1000, 50))
+    assert bench.DUMP_MAX_ROWS * (2 + 10) * 8 + bench.DUMP_MAX_NODES * 8 + 16 <= 64e6
+    edges = np.array([[1, 2], [1, 3], [2, 3]], np.uint64)
+    feats = np.arange(30, dtype=np.float64).reshape(3, 10) / 7
+    shapes = bench.dump_outputs(str(tmp_path / 'd'), edges, np.array([1, 2, 3], np.uint64), feats, [3, 3])
+    assert shapes == {'edges': [3, 2], 'nodes': [3], 'features': [3, 10], 'counts': [2]}
+    for name, want in (('edges', edges), ('features', feats), ('counts', [3, 3])):
+        got = np.load(str(tmp_path / 'd' / (name + '.npy')))
+        assert got.dtype == np.float64
+        np.testing.assert_array_equal(got, np.asarray(want, np.float64))
+
+
 def test_bench_launch_ranks_starts_n_processes(tmp_path):
     """launch_ranks really starts N rank processes through torch.distributed.run
     (rendezvous on 127.0.0.1), passes the arguments through, and relays the exit

@@ -21,5 +21,5 @@ timeout -k 10 300 python bench.py --gpus 2 --backend gloo --device 0 --config 1 
 rc=$?; echo "N2 gloo rc=$rc"; cat $O/bench_n2_gloo_c1.json | cut -c1-400; [ $rc -eq 0 ] || { tail -20 $O/bench_n2_gloo_c1.err; exit 1; }
 timeout -k 10 120 python bench.py --gpus 2 --config 1 --steps 5 > $O/bench_n2_nccl.json 2> $O/bench_n2_nccl.err
 echo "N2 nccl on one device rc=$? (expect 2): $(cat $O/bench_n2_nccl.err | tail -1)"
-timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 cut -c1-600 $O/bench.json

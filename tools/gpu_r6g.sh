@@ -12,7 +12,7 @@ grep '^{' $O/bench_n2_gloo_c2.json | cut -c1-300
 timeout -k 10 300 python bench.py --gpus 4 --backend gloo --device 0 --config 1 --steps 5 --warmup 1 --no-cpu-baseline \
   > $O/bench_n4_gloo_c1.json 2> $O/bench_n4_gloo_c1.err || { echo "N4 c1 FAILED"; tail -5 $O/bench_n4_gloo_c1.err; exit 1; }
 grep '^{' $O/bench_n4_gloo_c1.json | cut -c1-300
-timeout -k 10 900 python bench.py --config 0 > $O/bench_c0.json 2> $O/bench_c0.err || { echo "C0 FAILED"; tail -5 $O/bench_c0.err; exit 1; }
+timeout -k 10 900 python bench.py --full --config 0 > $O/bench_c0.json 2> $O/bench_c0.err || { echo "C0 FAILED"; tail -5 $O/bench_c0.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench_c0.json'))
 print('C0', d['value'], d['ms_per_step'], 'threads', d['thread_mode']['value'], 'cpu', d['cpu_baseline']['value'], d['config']['output_bytes'])

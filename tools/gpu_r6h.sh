@@ -12,7 +12,7 @@ for v in agg inl; do
 done
 bash tools/gpu_ab_sets.sh $TAG/ab "2 4 1" - CTG_LIB=variants/libctg_agg.so CTG_LIB=variants/libctg_inl.so - CTG_LIB=variants/libctg_agg.so CTG_LIB=variants/libctg_inl.so
 O=gpurun_out/$TAG
-timeout -k 10 900 python bench.py --config 0 --no-cpu-baseline > $O/bench_c0.json 2> $O/bench_c0.err || { echo "C0 FAILED"; tail -5 $O/bench_c0.err; exit 1; }
+timeout -k 10 900 python bench.py --full --config 0 --no-cpu-baseline > $O/bench_c0.json 2> $O/bench_c0.err || { echo "C0 FAILED"; tail -5 $O/bench_c0.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench_c0.json'))
 print('C0', d['value'], d['ms_per_step'], 'threads', d['thread_mode']['value'], d['config']['output_bytes'])
