@@ -4,10 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstddef>
+#include <memory>
+#include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ctg.h"
+#include "ctg_plan.h"
 
 namespace ctg {
 
@@ -51,8 +55,7 @@ constexpr int WAVE = 64;
 #define CTG_SCAN_THREADS 512
 #endif
 constexpr int SCAN_THREADS = CTG_SCAN_THREADS;   // 8 waves per workgroup (1024: 16 waves, one per CU)
-constexpr int TILE_X = 64;             // one wave row
-constexpr int TILE_Y = 8;
+constexpr int TILE_Y = 8;              // (TILE_X, one wave row: ctg_plan.h)
 // LDS edge-table entries: a multiple of 4 (4-slot buckets), at most one per
 // thread in a flush; a power of two or not (the home bucket is a multiply-high)
 #ifndef CTG_TABLE_CAP
@@ -316,14 +319,149 @@ struct Workspace {
     int profiling = 0;
 };
 
+// ---------------------------------------------------------------------------
+// workspace, allocator and error state (ctg_workspace.hip, ctg_api.hip)
+// ---------------------------------------------------------------------------
 Workspace& ws(int device);
+hipError_t ws_init(Workspace& w);
 int current_device();
 void set_error(const std::string& msg);
 void ensure(void** p, size_t& have, size_t need);
+void free_records(Workspace& w);
 hipError_t ensure_records(Workspace& w, int64_t need, int wide);
-// the library's caching device allocator (stream-ordered reuse, ctg_api.hip)
+// the library's caching device allocator (ctg_workspace.hip).  dev_free only
+// returns the block to the host-side pool: kernels already queued on the
+// stream still use it, and a later user of the block runs after them
+// ("stream-ordered reuse")
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);
+
+// One workspace per device: calls that use it are serialised per device, so
+// job threads may call the library concurrently (ctypes drops the GIL) --
+// their N5 decode overlaps, their GPU work queues.  Recursive: the dense
+// relabel and adjacency paths re-enter the C ABI.
+std::recursive_mutex& device_mutex(int device);
+struct DevLock {
+    std::lock_guard<std::recursive_mutex> g;
+    DevLock() : g(device_mutex(current_device())) {}
+};
+
+// A block of the caching allocator that goes back to the pool when its scope
+// ends (every early return included); reset() returns it sooner, release()
+// hands it to a result.  Sizes are in bytes.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    explicit DevBuf(size_t bytes) : p((T*)dev_alloc(bytes)) {}
+    DevBuf(DevBuf&& o) noexcept : p(o.release()) {}   // (move-only: no copy is declared)
+    ~DevBuf() { dev_free(p); }
+    T* alloc(size_t bytes) { return reset((T*)dev_alloc(bytes)); }
+    T* reset(T* q = nullptr) {
+        dev_free(std::exchange(p, q));
+        return p;
+    }
+    T* release() { return std::exchange(p, nullptr); }
+    operator T*() const { return p; }
+};
+
+// rocPRIM call with a growable temp buffer: size query (null temp), grow, run.
+// call: (void* temp, size_t& bytes) -> hipError_t
+template <class F>
+hipError_t with_temp(void*& temp, size_t& temp_bytes, F&& call) {
+    size_t bytes = 0;
+    hipError_t e = call(nullptr, bytes);
+    if (e != hipSuccess) return e;
+    ensure(&temp, temp_bytes, bytes + 256);
+    if (!temp) return hipErrorOutOfMemory;
+    bytes = temp_bytes;
+    return call(temp, bytes);
+}
+
+struct Ev {   // phase marks of a profiled call
+    Workspace& w;
+    hipStream_t s;
+    void mark(int i) {
+        if (w.profiling) hipEventRecord(w.ev[i], s);
+    }
+};
+
+// ---------------------------------------------------------------------------
+// launchers (one declaration each; the definitions name their file)
+// ---------------------------------------------------------------------------
+// ctg_scan.hip
+hipError_t launch_face_scan(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s);
+int scan_tile_rows();
+int scan_tile_rows_narrow();
+hipError_t launch_density(const void* L, int label_bits, const int64_t* shape, int n_rows, uint32_t* out,
+                          hipStream_t s);
+hipError_t launch_unique_tiles(const uint64_t* L, const int64_t* shape, const int64_t* b, const int64_t* e,
+                               uint64_t* out, unsigned long long* count, int64_t cap, hipStream_t s);
+hipError_t launch_unique_blocks(const void* L, int label_bits, const BlockGeom* blocks, const uint32_t* tile_prefix,
+                                int n_blocks, int64_t n_tiles, uint64_t* out, unsigned long long* count, int64_t cap,
+                                hipStream_t s);
+int unique_tile_y();
+// ctg_sort.hip
+hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, int64_t n, int lo_bit, int hi_bit,
+                            uint64_t kmin, uint64_t kmax, uint32_t* small, void** temp, size_t* temp_bytes,
+                            uint32_t* nbk_out, hipStream_t s);
+hipError_t bucket_runs(const uint64_t* sorted, int64_t n, int lo_bit, uint32_t nbk, uint32_t* small, uint64_t* uniq,
+                       uint32_t* runs, uint32_t* roffs, uint32_t* dE, hipStream_t s);
+hipError_t bucket_sort_pairs(const uint64_t* keys, const uint32_t* vals, uint64_t* ktmp, uint32_t* vtmp,
+                             uint64_t* kout, uint32_t* vout, int64_t n, int hi_bit, uint32_t* small, void** temp,
+                             size_t* temp_bytes, uint32_t* nbk_out, hipStream_t s);
+hipError_t group_sort_runs(const uint64_t* key, int64_t rcap, const RegionPrefix& pre, int64_t n, int nb, int ub,
+                           int ib, uint64_t min_label, uint64_t max_label, uint32_t* small, uint32_t* host_word,
+                           uint64_t* items, uint32_t* perm, uint64_t* uniq, uint32_t* runs, uint32_t* roffs,
+                           uint32_t* dE, bool* done, hipStream_t s);
+// ctg_reduce.hip
+hipError_t launch_pack_keys(int64_t n, const uint64_t* key, int nb, uint64_t* sk, uint32_t* idx, hipStream_t s);
+hipError_t launch_pack_regions(const uint64_t* key, int64_t rcap, const RegionPrefix& pre, int nb, int ib, uint64_t* sk,
+                               uint32_t* idx, hipStream_t s);
+hipError_t launch_pack_pairs(int64_t n, const uint64_t* uv, int nb, uint64_t* sk, uint32_t* idx, hipStream_t s);
+hipError_t launch_max_pairs(int64_t n, const uint64_t* uv, unsigned long long* out, hipStream_t s);
+hipError_t launch_reduce(int64_t E, const uint32_t* dE, const uint64_t* uniq, const uint32_t* runs,
+                         const uint32_t* offs, const uint32_t* perm32, const uint64_t* perm64, int ib,
+                         const RecordBuf& R, int wide, int stats, int nb, uint64_t umask, int need_adj,
+                         int ignore_label, double scale, double offset, const ReduceOut& O, hipStream_t s,
+                         uint32_t* heavy = nullptr, uint32_t* n_heavy = nullptr);
+hipError_t launch_block_bounds(int64_t n, const uint64_t* col, int stride, int n_blocks, int shift, int64_t* bounds,
+                               hipStream_t s);
+hipError_t launch_clear_bits(int64_t n, uint64_t* col, int stride, uint64_t mask, hipStream_t s);
+hipError_t launch_compact(int64_t E, const uint32_t* dE, const uint32_t* keep, const uint32_t* pos,
+                          const ReduceOut& in, const ReduceOut& out, uint32_t* dkept, hipStream_t s);
+hipError_t launch_endpoints(int64_t E, const uint64_t* uniq, int nb, uint32_t* out, hipStream_t s);
+hipError_t launch_u32_to_u64(int64_t n, const uint32_t* in, uint64_t* out, hipStream_t s);
+hipError_t launch_mark_nodes(int64_t E, const uint32_t* dE, const uint64_t* uniq, int nb, uint32_t* bits,
+                             int64_t W, uint32_t wbase, hipStream_t s);
+hipError_t launch_bits_to_nodes(int64_t W, const uint32_t* bits, const uint32_t* off, uint64_t* nodes, uint32_t* dN,
+                                int64_t cap, uint32_t wbase, hipStream_t s);
+hipError_t launch_build_bloom(const uint64_t* edges, int64_t E, unsigned long long* words, uint32_t mask,
+                              hipStream_t s);
+hipError_t launch_find_edges(const uint64_t* ge, int64_t n, const uint64_t* q, int64_t m, int64_t* out,
+                             hipStream_t s);
+hipError_t launch_remap_dense(const uint64_t* L, int64_t V, const uint64_t* U, int64_t n, uint32_t* out,
+                              hipStream_t s);
+hipError_t launch_gather_labels(const uint64_t* U, uint64_t* x, int64_t n, hipStream_t s);
+hipError_t launch_remap_dense64(const uint64_t* L, int64_t V, const uint64_t* U, int64_t n, uint64_t* out,
+                                hipStream_t s);
+hipError_t launch_row_keys(int64_t n, const uint64_t* ids, uint64_t begin, uint64_t end, uint32_t* key,
+                           uint32_t* idx, uint32_t* bad, hipStream_t s);
+hipError_t launch_merge_feature_rows(int64_t n, const uint32_t* key, const uint32_t* idx, const double* rows,
+                                     double* out, hipStream_t s);
+// ctg_synth.hip
+hipError_t launch_synth(uint64_t* labels, float* boundary, const int64_t* shape, int64_t z_offset,
+                        const int64_t* gshape, int cell, uint64_t seed, uint64_t label_offset, double noise_amp,
+                        hipStream_t s);
+hipError_t launch_synth_aff(const float* b, float* out, const int64_t* shape, int n_channels, const int32_t* off,
+                            hipStream_t s);
+#ifdef CTG_DIAG   // the per-file bounds-check blocks (CTG_BOUNDS_TAKE above)
+hipError_t bounds_take_api(unsigned long long* h);
+hipError_t bounds_take_reduce(unsigned long long* h);
+hipError_t bounds_take_sort(unsigned long long* h);
+hipError_t bounds_take_mgpu(unsigned long long* h);
+hipError_t bounds_take_scan(unsigned long long* h);
+#endif
 
 }  // namespace ctg
 
@@ -355,6 +493,37 @@ struct ctg_result {
 };
 
 namespace ctg {
+
+// a result under construction: freed (ctg_free) unless release()d to the caller
+struct ResultFree {
+    void operator()(ctg_result* r) const { ctg_free(r); }
+};
+using ResultPtr = std::unique_ptr<ctg_result, ResultFree>;
+ResultPtr new_result(int device);     // the one place a handle is made
+ResultPtr empty_result(int device);   // no edges, no nodes: the 16- and 8-byte placeholders
+
+// ---------------------------------------------------------------------------
+// shared back half (ctg_records.hip): records (n, with keys (u<<32|v) or
+// (u,v) pairs) -> result
+// ---------------------------------------------------------------------------
+struct ReduceJob {
+    int64_t n;                 // records
+    const uint64_t* keys;      // packed (u<<32)|v, or null if pairs given
+    const uint64_t* pairs;     // (u,v) pairs
+    RecordBuf R;
+    int wide, stats, need_adj, ignore_label, keep_stats;
+    uint64_t max_v;
+    uint64_t min_u = 0;        // smallest u of any key (scan records; 0: unknown)
+    double scale, offset;
+    const uint64_t* single_label_ptr;  // device pointer to a label to use if E == 0
+    const RegionPrefix* regions;       // keys in NREG regions of R (scan records), or null: dense
+    int ub = 0;                        // bits of the key's u field (0: = bits of the largest label)
+    uint64_t umask = ~0ull;            // label bits of u (batched blocks: below the block tag)
+    int skip_nodes = 0;                // batched blocks: nodes come from the per-block unique pass
+    int defer_stats = 0;               // CTG_DEFER_STATS (with keep_stats)
+};
+hipError_t reduce_records(Workspace& w, const ReduceJob& J, hipStream_t s, ctg_result* res);
+
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,
                       int world, uint64_t* spl, int64_t* counts, hipStream_t s);
@@ -365,6 +534,13 @@ hipError_t mgpu_pack(const ctg_result* r, const int64_t* counts_all, int world, 
 hipError_t mgpu_merge(ctg_result* local, const int64_t* recv, const int64_t* counts_all, int world, int rank,
                       double hist_lo, double hist_hi, hipStream_t s, ctg_result* out, int* lib_rc);
 }  // namespace ctg
+
+// in functions that return hipError_t: pass a failure up
+#define CTG_TRY(expr)                        \
+    do {                                     \
+        hipError_t e_ = (expr);              \
+        if (e_ != hipSuccess) return e_;     \
+    } while (0)
 
 #define CTG_CHECK(expr)                                                        \
     do {                                                                       \

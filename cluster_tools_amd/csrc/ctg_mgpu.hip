@@ -435,7 +435,7 @@ __global__ void k_mgpu_node_list(RecvSegs S, const uint64_t* __restrict__ recv, 
 }
 
 // ---------------------------------------------------------------------------
-// launchers (called from ctg_api.hip)
+// launchers (called from ctg_api.hip; declared in ctg_internal.h)
 // ---------------------------------------------------------------------------
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s) {
     hipLaunchKernelGGL(k_mgpu_sample, dim3((MS + 1 + 255) / 256), dim3(256), 0, s, edges, E, meta);
@@ -495,13 +495,9 @@ hipError_t mgpu_pack(const ctg_result* r, const int64_t* counts_all, int world, 
 // exclusive prefix sum of n u32 (rocPRIM, the workspace's temp buffer)
 static hipError_t excl_scan(Workspace& w, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    size_t tb = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
-    if (e != hipSuccess) return e;
-    ensure(&w.temp, w.temp_bytes, tb + 256);
-    if (!w.temp) return hipErrorOutOfMemory;
-    tb = w.temp_bytes;
-    return rocprim::exclusive_scan(w.temp, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
+    return with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+        return rocprim::exclusive_scan(t, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
+    });
 }
 
 static unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
@@ -539,18 +535,11 @@ hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_
     S.row0[S.n] = M;
     rn_off[S.n] = NM;
     const uint64_t* rv = reinterpret_cast<const uint64_t*>(recv);
-    std::vector<void*> tmp;
+    std::vector<DevBuf<void>> tmp;   // back to the pool when the merge returns (stream-ordered reuse)
     auto alloc = [&](size_t bytes) {
-        void* p = dev_alloc(std::max<size_t>(bytes, 16));
-        tmp.push_back(p);
-        return p;
+        tmp.emplace_back(std::max<size_t>(bytes, 16));
+        return tmp.back().p;
     };
-    struct Release {
-        std::vector<void*>& t;
-        ~Release() {
-            for (void* p : t) dev_free(p);   // stream-ordered reuse
-        }
-    } release{tmp};
     hipError_t e = hipSuccess;
 
     // nodes: the own range, or the own range and every received id, unique
@@ -572,8 +561,9 @@ hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_
         hipLaunchKernelGGL(k_mgpu_node_list, dim3(grid_of(total)), dim3(256), 0, s, S, rv, rnd,
                            rnd + CTG_MGPU_MAX_WORLD, L->nodes + n_lo, n_cnt, list, total);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        ctg_result* U = nullptr;
-        const int rc = ctg_unique_values(list, total, CTG_MEM_DEVICE, s, &U);
+        ctg_result* raw = nullptr;
+        const int rc = ctg_unique_values(list, total, CTG_MEM_DEVICE, s, &raw);
+        ResultPtr U(raw);
         if (rc) {   // its status and message pass through
             *lib_rc = rc;
             return hipErrorUnknown;
@@ -582,7 +572,6 @@ hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_
         r->n_nodes = U->n_nodes;
         r->owned.push_back(U->nodes);
         U->nodes = nullptr;
-        ctg_free(U);
     }
 
     // edges and features

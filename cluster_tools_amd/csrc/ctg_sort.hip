@@ -169,14 +169,10 @@ hipError_t bucket_sort_pairs(const uint64_t* keys, const uint32_t* vals, uint64_
         e = hipMemcpyAsync(kout, ktmp, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
         return e != hipSuccess ? e : hipMemcpyAsync(vout, vtmp, (size_t)n * 4, hipMemcpyDeviceToDevice, s);
     }
-    size_t need = 0;
-    e = rocprim::segmented_radix_sort_pairs(nullptr, need, ktmp, kout, vtmp, vout, (unsigned)n, nbk, offs, offs + 1,
-                                            0u, (unsigned)shift, s);
-    if (e != hipSuccess) return e;
-    ensure(temp, *temp_bytes, need + 256);
-    size_t have = *temp_bytes;
-    return rocprim::segmented_radix_sort_pairs(*temp, have, ktmp, kout, vtmp, vout, (unsigned)n, nbk, offs, offs + 1,
-                                               0u, (unsigned)shift, s);
+    return with_temp(*temp, *temp_bytes, [&](void* t, size_t& tb) {
+        return rocprim::segmented_radix_sort_pairs(t, tb, ktmp, kout, vtmp, vout, (unsigned)n, nbk, offs, offs + 1, 0u,
+                                                   (unsigned)shift, s);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -297,14 +293,10 @@ hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, 
     if (shift <= lo_bit) {   // the buckets are the keys: already grouped and ordered
         return hipMemcpyAsync(out, tmp, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
     }
-    size_t need = 0;
-    e = rocprim::segmented_radix_sort_keys(nullptr, need, tmp, out, (unsigned)n, nbk, offs, offs + 1,
-                                           (unsigned)lo_bit, (unsigned)shift, s);
-    if (e != hipSuccess) return e;
-    ensure(temp, *temp_bytes, need + 256);
-    size_t have = *temp_bytes;
-    return rocprim::segmented_radix_sort_keys(*temp, have, tmp, out, (unsigned)n, nbk, offs, offs + 1,
-                                              (unsigned)lo_bit, (unsigned)shift, s);
+    return with_temp(*temp, *temp_bytes, [&](void* t, size_t& tb) {
+        return rocprim::segmented_radix_sort_keys(t, tb, tmp, out, (unsigned)n, nbk, offs, offs + 1, (unsigned)lo_bit,
+                                                  (unsigned)shift, s);
+    });
 }
 
 // ---------------------------------------------------------------------------

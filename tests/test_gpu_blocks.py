@@ -91,6 +91,26 @@ def test_blocks_ignore_label_dense_relabel_without_zero(gpu):
         check_features(out['features'], f_ref)
 
 
+def test_blocks_dense_relabel_uint32_labels(gpu):
+    """The same volume and blocks with uint32 labels shifted by 2^29: 36 blocks
+    take a 6-bit tag, so the labels lie above the tag's range (2^26) and the
+    batched call widens the 32-bit arena before it relabels densely."""
+    shape, block = (26, 41, 70), (8, 16, 32)
+    lab, bnd = S.generate(shape, cell=5, seed=45)
+    big = lab + (np.uint64(1) << np.uint64(29))     # no zeros
+    assert big.max() < (1 << 32)
+    big32 = big.astype(np.uint32)
+    geo = _block_geometry(shape, block)
+    assert len(geo) == 36
+    res = rag.rag_blocks([big32[g['roi']] for g in geo], [g['own'] for g in geo], [g['graph'] for g in geo],
+                         data=[bnd[g['roi']] for g in geo], ignore_label=True)
+    for g, r in zip(geo, res):
+        np.testing.assert_array_equal(r['nodes'], np.unique(big[g['inner']]))
+        eb, f = _expected_boundary(big, bnd, g, ignore_label=True)
+        np.testing.assert_array_equal(r['edges'], eb)
+        check_features(r['features'], f)
+
+
 @pytest.mark.parametrize('dtype', ['float32', 'uint8'])
 def test_blocks_boundary_features(gpu, dtype):
     shape, block = (30, 37, 66), (10, 16, 32)
