@@ -111,19 +111,44 @@ def test_blocks_dense_relabel_uint32_labels(gpu):
         check_features(r['features'], f)
 
 
+def _expected_boundary_stats(lab, bnd, g):
+    """_expected_boundary for the oracle's statistics: the block's owned
+    samples as rows of its graph box's edge list, zero rows for edges seen
+    only on faces the block does not own."""
+    eb = O.rag_edges(lab[g['outer']])
+    sl = g['roi']
+    e_own, _, st = O.boundary_features(lab[sl], bnd[sl], own_begin=g['own'][0], own_end=g['own'][1],
+                                       return_stats=True)
+    rows = O.find_edges(eb, e_own)
+    assert np.all(rows >= 0)
+    stats = {}
+    for name, v in st.items():
+        stats[name] = np.zeros((eb.shape[0],) + v.shape[1:], v.dtype)
+        stats[name][rows] = v
+    return stats
+
+
 @pytest.mark.parametrize('dtype', ['float32', 'uint8'])
 def test_blocks_boundary_features(gpu, dtype):
+    """Features and the mergeable statistics rows (keep_stats) of every
+    block, the rows without owned samples included."""
+    from test_gpu_stats_exact import check_stats
     shape, block = (30, 37, 66), (10, 16, 32)
     lab, bnd = S.generate(shape, cell=5, seed=42)
     data = bnd if dtype == 'float32' else np.round(bnd * 255).astype(np.uint8)
     geo = _block_geometry(shape, block)
     res = rag.rag_blocks([lab[g['roi']] for g in geo], [g['own'] for g in geo], [g['graph'] for g in geo],
                          data=[data[g['roi']] for g in geo], keep_stats=True)
+    empty_rows = 0
     for g, r in zip(geo, res):
         eb, f = _expected_boundary(lab, data, g)
         np.testing.assert_array_equal(r['edges'], eb)
         check_features(r['features'], f)
         assert r['sums'].shape == (eb.shape[0], 2) and r['records'].shape == (eb.shape[0], 48)
+        stats = _expected_boundary_stats(lab, data, g)
+        check_stats(r, stats)
+        empty_rows += int((stats['count'] == 0).sum())
+    assert empty_rows > 0
 
 
 @pytest.mark.parametrize('offsets', [S.NN_OFFSETS, S.LR_OFFSETS])

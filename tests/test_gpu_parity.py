@@ -2,8 +2,14 @@
 and the committed golden fixtures.
 
 Bars (north_star): graph outputs (edges, nodes, counts) bit-exact; mean, var,
-min, max within 1e-5 relative; quantiles within one histogram bin width
-(1/40 on [0,1]).
+min, max within 1e-5 relative.  Quantiles within one histogram bin width
+(1/40 on [0,1]) is the project's bar against nifty, whose parity is unpinned;
+against the project's own oracle nothing in a quantile is approximate: the
+scan bins every sample with the oracle's f64 rule, so the histogram is exact
+(tests/test_gpu_stats_exact.py compares it slot by slot), counts are integers,
+min / max are float32 samples, and the reduce interpolates on the oracle's
+segment with the oracle's formula.  check_features therefore holds the
+quantile columns to QTOL, a few thousand ulp for a compiler's choice of FMAs.
 """
 import json
 import os
@@ -19,19 +25,38 @@ pytestmark = pytest.mark.gpu
 
 RTOL = 1e-5
 ATOL = 0.0
-BIN = 1.0 / 40
+QTOL = 1e-12      # quantiles: same histogram, same formula, another rounding (as _same_result)
+# the largest quantile deviation check_features has seen in this process,
+# absolute and in units of its bound (noted before the assertion)
+QDEV = {'abs': 0.0, 'of_bound': 0.0, 'rows': 0}
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
-def check_features(f_gpu, f_ref):
+def check_features(f_gpu, f_ref, lo=0.0, hi=1.0):
     """north_star bars with no absolute slack: mean / var / min / max within
     1e-5 relative (the variance too: the GPU keeps shifted sums about a
-    per-edge pivot), counts exact, quantiles within one bin."""
+    per-edge pivot), counts exact, and the quantiles of the
+    histogram range [lo, hi] within QTOL * max(|lo|, |hi|, |q_ref|) of the
+    oracle's."""
     assert f_gpu.shape == f_ref.shape
     np.testing.assert_array_equal(f_gpu[:, 9], f_ref[:, 9])            # count exact
     for c in (0, 1, 2, 8):                                               # mean var min max
         np.testing.assert_allclose(f_gpu[:, c], f_ref[:, c], rtol=RTOL, atol=ATOL)
-    np.testing.assert_array_less(np.abs(f_gpu[:, 3:8] - f_ref[:, 3:8]), BIN + 1e-12)
+    check_quantiles(f_gpu[:, 3:8], f_ref[:, 3:8], lo, hi)
+
+
+def check_quantiles(q_gpu, q_ref, lo=0.0, hi=1.0):
+    """The quantile bar of check_features on the five columns q10 .. q90."""
+    assert q_gpu.shape == q_ref.shape and q_ref.shape[1] == 5
+    dev = np.abs(q_gpu - q_ref)
+    bound = QTOL * np.maximum(max(abs(lo), abs(hi)), np.abs(q_ref))
+    if dev.size:
+        QDEV['abs'] = max(QDEV['abs'], float(np.nanmax(dev)))
+        QDEV['of_bound'] = max(QDEV['of_bound'], float(np.nanmax(dev / bound)))
+        QDEV['rows'] += dev.shape[0]
+    bad = ~(dev <= bound)                                                # (a NaN is a miss)
+    assert not bad.any(), 'quantiles off at %d of %d rows: largest deviation %.3g (bound %.3g), first rows %s' % (
+        bad.any(axis=1).sum(), dev.shape[0], np.nanmax(dev), bound.min(), np.flatnonzero(bad.any(axis=1))[:8])
 
 
 @pytest.fixture(scope='module')
@@ -206,9 +231,7 @@ def test_values_outside_range_and_custom_range(gpu):
     e_ref, f_ref = O.boundary_features(lab, data, lo=-1.0, hi=2.0)
     out = rag.rag_features(lab, data, hist_range=(-1.0, 2.0))
     np.testing.assert_array_equal(out['edges'], e_ref)
-    f = out['features']
-    np.testing.assert_array_equal(f[:, 9], f_ref[:, 9])
-    np.testing.assert_array_less(np.abs(f[:, 3:8] - f_ref[:, 3:8]), 3.0 / 40 + 1e-12)
+    check_features(out['features'], f_ref, lo=-1.0, hi=2.0)
 
 
 def test_single_label_and_empty(gpu):

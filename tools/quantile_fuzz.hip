@@ -1,12 +1,75 @@
 // Host-side check that vigra_quantiles_cross (crossing search) and
 // vigra_quantiles (keypoint walk) give bit-identical quantiles.
 // build: hipcc -O2 -std=c++17 --offload-arch=gfx950 tools/quantile_fuzz.hip -o /tmp/qfuzz && /tmp/qfuzz
+//
+// --dump N SEED: N seeded cases of float32 samples binned with ctg::hist_slot
+// and finalised with vigra_quantiles_cross, one line each, for the Python
+// oracle to re-derive (tests/test_abi.py::test_host_statistics_match_python_oracle):
+//   kind lo hi n min max, the 42 slots, q10 q25 q50 q75 q90, the n samples' f32 bits (hex); blank-separated
+// kind 0..2: ranges [0,1], [-1,2], [-0.37,0.91]; kind 3: u8 samples k/255 on [0,1].
 #include "../cluster_tools_amd/csrc/ctg_reduce.hip"
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
 
-int main() {
+static int dump(long n_cases, uint64_t seed) {
+    std::mt19937_64 rng(seed);
+    static const double LO[4] = {0.0, -1.0, -0.37, 0.0}, HI[4] = {1.0, 2.0, 0.91, 1.0};
+    auto unit = [&]() { return (double)(rng() >> 11) * (1.0 / 9007199254740992.0); };
+    for (long it = 0; it < n_cases; ++it) {
+        const int kind = (int)(it % 4);
+        const double lo = LO[kind], hi = HI[kind], w = hi - lo;
+        const double scale = (double)ctg::NBINS / w, offset = lo;   // as ctg_rag_features sets them
+        const int shape = (int)(rng() % 4);   // 0: any sample kind, 1: edges and their neighbours only,
+                                              // 2: one to three bins, 3: few samples
+        const int n = 1 + (int)(rng() % (shape == 3 ? 4 : 48));
+        const int k0 = (int)(rng() % ctg::NBINS), nk = 1 + (int)(rng() % 3);
+        float x[48];
+        uint32_t h[ctg::NSLOTS] = {0};
+        for (int j = 0; j < n; ++j) {
+            float v;
+            if (kind == 3) {
+                v = (float)(rng() % 256) / 255.0f;
+            } else {
+                const int pick = shape == 1 ? 1 + (int)(rng() % 3) : (int)(rng() % 7);
+                const int k = shape == 2 ? std::min(k0 + (int)(rng() % nk), (int)ctg::NBINS) : (int)(rng() % (ctg::NBINS + 1));
+                const float edge = (float)(lo + (double)k * w / (double)ctg::NBINS);
+                if (pick == 0 || (shape == 2 && pick > 3)) v = (float)(lo + ((double)k + unit()) * w / (double)ctg::NBINS);
+                else if (pick == 1) v = edge;
+                else if (pick == 2) v = std::nextafterf(edge, INFINITY);
+                else if (pick == 3) v = std::nextafterf(edge, -INFINITY);
+                else if (pick == 4) v = (float)(lo - unit() * w);                               // left of the range
+                else if (pick == 5) v = (float)(hi + unit() * w);                               // right of the range
+                else v = (float)(lo - unit() * w / (double)ctg::NBINS);                         // (-1, 0] bins: bin 0
+            }
+            x[j] = v;
+            ++h[ctg::hist_slot((double)v, scale, offset)];
+        }
+        float mn = x[0], mx = x[0];
+        for (int j = 1; j < n; ++j) {
+            mn = std::fmin(mn, x[j]);
+            mx = std::fmax(mx, x[j]);
+        }
+        double q[5] = {0, 0, 0, 0, 0};
+        ctg::vigra_quantiles_cross(h, (double)n, (double)mn, (double)mx, scale, offset, q);
+        std::printf("%d %.17g %.17g %d %.17g %.17g", kind, lo, hi, n, (double)mn, (double)mx);
+        for (int s = 0; s < ctg::NSLOTS; ++s) std::printf(" %u", h[s]);
+        for (int i = 0; i < 5; ++i) std::printf(" %.17g", q[i]);
+        for (int j = 0; j < n; ++j) {
+            uint32_t b;
+            std::memcpy(&b, &x[j], 4);
+            std::printf(" %08x", b);
+        }
+        std::printf("\n");
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 4 && std::strcmp(argv[1], "--dump") == 0)
+        return dump(std::atol(argv[2]), (uint64_t)std::strtoull(argv[3], nullptr, 10));
     std::mt19937_64 rng(12345);
     long bad = 0, n = 0;
     for (int it = 0; it < 2000000; ++it) {
