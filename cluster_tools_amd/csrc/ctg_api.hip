@@ -1,7 +1,7 @@
 // C ABI of libctg.so (include/ctg.h): the entry points -- host orchestration
 // of the face scan and the result handles.  The allocator and the workspace
-// live in ctg_workspace.hip, the record back half in ctg_records.hip, the host
-// decisions in ctg_plan.h.
+// live in ctg_workspace.hip (ctg_pool.h, ctg_buffers.h), the record back half
+// in ctg_records.hip, the host decisions in ctg_plan.h.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -46,19 +46,17 @@ static int nested(ResultPtr& r, Call&& call) {
     return rc;
 }
 
-static int stage_in(Workspace& w, int slot, const void* src, size_t bytes, int mem, hipStream_t s,
-                    const void** dev) {
+static int stage_in(GrowBuf& stage, const void* src, size_t bytes, int mem, hipStream_t s, const void** dev) {
     if (mem == CTG_MEM_DEVICE || src == nullptr) {
         *dev = src;
         return CTG_OK;
     }
-    ensure(&w.stage[slot], w.stage_bytes[slot], bytes);
-    if (!w.stage[slot]) {
+    if (!stage.reserve(bytes)) {
         set_error("out of device memory staging input");
         return CTG_ERR_NOMEM;
     }
-    CTG_CHECK(hipMemcpyAsync(w.stage[slot], src, bytes, hipMemcpyHostToDevice, s));
-    *dev = w.stage[slot];
+    CTG_CHECK(hipMemcpyAsync(stage.p, src, bytes, hipMemcpyHostToDevice, s));
+    *dev = stage.p;
     return CTG_OK;
 }
 
@@ -88,17 +86,17 @@ static hipError_t sort_unique_u64(Workspace& w, const uint64_t* in, int64_t n, u
                                   hipStream_t s, unsigned end_bit = 64u) {
     DevBuf<uint64_t> sorted(std::max<int64_t>(n, 1) * 8);
     if (!sorted) return hipErrorOutOfMemory;
-    hipError_t e = with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+    hipError_t e = with_temp(w.temp, [&](void* t, size_t& tb) {
         return rocprim::radix_sort_keys(t, tb, in, (uint64_t*)sorted, (size_t)n, 0u, end_bit, s);
     });
     if (e != hipSuccess) return e;
-    return with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+    return with_temp(w.temp, [&](void* t, size_t& tb) {
         return rocprim::unique(t, tb, (uint64_t*)sorted, out, count_dev, (size_t)n, rocprim::equal_to<uint64_t>(), s);
     });
 }
 
 // one u32 device word, after everything queued on s
-static int read_word(Workspace& w, int i, hipStream_t s, int64_t* v) {
+static int read_word(Workspace& w, SmallSlot i, hipStream_t s, int64_t* v) {
     CTG_CHECK(hipMemcpyAsync(w.small_host + i, w.small + i, 4, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
     *v = w.small_host[i];
@@ -374,8 +372,8 @@ static int block_nodes(Workspace& w, const void* dl, int label_bits, const Block
             continue;
         }
         int64_t N = 0;
-        CTG_CHECK(sort_unique_u64(w, cand, m, nodes, w.small + 2, s, 32u + (unsigned)bits_u(n_blocks - 1)));
-        if (int rc = read_word(w, 2, s, &N)) return rc;
+        CTG_CHECK(sort_unique_u64(w, cand, m, nodes, w.small + SLOT_NODES, s, 32u + (unsigned)bits_u(n_blocks - 1)));
+        if (int rc = read_word(w, SLOT_NODES, s, &N)) return rc;
         CTG_CHECK(launch_block_bounds(N, nodes, 1, n_blocks, 32, bounds, s));
         r->node_off.assign(n_blocks + 1, 0);
         CTG_CHECK(hipMemcpyAsync(r->node_off.data(), bounds, (n_blocks + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -628,9 +626,9 @@ int ctg_rag_features(const void* labels, int label_bits, const void* data, int d
     const size_t dbytes = data ? (size_t)V * (n_channels > 0 ? n_channels : 1) * (data_kind == CTG_DATA_U8 ? 1 : 4) : 0;
     const void* dl = nullptr;
     const void* dd = nullptr;
-    int rc = stage_in(w, 0, labels, lbytes, mem, s, &dl);
+    int rc = stage_in(w.stage[0], labels, lbytes, mem, s, &dl);
     if (rc) return rc;
-    rc = stage_in(w, 1, data, dbytes, mem, s, &dd);
+    rc = stage_in(w.stage[1], data, dbytes, mem, s, &dd);
     if (rc) return rc;
 
     ScanParams P;
@@ -665,10 +663,10 @@ int ctg_rag_features(const void* labels, int label_bits, const void* data, int d
         if (nr) {
             P.narrow_rows = atoi(nr) ? 1 : 0;
         } else {
-            CTG_CHECK(hipMemsetAsync(w.small + 4, 0, 8, s));
-            CTG_CHECK(launch_density(dl, label_bits, shape, 512, w.small + 4, s));
+            P.density = w.small + SLOT_DENSITY;
+            CTG_CHECK(hipMemsetAsync(w.small + SLOT_DENSITY, 0, 2 * sizeof(uint32_t), s));
+            CTG_CHECK(launch_density(dl, label_bits, shape, 512, w.small + SLOT_DENSITY, s));
             P.narrow_rows = 2;
-            P.density = w.small + 4;
         }
     }
 
@@ -692,7 +690,6 @@ int ctg_rag_features(const void* labels, int label_bits, const void* data, int d
         }
     } adj_release{bloom, adj_graph, s};
 
-    if (data) w.last_ms[7] = 0.0;   // the narrowing pass of earlier builds: no longer run
     if (cc.long_range && !(flags & CTG_NO_ADJ_FILTER) && V > 0) {
         rc = ctg_rag_features(dl, label_bits, nullptr, CTG_DATA_NONE, 0, nullptr, shape, own_begin, own_end, 0,
                               hist_lo, hist_hi, 0, CTG_MEM_DEVICE, stream, &adj_graph);
@@ -862,9 +859,9 @@ int ctg_rag_blocks(const void* labels, int label_bits, const void* data, int dat
     hipStream_t s = (hipStream_t)stream;
     const void* dl = nullptr;
     const void* dd = nullptr;
-    int rc = stage_in(w, 0, labels, (size_t)labels_len * (label_bits / 8), mem, s, &dl);
+    int rc = stage_in(w.stage[0], labels, (size_t)labels_len * (label_bits / 8), mem, s, &dl);
     if (rc) return rc;
-    rc = stage_in(w, 1, data, data ? (size_t)data_len * (data_kind == CTG_DATA_U8 ? 1 : 4) : 0, mem, s, &dd);
+    rc = stage_in(w.stage[1], data, data ? (size_t)data_len * (data_kind == CTG_DATA_U8 ? 1 : 4) : 0, mem, s, &dd);
     if (rc) return rc;
 
     ScanParams P;
@@ -1047,7 +1044,7 @@ int ctg_unique_labels(const uint64_t* labels, const int64_t* shape, const int64_
     hipStream_t s = (hipStream_t)stream;
     const int64_t V = shape[0] * shape[1] * shape[2];
     const void* dl = nullptr;
-    int rc = stage_in(w, 0, labels, (size_t)V * 8, mem, s, &dl);
+    int rc = stage_in(w.stage[0], labels, (size_t)V * 8, mem, s, &dl);
     if (rc) return rc;
     const int64_t nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
     if (nb == 0) {
@@ -1071,8 +1068,8 @@ int ctg_unique_labels(const uint64_t* labels, const int64_t* shape, const int64_
             cap = std::min<int64_t>(nb, m + 1024);
             continue;
         }
-        CTG_CHECK(sort_unique_u64(w, cand, m, nodes, w.small + 2, s));
-        if ((rc = read_word(w, 2, s, &r->n_nodes)) != CTG_OK) return rc;
+        CTG_CHECK(sort_unique_u64(w, cand, m, nodes, w.small + SLOT_NODES, s));
+        if ((rc = read_word(w, SLOT_NODES, s, &r->n_nodes)) != CTG_OK) return rc;
         r->nodes = nodes.release();
         r->edges = (uint64_t*)dev_alloc(16);
         *out = r.release();
@@ -1107,8 +1104,8 @@ int ctg_unique_values(const uint64_t* values, int64_t n, int mem, void* stream, 
     DevInput<uint64_t> in;
     int rc = in.put(values, (size_t)n * 8, mem, s, "ctg_unique_values");
     if (rc) return rc;
-    CTG_CHECK(sort_unique_u64(w, in, n, r->nodes, w.small + 2, s));
-    if ((rc = read_word(w, 2, s, &r->n_nodes)) != CTG_OK) return rc;
+    CTG_CHECK(sort_unique_u64(w, in, n, r->nodes, w.small + SLOT_NODES, s));
+    if ((rc = read_word(w, SLOT_NODES, s, &r->n_nodes)) != CTG_OK) return rc;
     *out = r.release();
     return CTG_OK;
 }
@@ -1189,18 +1186,18 @@ int ctg_merge_feature_rows(const uint64_t* ids, const double* rows, int64_t n, i
             set_error("ctg_merge_feature_rows: out of device memory");
             return CTG_ERR_NOMEM;
         }
-        CTG_CHECK(hipMemsetAsync(w.small + 3, 0, 4, s));
-        CTG_CHECK(launch_row_keys(n, di, (uint64_t)id_begin, (uint64_t)id_end, k_in, i_in, w.small + 3, s));
+        CTG_CHECK(hipMemsetAsync(w.small + SLOT_BAD_ID, 0, 4, s));
+        CTG_CHECK(launch_row_keys(n, di, (uint64_t)id_begin, (uint64_t)id_end, k_in, i_in, w.small + SLOT_BAD_ID, s));
         const unsigned kb = (unsigned)bits_for((uint64_t)std::max<int64_t>(E - 1, 1));
-        CTG_CHECK(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+        CTG_CHECK(with_temp(w.temp, [&](void* t, size_t& tb) {
             return rocprim::radix_sort_pairs(t, tb, k_in.p, k_out.p, i_in.p, i_out.p, (size_t)n, 0u, kb, s);
         }));
         CTG_CHECK(launch_merge_feature_rows(n, k_out, i_out, dr, dout, s));
-        CTG_CHECK(hipMemcpyAsync(w.small_host + 3, w.small + 3, 4, hipMemcpyDeviceToHost, s));
+        CTG_CHECK(hipMemcpyAsync(w.small_host + SLOT_BAD_ID, w.small + SLOT_BAD_ID, 4, hipMemcpyDeviceToHost, s));
     }
     if (host) CTG_CHECK(hipMemcpyAsync(out, dout, E * N_FEATURES * 8, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
-    if (n && w.small_host[3]) {
+    if (n && w.small_host[SLOT_BAD_ID]) {
         set_error("ctg_merge_feature_rows: an edge id lies outside [id_begin, id_end)");
         return CTG_ERR_ARG;
     }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/ctg.h"
+#include "ctg_buffers.h"
 #include "ctg_plan.h"
 
 namespace ctg {
@@ -285,36 +286,52 @@ struct ReduceOut {
 constexpr int BK_SMALL_WORDS = 5 * 4096 + 16;   // bucket sort: counts, offsets, cursors, run heads
 constexpr int GS_SMALL_WORDS = 5 * 65536 + 16;   // group sort: counts, offsets, cursors, misc, run counts / offsets (5M + 9)
 
+// The scalar words of Workspace::small (device) and, at the same index,
+// Workspace::small_host (pinned): who owns which.
+enum SmallSlot : int {
+    SLOT_RUNS = 0,         // reduce_records: runs, kept edges, nodes -- read back together
+    SLOT_EDGES = 1,
+    SLOT_NODES = 2,        // (also the count of the unique-label entry points)
+    SLOT_BAD_ID = 3,       // ctg_merge_feature_rows: an id outside the block
+    SLOT_DENSITY = 4,      // 2 words: the density probe's changes / pairs
+    SLOT_GROUP_SORT = 16,  // host word of the group sort
+    SLOT_MERGE = 20,       // 2 words: MergeCounts (ctg_mgpu.hip)
+    SLOT_HEAVY = 40,       // edges listed for the wide-histogram kernel
+    SMALL_WORDS = 64
+};
+struct MergeCounts {       // the multi-GPU merge's pair at SLOT_MERGE, cleared as one
+    uint32_t keys;         // distinct received keys
+    uint32_t rows;         // rows of the shard
+};
+// each slot ends where the next begins or before it, the last one below SMALL_WORDS: disjoint and in range
+static_assert(SLOT_RUNS >= 0 && SLOT_RUNS + 1 <= SLOT_EDGES && SLOT_EDGES + 1 <= SLOT_NODES &&
+                  SLOT_NODES + 1 <= SLOT_BAD_ID && SLOT_BAD_ID + 1 <= SLOT_DENSITY &&
+                  SLOT_DENSITY + 2 <= SLOT_GROUP_SORT && SLOT_GROUP_SORT + 1 <= SLOT_MERGE &&
+                  SLOT_MERGE + (int)(sizeof(MergeCounts) / 4) <= SLOT_HEAVY && SLOT_HEAVY + 1 <= SMALL_WORDS,
+              "the scalar slots overlap or pass SMALL_WORDS");
+
 struct Workspace {
+    bool ready = false;   // ws_init made every fixed member (counters .. mgpu_spl, ev); set last
     int device = -1;
     // bumped by every call that overwrites the records or the sort / run
     // buffers (a CTG_DEFER_STATS handle compares it)
     uint64_t gen = 1;
     RecordBuf rec;
-    // sort / reduce scratch
-    uint64_t* sk_in = nullptr; uint64_t* sk_out = nullptr;
-    uint32_t* idx_in = nullptr; uint32_t* idx_out = nullptr;
-    int64_t sort_cap = 0;
-    uint64_t* uniq = nullptr; uint32_t* runs = nullptr; uint32_t* offs = nullptr;
-    uint32_t* keep = nullptr; uint32_t* pos = nullptr;
-    int64_t edge_cap = 0;
-    void* temp = nullptr; size_t temp_bytes = 0;
+    SortScratch sort;   // sort / reduce scratch
+    GrowBuf temp;       // rocPRIM's temporary storage (with_temp)
     Counters* counters = nullptr;        // device
     Counters* counters_host = nullptr;   // pinned
-    unsigned int* small = nullptr;       // device scalars (run counts etc.)
+    unsigned int* small = nullptr;       // device scalars, SMALL_WORDS of them (SmallSlot)
     unsigned int* small_host = nullptr;
     uint32_t* bsort = nullptr;           // device: bucket-sort scratch, BK_SMALL_WORDS u32 (ctg_sort.hip)
     uint32_t* gsort = nullptr;           // device: group-sort scratch, GS_SMALL_WORDS u32 (ctg_sort.hip)
     uint64_t* mgpu_spl = nullptr;        // device: the exchange's splitters, CTG_MGPU_MAX_WORLD u64
     hipEvent_t mgpu_spl_ev = nullptr;    // recorded after the last split read mgpu_spl (a split on another
                                          // stream waits for it before overwriting the splitters)
-    // host->device staging of volumes
-    void* stage[2] = {nullptr, nullptr};
-    size_t stage_bytes[2] = {0, 0};
+    GrowBuf stage[2];   // host->device staging of volumes
     // timing
-    hipEvent_t ev[10];   // 0..6 phases of a call; 8, 9 bracket the label narrowing (prep)
-    bool events = false;
-    double last_ms[8] = {0};   // scan, pack, sort, segment, reduce, nodes, total, narrow
+    hipEvent_t ev[7] = {};   // 0..6: the phase marks of a call
+    double last_ms[8] = {0};   // scan, pack, sort, segment, reduce, nodes, total, narrow (always 0: no such pass)
     int64_t last_records = 0, last_direct = 0;
     int profiling = 0;
 };
@@ -326,15 +343,8 @@ Workspace& ws(int device);
 hipError_t ws_init(Workspace& w);
 int current_device();
 void set_error(const std::string& msg);
-void ensure(void** p, size_t& have, size_t need);
 void free_records(Workspace& w);
 hipError_t ensure_records(Workspace& w, int64_t need, int wide);
-// the library's caching device allocator (ctg_workspace.hip).  dev_free only
-// returns the block to the host-side pool: kernels already queued on the
-// stream still use it, and a later user of the block runs after them
-// ("stream-ordered reuse")
-void* dev_alloc(size_t bytes);
-void dev_free(void* p);
 
 // One workspace per device: calls that use it are serialised per device, so
 // job threads may call the library concurrently (ctypes drops the GIL) --
@@ -346,36 +356,16 @@ struct DevLock {
     DevLock() : g(device_mutex(current_device())) {}
 };
 
-// A block of the caching allocator that goes back to the pool when its scope
-// ends (every early return included); reset() returns it sooner, release()
-// hands it to a result.  Sizes are in bytes.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    DevBuf() = default;
-    explicit DevBuf(size_t bytes) : p((T*)dev_alloc(bytes)) {}
-    DevBuf(DevBuf&& o) noexcept : p(o.release()) {}   // (move-only: no copy is declared)
-    ~DevBuf() { dev_free(p); }
-    T* alloc(size_t bytes) { return reset((T*)dev_alloc(bytes)); }
-    T* reset(T* q = nullptr) {
-        dev_free(std::exchange(p, q));
-        return p;
-    }
-    T* release() { return std::exchange(p, nullptr); }
-    operator T*() const { return p; }
-};
-
 // rocPRIM call with a growable temp buffer: size query (null temp), grow, run.
 // call: (void* temp, size_t& bytes) -> hipError_t
 template <class F>
-hipError_t with_temp(void*& temp, size_t& temp_bytes, F&& call) {
+hipError_t with_temp(GrowBuf& temp, F&& call) {
     size_t bytes = 0;
     hipError_t e = call(nullptr, bytes);
     if (e != hipSuccess) return e;
-    ensure(&temp, temp_bytes, bytes + 256);
-    if (!temp) return hipErrorOutOfMemory;
-    bytes = temp_bytes;
-    return call(temp, bytes);
+    if (!temp.reserve(bytes + 256)) return hipErrorOutOfMemory;
+    bytes = temp.bytes;
+    return call(temp.p, bytes);
 }
 
 struct Ev {   // phase marks of a profiled call
@@ -403,13 +393,13 @@ hipError_t launch_unique_blocks(const void* L, int label_bits, const BlockGeom* 
 int unique_tile_y();
 // ctg_sort.hip
 hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, int64_t n, int lo_bit, int hi_bit,
-                            uint64_t kmin, uint64_t kmax, uint32_t* small, void** temp, size_t* temp_bytes,
-                            uint32_t* nbk_out, hipStream_t s);
+                            uint64_t kmin, uint64_t kmax, uint32_t* small, GrowBuf& temp, uint32_t* nbk_out,
+                            hipStream_t s);
 hipError_t bucket_runs(const uint64_t* sorted, int64_t n, int lo_bit, uint32_t nbk, uint32_t* small, uint64_t* uniq,
                        uint32_t* runs, uint32_t* roffs, uint32_t* dE, hipStream_t s);
 hipError_t bucket_sort_pairs(const uint64_t* keys, const uint32_t* vals, uint64_t* ktmp, uint32_t* vtmp,
-                             uint64_t* kout, uint32_t* vout, int64_t n, int hi_bit, uint32_t* small, void** temp,
-                             size_t* temp_bytes, uint32_t* nbk_out, hipStream_t s);
+                             uint64_t* kout, uint32_t* vout, int64_t n, int hi_bit, uint32_t* small, GrowBuf& temp,
+                             uint32_t* nbk_out, hipStream_t s);
 hipError_t group_sort_runs(const uint64_t* key, int64_t rcap, const RegionPrefix& pre, int64_t n, int nb, int ub,
                            int ib, uint64_t min_label, uint64_t max_label, uint32_t* small, uint32_t* host_word,
                            uint64_t* items, uint32_t* perm, uint64_t* uniq, uint32_t* runs, uint32_t* roffs,

@@ -493,9 +493,9 @@ hipError_t mgpu_pack(const ctg_result* r, const int64_t* counts_all, int world, 
 
 
 // exclusive prefix sum of n u32 (rocPRIM, the workspace's temp buffer)
-static hipError_t excl_scan(Workspace& w, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s) {
+static hipError_t excl_scan(GrowBuf& temp, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    return with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+    return with_temp(temp, [&](void* t, size_t& tb) {
         return rocprim::exclusive_scan(t, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
     });
 }
@@ -621,8 +621,9 @@ hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_
     const int64_t n_slots = e_cnt + M;
     uint32_t* keep = (uint32_t*)alloc(std::max<int64_t>(n_slots, 1) * 4);
     uint32_t* fpos = (uint32_t*)alloc(std::max<int64_t>(n_slots, 1) * 4);
-    uint32_t* nK = w.small + 20;
-    uint32_t* n_out = w.small + 21;
+    MergeCounts* mc = reinterpret_cast<MergeCounts*>(w.small + SLOT_MERGE);
+    uint32_t* nK = &mc->keys;
+    uint32_t* n_out = &mc->rows;
     if (!order || !skeys || !head || !rid || !run0 || !mkeys || !mfeats || !mkeep || !mnew || !nrank || !mins ||
         !touched || !keep || !fpos)
         return hipErrorOutOfMemory;
@@ -636,22 +637,22 @@ hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_
     io.mnew = mnew;
     io.mins = mins;
     io.touched = touched;
-    if ((e = hipMemsetAsync(nK, 0, 8, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(mc, 0, sizeof(MergeCounts), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(mnew, 0, Mb * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(touched, 0, std::max<int64_t>(e_cnt, 1) * 4, s)) != hipSuccess) return e;
     if (M > 0) {
         hipLaunchKernelGGL(k_mgpu_order, dim3(grid_of(M)), dim3(256), 0, s, S, rv, order, skeys);
         hipLaunchKernelGGL(k_mgpu_heads, dim3(grid_of(M)), dim3(256), 0, s, M, skeys, head);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = excl_scan(w, head, rid, M, s)) != hipSuccess) return e;
+        if ((e = excl_scan(w.temp, head, rid, M, s)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_mgpu_runs, dim3(grid_of(M)), dim3(256), 0, s, M, head, rid, run0, nK);
         hipLaunchKernelGGL(k_mgpu_combine, dim3(grid_of(M)), dim3(256), 0, s, S, io);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = excl_scan(w, mnew, nrank, M, s)) != hipSuccess) return e;
+        if ((e = excl_scan(w.temp, mnew, nrank, M, s)) != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_mgpu_slots, dim3(grid_of(n_slots)), dim3(256), 0, s, io, nrank, keep, n_slots);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = excl_scan(w, keep, fpos, n_slots, s)) != hipSuccess) return e;
+    if ((e = excl_scan(w.temp, keep, fpos, n_slots, s)) != hipSuccess) return e;
     r->edges = (uint64_t*)dev_alloc((size_t)std::max<int64_t>(n_slots, 1) * 16);
     r->features = (double*)dev_alloc((size_t)std::max<int64_t>(n_slots, 1) * N_FEATURES * 8);
     r->owned.push_back(r->edges);
@@ -660,9 +661,10 @@ hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_
     hipLaunchKernelGGL(k_mgpu_scatter, dim3(grid_of(n_slots)), dim3(256), 0, s, io, nrank, keep, fpos, n_slots,
                        r->edges, r->features, n_out);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(w.small_host + 21, n_out, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+    uint32_t* rows_host = &reinterpret_cast<MergeCounts*>(w.small_host + SLOT_MERGE)->rows;
+    if ((e = hipMemcpyAsync(rows_host, n_out, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    r->n_edges = n_slots ? w.small_host[21] : 0;
+    r->n_edges = n_slots ? *rows_host : 0;
     return hipSuccess;
 }
 

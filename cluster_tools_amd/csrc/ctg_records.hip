@@ -53,20 +53,22 @@ static SortSwitches sort_switches() {
     return sw;
 }
 
-// Step 1's result: the runs of equal keys lie in w.uniq / w.runs / w.offs,
-// their count in w.small[0]; sorted position r is record slot perm(r).
+// Step 1's result: the runs of equal keys lie in the sort scratch's uniq /
+// runs / offs, their count in w.small[SLOT_RUNS]; sorted position r is record
+// slot perm(r).
 struct RunTable {
-    bool packed;   // the slots are the low ib bits of w.sk_out (else the u32 permutation w.idx_out)
+    bool packed;   // the slots are the low ib bits of sk_out (else the u32 permutation idx_out)
     int ib;
-    Perm perm(const Workspace& w) const {
-        return Perm{packed ? nullptr : w.idx_out, packed ? w.sk_out : nullptr, packed ? ib : 0};
+    Perm perm(const SortScratch& S) const {
+        return Perm{packed ? nullptr : S.idx_out, packed ? S.sk_out : nullptr, packed ? ib : 0};
     }
 };
 
 // record sort -> run table (phase marks 2, 3)
 static hipError_t sort_to_runs(Workspace& w, const ReduceJob& J, int nb, int ub, Ev& ev, hipStream_t s, RunTable& T) {
     const int64_t n = J.n;
-    uint32_t* dE_all = w.small;
+    const SortScratch& S = w.sort;
+    uint32_t* dE_all = w.small + SLOT_RUNS;
     hipError_t e = hipSuccess;
     const int ib = J.regions ? bits_for((uint64_t)std::max<int64_t>(J.R.cap - 1, 1)) : 0;
     // block-tagged keys (ctg_rag_blocks, J.ub set) are not spread over their top bits
@@ -78,7 +80,7 @@ static hipError_t sort_to_runs(Workspace& w, const ReduceJob& J, int nb, int ub,
         bool grouped = false;
         ev.mark(2);   // (phases: the whole group sort is "sort")
         CTG_TRY(group_sort_runs(J.keys, J.R.rcap, *J.regions, n, nb, ub, ib, J.min_u, J.max_v, w.gsort,
-                                w.small_host + 16, w.sk_out, w.idx_out, w.uniq, w.runs, w.offs, dE_all, &grouped, s));
+                                w.small_host + SLOT_GROUP_SORT, S.sk_out, S.idx_out, S.uniq, S.runs, S.offs, dE_all, &grouped, s));
         if (grouped) {
             ev.mark(3);
             T.packed = false;   // (key, slot) runs and a u32 slot permutation, as for unpackable records
@@ -86,9 +88,9 @@ static hipError_t sort_to_runs(Workspace& w, const ReduceJob& J, int nb, int ub,
         }
     }
     if (J.keys && J.regions)
-        e = launch_pack_regions(J.keys, J.R.rcap, *J.regions, nb, T.packed ? ib : 0, w.sk_in, w.idx_in, s);
-    else if (J.keys) e = launch_pack_keys(n, J.keys, nb, w.sk_in, w.idx_in, s);
-    else e = launch_pack_pairs(n, J.pairs, nb, w.sk_in, w.idx_in, s);
+        e = launch_pack_regions(J.keys, J.R.rcap, *J.regions, nb, T.packed ? ib : 0, S.sk_in, S.idx_in, s);
+    else if (J.keys) e = launch_pack_keys(n, J.keys, nb, S.sk_in, S.idx_in, s);
+    else e = launch_pack_pairs(n, J.pairs, nb, S.sk_in, S.idx_in, s);
     if (e != hipSuccess) return e;
     ev.mark(2);
     bool have_offs = false;   // run offsets already written (bucket paths)
@@ -98,57 +100,57 @@ static hipError_t sort_to_runs(Workspace& w, const ReduceJob& J, int nb, int ub,
         // 4 fused launches instead of 4 onesweep passes with their fills
         const KeyRange kr = packed_key_range(J.min_u, J.max_v, nb, ib);
         uint32_t nbk = 0;
-        CTG_TRY(bucket_sort_keys(w.sk_in, w.uniq, w.sk_out, n, ib, ib + ub + nb, kr.kmin, kr.kmax, w.bsort, &w.temp,
-                                 &w.temp_bytes, &nbk, s));
+        CTG_TRY(bucket_sort_keys(S.sk_in, S.uniq, S.sk_out, n, ib, ib + ub + nb, kr.kmin, kr.kmax, w.bsort, w.temp,
+                                 &nbk, s));
         ev.mark(3);
         // runs from the buckets: unique keys, lengths and offsets in one go
-        e = bucket_runs(w.sk_out, n, ib, nbk, w.bsort, w.uniq, w.runs, w.offs, dE_all, s);
+        e = bucket_runs(S.sk_out, n, ib, nbk, w.bsort, S.uniq, S.runs, S.offs, dE_all, s);
         have_offs = true;
         break;
     }
     case SortPath::OnesweepKeys: {
-        CTG_TRY(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
-            return rocprim::radix_sort_keys<RecordSortConfig>(t, tb, w.sk_in, w.sk_out, (size_t)n, (unsigned)ib,
+        CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
+            return rocprim::radix_sort_keys<RecordSortConfig>(t, tb, S.sk_in, S.sk_out, (size_t)n, (unsigned)ib,
                                                               (unsigned)(ib + ub + nb), s);
         }));
         ev.mark(3);
-        auto key_only = rocprim::make_transform_iterator(w.sk_out, [ib] __device__(uint64_t k) { return k >> ib; });
-        e = with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
-            return rocprim::run_length_encode(t, tb, key_only, (unsigned)n, w.uniq, w.runs, dE_all, s);
+        auto key_only = rocprim::make_transform_iterator(S.sk_out, [ib] __device__(uint64_t k) { return k >> ib; });
+        e = with_temp(w.temp, [&](void* t, size_t& tb) {
+            return rocprim::run_length_encode(t, tb, key_only, (unsigned)n, S.uniq, S.runs, dE_all, s);
         });
         break;
     }
     case SortPath::BucketPairs: {
-        // tmp buffers: w.uniq (keys) and w.keep (values) are free until the
+        // tmp buffers: S.uniq (keys) and S.keep (values) are free until the
         // run-length pass / the reduction
         uint32_t nbk = 0;
-        CTG_TRY(bucket_sort_pairs(w.sk_in, w.idx_in, w.uniq, w.keep, w.sk_out, w.idx_out, n, ub + nb, w.bsort,
-                                  &w.temp, &w.temp_bytes, &nbk, s));
+        CTG_TRY(bucket_sort_pairs(S.sk_in, S.idx_in, S.uniq, S.keep, S.sk_out, S.idx_out, n, ub + nb, w.bsort,
+                                  w.temp, &nbk, s));
         ev.mark(3);
         // runs never cross the MSD buckets: unique keys, lengths and offsets per bucket
-        e = bucket_runs(w.sk_out, n, 0, nbk, w.bsort, w.uniq, w.runs, w.offs, dE_all, s);
+        e = bucket_runs(S.sk_out, n, 0, nbk, w.bsort, S.uniq, S.runs, S.offs, dE_all, s);
         have_offs = true;
         break;
     }
     case SortPath::OnesweepPairsWide:
     case SortPath::OnesweepPairsDefault:
-        CTG_TRY(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+        CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
             return plan.path == SortPath::OnesweepPairsWide
-                       ? rocprim::radix_sort_pairs<RecordSortConfig>(t, tb, w.sk_in, w.sk_out, w.idx_in, w.idx_out,
+                       ? rocprim::radix_sort_pairs<RecordSortConfig>(t, tb, S.sk_in, S.sk_out, S.idx_in, S.idx_out,
                                                                      (size_t)n, 0u, (unsigned)(ub + nb), s)
-                       : rocprim::radix_sort_pairs(t, tb, w.sk_in, w.sk_out, w.idx_in, w.idx_out, (size_t)n, 0u,
+                       : rocprim::radix_sort_pairs(t, tb, S.sk_in, S.sk_out, S.idx_in, S.idx_out, (size_t)n, 0u,
                                                    (unsigned)(ub + nb), s);
         }));
         ev.mark(3);
-        e = with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
-            return rocprim::run_length_encode(t, tb, w.sk_out, (unsigned)n, w.uniq, w.runs, dE_all, s);
+        e = with_temp(w.temp, [&](void* t, size_t& tb) {
+            return rocprim::run_length_encode(t, tb, S.sk_out, (unsigned)n, S.uniq, S.runs, dE_all, s);
         });
         break;
     }
     if (e != hipSuccess || have_offs) return e;
     // offsets over the n-bound: entries past E_all are never read
-    return with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
-        return rocprim::exclusive_scan(t, tb, w.runs, w.offs, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
+    return with_temp(w.temp, [&](void* t, size_t& tb) {
+        return rocprim::exclusive_scan(t, tb, S.runs, S.offs, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
     });
 }
 
@@ -156,8 +158,9 @@ static hipError_t sort_to_runs(Workspace& w, const ReduceJob& J, int nb, int ub,
 static hipError_t reduce_runs(Workspace& w, const ReduceJob& J, int nb, const RunTable& T, hipStream_t s,
                               ctg_result* res) {
     const int64_t n = J.n;
-    uint32_t* dE_all = w.small;
-    uint32_t* dE = w.small + 1;
+    const SortScratch& S = w.sort;
+    uint32_t* dE_all = w.small + SLOT_RUNS;
+    uint32_t* dE = w.small + SLOT_EDGES;
     // outputs (uncompacted), sized by the bound n
     const bool may_drop = J.need_adj || J.ignore_label;
     // CTG_DEFER_STATS: result row e is run e of the records (no compaction),
@@ -177,7 +180,7 @@ static hipError_t reduce_runs(Workspace& w, const ReduceJob& J, int nb, const Ru
     ReduceOut O{};
     O.edges = edges;
     O.feats = feats;
-    O.keep = may_drop ? w.keep : nullptr;
+    O.keep = may_drop ? S.keep : nullptr;
     O.wstats = wstats;
     O.wsums = wsums;
     O.count_out = may_drop ? nullptr : dE;   // no compaction: the kernel copies the count
@@ -191,19 +194,19 @@ static hipError_t reduce_runs(Workspace& w, const ReduceJob& J, int nb, const Ru
     O.ablate = 0;
 #endif
     // features-only narrow reduce: edges past 2^16 samples are listed for the
-    // wide-histogram kernel (w.small[40]: their count)
+    // wide-histogram kernel (w.small[SLOT_HEAVY]: their count)
     DevBuf<uint32_t> heavy;
     const bool list_heavy = !J.wide && J.stats && !O.wstats;
     if (list_heavy && !heavy.alloc(n * 4)) return hipErrorOutOfMemory;
-    const Perm perm = T.perm(w);
-    hipError_t e = launch_reduce(n, dE_all, w.uniq, w.runs, w.offs, perm.p32, perm.p64, perm.ib, J.R, J.wide, J.stats,
+    const Perm perm = T.perm(S);
+    hipError_t e = launch_reduce(n, dE_all, S.uniq, S.runs, S.offs, perm.p32, perm.p64, perm.ib, J.R, J.wide, J.stats,
                                  nb, J.umask, J.need_adj, J.ignore_label, J.scale, J.offset, O, s, heavy,
-                                 list_heavy ? w.small + 40 : nullptr);
+                                 list_heavy ? w.small + SLOT_HEAVY : nullptr);
     heavy.reset();   // stream-ordered reuse
     if (e != hipSuccess) return e;
     if (may_drop) {
-        CTG_TRY(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
-            return rocprim::exclusive_scan(t, tb, w.keep, w.pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
+        CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
+            return rocprim::exclusive_scan(t, tb, S.keep, S.pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
         }));
         DevBuf<uint64_t> c_edges(n * 16);
         DevBuf<double> c_feats;
@@ -220,7 +223,7 @@ static hipError_t reduce_runs(Workspace& w, const ReduceJob& J, int nb, const Ru
         C2.feats = c_feats;
         C2.wstats = c_wstats;
         C2.wsums = c_wsums;
-        CTG_TRY(launch_compact(n, dE_all, w.keep, w.pos, O, C2, dE, s));
+        CTG_TRY(launch_compact(n, dE_all, S.keep, S.pos, O, C2, dE, s));
         // the uncompacted tables go back to the pool (stream-ordered reuse)
         edges.reset(c_edges.release());
         feats.reset(c_feats.release());
@@ -233,8 +236,8 @@ static hipError_t reduce_runs(Workspace& w, const ReduceJob& J, int nb, const Ru
     res->stat_sums = wsums.release();
     if (defer) {
         res->defer.on = 1;
-        res->defer.offs = w.offs;
-        res->defer.runs = w.runs;
+        res->defer.offs = S.offs;
+        res->defer.runs = S.runs;
         res->defer.perm = perm;
         res->defer.hist = J.R.hist;
         res->defer.gen = w.gen;
@@ -250,8 +253,10 @@ static hipError_t reduce_runs(Workspace& w, const ReduceJob& J, int nb, const Ru
 static hipError_t collect_nodes(Workspace& w, const ReduceJob& J, int nb, hipStream_t s, ctg_result* res,
                                 uint32_t* counts) {
     const int64_t n = J.n;
-    uint32_t* dE_all = w.small;
-    uint32_t* dN = w.small + 2;
+    const SortScratch& S = w.sort;
+    uint32_t* dE_all = w.small + SLOT_RUNS;
+    uint32_t* dN = w.small + SLOT_NODES;
+    static_assert(SLOT_RUNS == 0 && SLOT_EDGES == 1 && SLOT_NODES == 2, "counts[] is read back as one range");
     // the first k of the device counts, after everything queued so far
     auto read_counts = [&](int k) {
         hipError_t e_ = hipMemcpyAsync(w.small_host, w.small, k * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
@@ -274,13 +279,13 @@ static hipError_t collect_nodes(Workspace& w, const ReduceJob& J, int nb, hipStr
         res->nodes = (uint64_t*)dev_alloc(node_cap * 8);
         if (!bits || !off || !res->nodes) return hipErrorOutOfMemory;
         CTG_TRY(hipMemsetAsync(bits, 0, W * 4, s));
-        CTG_TRY(launch_mark_nodes(n, dE_all, w.uniq, nb, bits, W, wbase, s));
+        CTG_TRY(launch_mark_nodes(n, dE_all, S.uniq, nb, bits, W, wbase, s));
         // word offsets = exclusive scan of the words' popcounts (read through the scan's input iterator)
         // (tried: the scan and the expansion in one workgroup for small label ranges -- 0.053 -> 0.115 ms
         // at 512^3, the serial per-thread expansion loses to the wide launch)
         auto popc = rocprim::make_transform_iterator((uint32_t*)bits,
                                                      [] __device__(uint32_t b) { return (uint32_t)__popc(b); });
-        CTG_TRY(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+        CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
             return rocprim::exclusive_scan(t, tb, popc, (uint32_t*)off, 0u, (size_t)W, rocprim::plus<uint32_t>(), s);
         }));
         CTG_TRY(launch_bits_to_nodes(W, bits, off, res->nodes, dN, node_cap, wbase, s));
@@ -294,17 +299,17 @@ static hipError_t collect_nodes(Workspace& w, const ReduceJob& J, int nb, hipStr
     DevBuf<uint32_t> ep(std::max<int64_t>(E_all, 1) * 8), ep2(std::max<int64_t>(E_all, 1) * 8),
         nodes32(std::max<int64_t>(E_all, 1) * 8);
     if (!ep || !ep2 || !nodes32) return hipErrorOutOfMemory;
-    CTG_TRY(launch_endpoints(E_all, w.uniq, nb, ep, s));
-    CTG_TRY(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+    CTG_TRY(launch_endpoints(E_all, S.uniq, nb, ep, s));
+    CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
         return rocprim::radix_sort_keys(t, tb, (uint32_t*)ep, (uint32_t*)ep2, (size_t)(2 * E_all), 0u, (unsigned)nb, s);
     }));
-    CTG_TRY(with_temp(w.temp, w.temp_bytes, [&](void* t, size_t& tb) {
+    CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
         return rocprim::unique(t, tb, (uint32_t*)ep2, (uint32_t*)nodes32, dN, (size_t)(2 * E_all),
                                rocprim::equal_to<uint32_t>(), s);
     }));
-    CTG_TRY(hipMemcpyAsync(w.small_host + 2, dN, 4, hipMemcpyDeviceToHost, s));
+    CTG_TRY(hipMemcpyAsync(w.small_host + SLOT_NODES, dN, 4, hipMemcpyDeviceToHost, s));
     CTG_TRY(hipStreamSynchronize(s));
-    counts[2] = w.small_host[2];
+    counts[2] = w.small_host[SLOT_NODES];
     res->nodes = (uint64_t*)dev_alloc(std::max<int64_t>(counts[2], 1) * 8);
     if (!res->nodes) return hipErrorOutOfMemory;
     CTG_TRY(launch_u32_to_u64(counts[2], nodes32, res->nodes, s));
@@ -317,7 +322,7 @@ static hipError_t collect_nodes(Workspace& w, const ReduceJob& J, int nb, hipStr
 
 hipError_t reduce_records(Workspace& w, const ReduceJob& J, hipStream_t s, ctg_result* res) {
     // Device-resident counts: the run count E_all, the kept edge count E and
-    // the node count N stay in w.small[0..2] until one read-back at the end;
+    // the node count N stay in w.small (SLOT_RUNS .. SLOT_NODES) until one read-back at the end;
     // every kernel in between bounds itself by them, and buffers are sized by
     // the record count n (an upper bound), so the back half issues no
     // host synchronisation (except on the rare node path for labels >= 2^30).
@@ -344,20 +349,7 @@ hipError_t reduce_records(Workspace& w, const ReduceJob& J, hipStream_t s, ctg_r
         for (int i = 2; i <= 6; ++i) ev.mark(i);
         return hipStreamSynchronize(s);
     }
-    // sort buffers
-    if (n > w.sort_cap) {
-        dev_free(w.sk_in); dev_free(w.sk_out); dev_free(w.idx_in); dev_free(w.idx_out);
-        dev_free(w.uniq); dev_free(w.runs); dev_free(w.offs); dev_free(w.keep); dev_free(w.pos);
-        const int64_t cap = std::max<int64_t>(n, w.sort_cap + w.sort_cap / 2);
-        w.sk_in = (uint64_t*)dev_alloc(cap * 8); w.sk_out = (uint64_t*)dev_alloc(cap * 8);
-        w.idx_in = (uint32_t*)dev_alloc(cap * 4); w.idx_out = (uint32_t*)dev_alloc(cap * 4);
-        w.uniq = (uint64_t*)dev_alloc(cap * 8); w.runs = (uint32_t*)dev_alloc(cap * 4);
-        w.offs = (uint32_t*)dev_alloc(cap * 4); w.keep = (uint32_t*)dev_alloc(cap * 4);
-        w.pos = (uint32_t*)dev_alloc(cap * 4);
-        if (!w.sk_in || !w.sk_out || !w.idx_in || !w.idx_out || !w.uniq || !w.runs || !w.offs || !w.keep || !w.pos)
-            return hipErrorOutOfMemory;
-        w.sort_cap = cap;
-    }
+    if (!w.sort.reserve(n)) return hipErrorOutOfMemory;
     RunTable T{};
     CTG_TRY(sort_to_runs(w, J, nb, ub, ev, s, T));
     ev.mark(4);

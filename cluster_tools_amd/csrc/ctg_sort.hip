@@ -146,8 +146,8 @@ static int bucket_bits(int64_t n, int key_bits) {
 
 // (keys, vals) sorted by key bits [0, hi_bit) into (kout, vout); ktmp / vtmp: n each
 hipError_t bucket_sort_pairs(const uint64_t* keys, const uint32_t* vals, uint64_t* ktmp, uint32_t* vtmp,
-                             uint64_t* kout, uint32_t* vout, int64_t n, int hi_bit, uint32_t* small, void** temp,
-                             size_t* temp_bytes, uint32_t* nbk_out, hipStream_t s) {
+                             uint64_t* kout, uint32_t* vout, int64_t n, int hi_bit, uint32_t* small, GrowBuf& temp,
+                             uint32_t* nbk_out, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > 0xFFFFFFFFll || hi_bit > 64 || hi_bit <= 0) return hipErrorInvalidValue;
     const int bb = bucket_bits(n, hi_bit);
@@ -169,7 +169,7 @@ hipError_t bucket_sort_pairs(const uint64_t* keys, const uint32_t* vals, uint64_
         e = hipMemcpyAsync(kout, ktmp, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
         return e != hipSuccess ? e : hipMemcpyAsync(vout, vtmp, (size_t)n * 4, hipMemcpyDeviceToDevice, s);
     }
-    return with_temp(*temp, *temp_bytes, [&](void* t, size_t& tb) {
+    return with_temp(temp, [&](void* t, size_t& tb) {
         return rocprim::segmented_radix_sort_pairs(t, tb, ktmp, kout, vtmp, vout, (unsigned)n, nbk, offs, offs + 1, 0u,
                                                    (unsigned)shift, s);
     });
@@ -261,10 +261,10 @@ hipError_t bucket_runs(const uint64_t* sorted, int64_t n, int lo_bit, uint32_t n
 
 // keys (n, packed: key bits [lo_bit, hi_bit), slot bits below) -> sorted by
 // the key bits into out (order among equal keys: any).  tmp: n u64;
-// small: 3 * 4096 + 1 u32; temp / temp_bytes: the caller's growable scratch.
+// small: 3 * 4096 + 1 u32; temp: the caller's growable scratch.
 hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, int64_t n, int lo_bit, int hi_bit,
-                            uint64_t kmin, uint64_t kmax, uint32_t* small, void** temp, size_t* temp_bytes,
-                            uint32_t* nbk_out, hipStream_t s) {
+                            uint64_t kmin, uint64_t kmax, uint32_t* small, GrowBuf& temp, uint32_t* nbk_out,
+                            hipStream_t s) {
     if (n <= 0) return hipSuccess;
     if (n > 0xFFFFFFFFll || hi_bit > 64 || lo_bit < 0 || hi_bit <= lo_bit || kmin > kmax) return hipErrorInvalidValue;
     const int bb = bucket_bits(n, hi_bit - lo_bit);
@@ -293,7 +293,7 @@ hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, 
     if (shift <= lo_bit) {   // the buckets are the keys: already grouped and ordered
         return hipMemcpyAsync(out, tmp, (size_t)n * 8, hipMemcpyDeviceToDevice, s);
     }
-    return with_temp(*temp, *temp_bytes, [&](void* t, size_t& tb) {
+    return with_temp(temp, [&](void* t, size_t& tb) {
         return rocprim::segmented_radix_sort_keys(t, tb, tmp, out, (unsigned)n, nbk, offs, offs + 1, (unsigned)lo_bit,
                                                   (unsigned)shift, s);
     });

@@ -5,20 +5,19 @@
 #include <cstring>
 #include <sys/mman.h>
 
-#include <algorithm>
 #include <map>
 #include <mutex>
 
 #include "ctg_internal.h"
+#include "ctg_pool.h"
 
 namespace ctg {
 
 // ---------------------------------------------------------------------------
-// caching device allocator: results and scratch are recycled between calls so
-// steady-state calls do no hipMalloc/hipFree
+// the caching device allocator (ctg_pool.h) over hipMalloc / hipFree
 // ---------------------------------------------------------------------------
-static std::mutex g_mu;
-static std::multimap<size_t, void*> g_pool[64];
+static DevicePool g_pool([](void** p, size_t bytes) -> int { return hipMalloc(p, bytes); },
+                         [](void* p) -> int { return hipFree(p); });
 
 int current_device() {
     int d = 0;
@@ -26,63 +25,8 @@ int current_device() {
     return d;
 }
 
-static size_t round_up(size_t b) {
-    size_t r = 256;
-    while (r < b) r = r < (1u << 20) ? r * 2 : r + (r >> 2);
-    return r;
-}
-
-static void* dmalloc(size_t bytes) {
-    if (bytes == 0) bytes = 256;
-    bytes = round_up(bytes);
-    const int d = current_device();
-    {
-        std::lock_guard<std::mutex> g(g_mu);
-        auto& pool = g_pool[d & 63];
-        auto it = pool.lower_bound(bytes);
-        if (it != pool.end() && it->first <= bytes * 2) {
-            void* p = it->second;
-            pool.erase(it);
-            return p;
-        }
-    }
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes + 64) != hipSuccess) {
-        // release cached blocks and retry once
-        std::lock_guard<std::mutex> g(g_mu);
-        for (auto& kv : g_pool[d & 63]) hipFree(kv.second);
-        g_pool[d & 63].clear();
-        if (hipMalloc(&p, bytes + 64) != hipSuccess) return nullptr;
-    }
-    return p;
-}
-
-static std::map<void*, size_t> g_sizes;
-void* dev_alloc(size_t bytes) {
-    bytes = round_up(bytes == 0 ? 256 : bytes);
-    void* p = dmalloc(bytes);
-    if (p) {
-        std::lock_guard<std::mutex> g(g_mu);
-        g_sizes[p] = bytes;
-    }
-    return p;
-}
-void dev_free(void* p) {
-    if (!p) return;
-    const int d = current_device();
-    std::lock_guard<std::mutex> g(g_mu);
-    auto it = g_sizes.find(p);
-    size_t b = it == g_sizes.end() ? 256 : it->second;
-    g_pool[d & 63].emplace(b, p);
-}
-
-void ensure(void** p, size_t& have, size_t need) {
-    if (need <= have && *p) return;
-    if (*p) dev_free(*p);
-    size_t n = std::max(need, have + have / 2);
-    *p = dev_alloc(n);
-    have = *p ? n : 0;
-}
+void* dev_alloc(size_t bytes) { return g_pool.alloc(current_device(), bytes); }
+void dev_free(void* p) { g_pool.free(p); }
 
 static Workspace g_ws[64];
 Workspace& ws(int device) { return g_ws[device & 63]; }
@@ -90,21 +34,41 @@ Workspace& ws(int device) { return g_ws[device & 63]; }
 static std::recursive_mutex g_dev_mu[64];
 std::recursive_mutex& device_mutex(int device) { return g_dev_mu[device & 63]; }
 
-hipError_t ws_init(Workspace& w) {
-    if (w.counters) return hipSuccess;
+static hipError_t ws_create(Workspace& w) {
     CTG_TRY(hipMalloc(&w.counters, sizeof(Counters)));
     CTG_TRY(hipHostMalloc(&w.counters_host, sizeof(Counters), hipHostMallocDefault));
-    CTG_TRY(hipMalloc(&w.small, 64 * sizeof(unsigned int)));
+    CTG_TRY(hipMalloc(&w.small, SMALL_WORDS * sizeof(unsigned int)));
     CTG_TRY(hipMalloc(&w.bsort, BK_SMALL_WORDS * sizeof(uint32_t)));   // bucket sort scratch
     CTG_TRY(hipMalloc(&w.gsort, GS_SMALL_WORDS * sizeof(uint32_t)));   // group sort scratch
     // the splitters stay in workspace memory: k_mgpu_bounds still reads them
     // after ctg_mgpu_split returns (a pool block freed there could be handed
     // to a call on another stream while that kernel runs)
     CTG_TRY(hipMalloc(&w.mgpu_spl, CTG_MGPU_MAX_WORLD * sizeof(uint64_t)));
-    CTG_TRY(hipHostMalloc(&w.small_host, 64 * sizeof(unsigned int), hipHostMallocDefault));
-    for (int i = 0; i < 10; ++i) hipEventCreate(&w.ev[i]);
-    w.events = true;
+    CTG_TRY(hipHostMalloc(&w.small_host, SMALL_WORDS * sizeof(unsigned int), hipHostMallocDefault));
+    for (hipEvent_t& ev : w.ev) CTG_TRY(hipEventCreate(&ev));
     return hipSuccess;
+}
+
+// All or nothing: ready only once every member exists; a failed attempt
+// releases what it made, so the next call starts over.
+hipError_t ws_init(Workspace& w) {
+    if (w.ready) return hipSuccess;
+    const hipError_t e = ws_create(w);
+    w.ready = e == hipSuccess;
+    if (w.ready) return e;
+    auto drop = [](auto*& p, auto release) {
+        if (p) release(p);
+        p = nullptr;
+    };
+    drop(w.counters, hipFree);
+    drop(w.counters_host, hipHostFree);
+    drop(w.small, hipFree);
+    drop(w.bsort, hipFree);
+    drop(w.gsort, hipFree);
+    drop(w.mgpu_spl, hipFree);
+    drop(w.small_host, hipHostFree);
+    for (hipEvent_t& ev : w.ev) drop(ev, hipEventDestroy);
+    return e;
 }
 
 void free_records(Workspace& w) {
@@ -115,6 +79,7 @@ void free_records(Workspace& w) {
     w.rec = RecordBuf{};
 }
 
+// all or nothing, like the sort scratch: cap > 0 exactly when the buffers exist
 hipError_t ensure_records(Workspace& w, int64_t need, int wide) {
     ++w.gen;   // a scan is about to overwrite the records
     if (need <= w.rec.cap && w.rec.key) return hipSuccess;
@@ -123,7 +88,10 @@ hipError_t ensure_records(Workspace& w, int64_t need, int wide) {
     w.rec.key = (uint64_t*)dev_alloc((size_t)need * 8);
     w.rec.sums = wide ? (double2*)dev_alloc((size_t)need * 16) : nullptr;
     w.rec.hist = (uint32_t*)dev_alloc((size_t)need * words * 4);
-    if (!w.rec.key || (wide && !w.rec.sums) || !w.rec.hist) return hipErrorOutOfMemory;
+    if (!w.rec.key || (wide && !w.rec.sums) || !w.rec.hist) {
+        free_records(w);
+        return hipErrorOutOfMemory;
+    }
     w.rec.cap = need;
     w.rec.rcap = need / NREG;
     return hipSuccess;
@@ -143,25 +111,10 @@ int ctg_trim(void) {
     Workspace& w = ws(d);
     CTG_CHECK(hipDeviceSynchronize());
     free_records(w);   // bumps w.gen: deferred handles made before the trim are refused (CTG_ERR_STALE)
-    dev_free(w.sk_in); dev_free(w.sk_out); dev_free(w.idx_in); dev_free(w.idx_out);
-    dev_free(w.uniq); dev_free(w.runs); dev_free(w.offs); dev_free(w.keep); dev_free(w.pos);
-    w.sk_in = w.sk_out = w.uniq = nullptr;
-    w.idx_in = w.idx_out = w.runs = w.offs = w.keep = w.pos = nullptr;
-    w.sort_cap = 0;
-    dev_free(w.temp);
-    w.temp = nullptr;
-    w.temp_bytes = 0;
-    for (int i = 0; i < 2; ++i) {
-        dev_free(w.stage[i]);
-        w.stage[i] = nullptr;
-        w.stage_bytes[i] = 0;
-    }
-    std::lock_guard<std::mutex> g(g_mu);
-    for (auto& kv : g_pool[d & 63]) {
-        g_sizes.erase(kv.second);
-        CTG_CHECK(hipFree(kv.second));
-    }
-    g_pool[d & 63].clear();
+    w.sort.free();
+    w.temp.free();
+    for (GrowBuf& st : w.stage) st.free();
+    CTG_CHECK((hipError_t)g_pool.purge(d));   // hipFree of every cached block; the first failure is reported
     return CTG_OK;
 }
 

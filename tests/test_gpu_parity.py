@@ -205,6 +205,27 @@ def test_boundary_whole_volume(gpu, shape, cell):
     check_features(out['features'], f_ref)
 
 
+def test_workspace_trimmed_then_regrown(gpu):
+    """The workspace buffers (records, sort scratch, staging, rocPRIM temp)
+    released by trim_cache, reserved afresh by a smaller call and grown again
+    by the first one: every result equals the oracle's."""
+    big = S.generate((24, 40, 72), cell=6, seed=7)
+    small = S.generate((8, 20, 40), cell=6, seed=7)
+    ref = {id(v): (O.boundary_features(*v), O.unique_labels(v[0])) for v in (big, small)}
+
+    def call(v):
+        (e_ref, f_ref), n_ref = ref[id(v)]
+        out = rag.rag_features(v[0], v[1], keep_stats=True)
+        np.testing.assert_array_equal(out['edges'], e_ref)
+        np.testing.assert_array_equal(out['nodes'], n_ref)
+        check_features(out['features'], f_ref)
+
+    call(big)
+    rag.trim_cache()
+    call(small)
+    call(big)
+
+
 def test_graph_only(gpu):
     lab, _ = S.generate((33, 70, 90), cell=7, seed=1, with_boundary=False)
     out = rag.rag_features(lab)
