@@ -78,6 +78,11 @@ PROTOTYPES = {
                                               ctypes.c_int, c_vp]),
     'ctg_unique_pairs': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
     'ctg_unique_values': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_label_overlaps': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int,
+                                          ctypes.c_uint64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_merge_overlaps': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_max_overlaps': (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_int, c_vp]),
+    'ctg_result_copy_counts': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

@@ -552,15 +552,15 @@ int ctg_diag_bounds(uint64_t* out) {
 #ifdef CTG_DIAG
     if (!out) return CTG_ERR_ARG;
     CTG_CHECK(hipDeviceSynchronize());
-    hipError_t (*take[5])(unsigned long long*) = {bounds_take_api, bounds_take_scan, bounds_take_sort,
-                                                   bounds_take_reduce, bounds_take_mgpu};
+    hipError_t (*take[6])(unsigned long long*) = {bounds_take_api,    bounds_take_scan, bounds_take_sort,
+                                                   bounds_take_reduce, bounds_take_mgpu, bounds_take_overlap};
     out[0] = out[1] = out[2] = out[3] = 0;
     int found = 0;
-    for (int f = 0; f < 5; ++f) {
+    for (int f = 0; f < 6; ++f) {
         unsigned long long h[3] = {0, 0, 0};
         CTG_CHECK(take[f](h));
         if (h[0] && !found) {
-            out[0] = (uint64_t)f + 1;   // 1 api, 2 scan, 3 sort, 4 reduce, 5 mgpu
+            out[0] = (uint64_t)f + 1;   // 1 api, 2 scan, 3 sort, 4 reduce, 5 mgpu, 6 overlap
             out[1] = h[0];
             out[2] = h[1];
             out[3] = h[2];
@@ -1231,6 +1231,214 @@ int ctg_unique_pairs(const uint64_t* pairs, int64_t n, int mem, void* stream, ct
     return reduce_pairs(w, J, dk, s, "ctg_unique_pairs", out);
 }
 
+// ---------------------------------------------------------------------------
+// label overlaps (kernels and back half: ctg_overlap.hip)
+// ---------------------------------------------------------------------------
+static int overlap_status(hipError_t e, const char* who) {
+    if (e == hipSuccess) return CTG_OK;
+    set_error(std::string(who) + ": " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? CTG_ERR_NOMEM : CTG_ERR_HIP;
+}
+
+// an overlaps result without rows: the placeholders of empty_result plus the counts'
+static ResultPtr empty_overlaps(int device) {
+    ResultPtr r = empty_result(device);
+    r->counts = (uint64_t*)dev_alloc(8);
+    return r;
+}
+
+// One side of ctg_label_overlaps whose labels reach 2^32: the box's sorted
+// unique labels U and the whole array as 32-bit ranks in U (monotone; voxels
+// outside the box get some rank and are never read).
+struct DenseSide {
+    ResultPtr U;
+    DevBuf<uint32_t> ids;
+    int build(const void* vol, const int64_t* shape, const int64_t* b, const int64_t* e, void* stream) {
+        int rc = nested(U, [&](ctg_result** u) {
+            return ctg_unique_labels((const uint64_t*)vol, shape, b, e, CTG_MEM_DEVICE, stream, u);
+        });
+        if (rc) return rc;
+        if (U->n_nodes > 0xFFFFFFFFll) {
+            set_error("ctg_label_overlaps: more than 2^32 distinct labels in one box");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        const int64_t V = shape[0] * shape[1] * shape[2];
+        if (!ids.alloc((size_t)V * 4)) {
+            set_error("ctg_label_overlaps: out of device memory for the dense relabelling");
+            return CTG_ERR_NOMEM;
+        }
+        CTG_CHECK(launch_remap_dense((const uint64_t*)vol, V, U->nodes, U->n_nodes, ids, (hipStream_t)stream));
+        return CTG_OK;
+    }
+};
+
+int ctg_label_overlaps(const void* labels, int label_bits, const void* values, int value_bits, const int64_t* shape,
+                       const int64_t* begin, const int64_t* end, int with_ignore, uint64_t ignore_label, int mem,
+                       void* stream, ctg_result** out) {
+    DevLock dev_lock;
+    if (!labels || !values || !shape || !out) {
+        set_error("ctg_label_overlaps: null argument");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if ((label_bits != 32 && label_bits != 64) || (value_bits != 32 && value_bits != 64)) {
+        set_error("ctg_label_overlaps: label_bits and value_bits must be 32 or 64");
+        return CTG_ERR_ARG;
+    }
+    int64_t b[3], e[3];
+    for (int k = 0; k < 3; ++k) {
+        b[k] = begin ? begin[k] : 0;
+        e[k] = end ? end[k] : shape[k];
+        if (shape[k] < 0 || b[k] < 0 || e[k] > shape[k] || b[k] > e[k]) {
+            set_error("ctg_label_overlaps: box outside the array");
+            return CTG_ERR_ARG;
+        }
+    }
+    const int64_t nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
+    if (nb >= 0xFFFFFFFFll) {   // (a record per voxel at most; the run table numbers records in 32 bits)
+        set_error("ctg_label_overlaps: boxes of 2^32 voxels or more are not supported");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    const int dev = current_device();
+    Workspace& w = ws(dev);
+    CTG_CHECK(ws_init(w));
+    hipStream_t s = (hipStream_t)stream;
+    ResultPtr r = empty_overlaps(dev);
+    if (nb == 0) {
+        *out = r.release();
+        return CTG_OK;
+    }
+    const int64_t V = shape[0] * shape[1] * shape[2];
+    const void *dl = nullptr, *dv = nullptr;
+    int rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
+    if (!rc) rc = stage_in(w.stage[1], values, (size_t)V * (value_bits / 8), mem, s, &dv);
+    if (rc) return rc;
+    unsigned over = 0;
+    if ((rc = overlap_status(overlap_tables(w, dl, label_bits, dv, value_bits, shape, b, e, with_ignore, ignore_label,
+                                            s, r.get(), &over),
+                             "ctg_label_overlaps")) != CTG_OK)
+        return rc;
+    if (over) {
+        // labels >= 2^32 do not fit the 32 + 32 bit keys: the side(s) that hold
+        // them run again as dense ids, and the sorted tables map back
+        DenseSide da, db;
+        if ((over & 1u) && (rc = da.build(dl, shape, b, e, stream)) != CTG_OK) return rc;
+        if ((over & 2u) && (rc = db.build(dv, shape, b, e, stream)) != CTG_OK) return rc;
+        if ((over & 2u) && with_ignore) {   // the ignore label's dense id (absent from the box: nothing to skip)
+            DevBuf<uint32_t> rank(4);
+            uint32_t h = 0;
+            if (!rank) return overlap_status(hipErrorOutOfMemory, "ctg_label_overlaps");
+            CTG_CHECK(launch_overlap_find(db.U->nodes, db.U->n_nodes, ignore_label, rank, s));
+            CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
+            CTG_CHECK(hipStreamSynchronize(s));
+            with_ignore = h != 0xFFFFFFFFu;
+            ignore_label = h;
+        }
+        unsigned again = 0;
+        if ((rc = overlap_status(overlap_tables(w, da.U ? (const void*)da.ids.p : dl, da.U ? 32 : label_bits,
+                                                db.U ? (const void*)db.ids.p : dv, db.U ? 32 : value_bits, shape, b,
+                                                e, with_ignore, ignore_label, s, r.get(), &again),
+                                 "ctg_label_overlaps")) != CTG_OK)
+            return rc;
+        if (again) {
+            set_error("ctg_label_overlaps: dense ids past 2^32");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        CTG_CHECK(launch_overlap_map_back(r->n_edges, r->edges, da.U ? da.U->nodes : nullptr,
+                                          da.U ? da.U->n_nodes : 0, db.U ? db.U->nodes : nullptr,
+                                          db.U ? db.U->n_nodes : 0, s));
+        if (da.U) CTG_CHECK(launch_gather_labels(da.U->nodes, r->nodes, r->n_nodes, s));
+    }
+    if (w.profiling && r->n_records > 0) {
+        if ((rc = read_phase_times(w, s)) != CTG_OK) return rc;
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    w.last_records = r->n_records;
+    w.last_direct = r->n_direct;
+    *out = r.release();
+    return CTG_OK;
+}
+
+int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n, int mem, void* stream,
+                       ctg_result** out) {
+    DevLock dev_lock;
+    if (!out || n < 0 || (n > 0 && (!pairs || !counts))) {
+        set_error("ctg_merge_overlaps: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (n >= 0xFFFFFFFFll) {
+        set_error("ctg_merge_overlaps: 2^32 rows or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    const int dev = current_device();
+    Workspace& w = ws(dev);
+    CTG_CHECK(ws_init(w));
+    hipStream_t s = (hipStream_t)stream;
+    ResultPtr r = empty_overlaps(dev);
+    if (n == 0) {
+        *out = r.release();
+        return CTG_OK;
+    }
+    DevInput<uint64_t> dp, dc;
+    int rc = dp.put(pairs, (size_t)n * 16, mem, s, "ctg_merge_overlaps");
+    if (!rc) rc = dc.put(counts, (size_t)n * 8, mem, s, "ctg_merge_overlaps");
+    if (rc) return rc;
+    CTG_CHECK(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
+    CTG_CHECK(launch_max_pairs(n, dp, &w.counters->max_v, s));
+    CTG_CHECK(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    DensePairs dense;
+    const uint64_t* src = dp;
+    if (w.counters_host->max_v >> 32) {
+        if ((rc = dense.build(dp, n, s)) != CTG_OK) return rc;
+        if (dense.U->n_nodes > 0xFFFFFFFFll) {
+            set_error("ctg_merge_overlaps: more than 2^32 distinct labels");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        src = dense.dense;
+    }
+    DevBuf<uint64_t> key((size_t)n * 8);
+    if (!key) return overlap_status(hipErrorOutOfMemory, "ctg_merge_overlaps");
+    CTG_CHECK(launch_overlap_pack(n, src, key, s));
+    if ((rc = overlap_status(overlap_reduce(w, key, dc, n, s, r.get()), "ctg_merge_overlaps")) != CTG_OK) return rc;
+    CTG_CHECK(dense.map_back(r.get(), s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    r->n_records = n;
+    *out = r.release();
+    return CTG_OK;
+}
+
+int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_end, uint64_t* out_labels,
+                     uint64_t* out_counts, int mem, void* stream) {
+    DevLock dev_lock;
+    if (!r || label_end < label_begin || (label_end > label_begin && !out_labels)) {
+        set_error("ctg_max_overlaps: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (!r->counts || (r->n_nodes > 0 && !r->row_off)) {
+        set_error("ctg_max_overlaps: not an overlaps result (ctg_label_overlaps, ctg_merge_overlaps)");
+        return CTG_ERR_ARG;
+    }
+    const uint64_t n = label_end - label_begin;
+    if (n == 0) return CTG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool host = mem == CTG_MEM_HOST;
+    DevBuf<uint64_t> own_l, own_c;
+    uint64_t *dl = out_labels, *dc = out_counts;
+    if (host && (!(dl = own_l.alloc(n * 8)) || (out_counts && !(dc = own_c.alloc(n * 8)))))
+        return overlap_status(hipErrorOutOfMemory, "ctg_max_overlaps");
+    CTG_CHECK(hipMemsetAsync(dl, 0, n * 8, s));
+    if (dc) CTG_CHECK(hipMemsetAsync(dc, 0, n * 8, s));
+    CTG_CHECK(launch_overlap_argmax(r, label_begin, label_end, dl, dc, s));
+    if (host) {
+        CTG_CHECK(hipMemcpyAsync(out_labels, dl, n * 8, hipMemcpyDeviceToHost, s));
+        if (dc) CTG_CHECK(hipMemcpyAsync(out_counts, dc, n * 8, hipMemcpyDeviceToHost, s));
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
+
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global, const uint64_t* query, int64_t n_query,
                      int64_t* out_ids, int mem, void* stream) {
     DevLock dev_lock;
@@ -1294,6 +1502,13 @@ int ctg_result_copy_stats(const ctg_result* r, double* sums_dst, uint32_t* recor
     if (rc) return rc;
     return copy_out(records_dst, r->stats, (size_t)r->n_edges * WREC_WORDS * 4, mem);
 }
+int ctg_result_copy_counts(const ctg_result* r, uint64_t* dst, int mem) {
+    if (!r->counts) {
+        set_error("result has no counts (not an overlaps result)");
+        return CTG_ERR_ARG;
+    }
+    return copy_out(dst, r->counts, (size_t)r->n_edges * 8, mem);
+}
 const uint64_t* ctg_result_device_edges(const ctg_result* r) { return r ? r->edges : nullptr; }
 const double* ctg_result_device_features(const ctg_result* r) { return r ? r->features : nullptr; }
 int ctg_result_info(const ctg_result* r, int64_t* n_records, int64_t* n_direct) {
@@ -1316,6 +1531,8 @@ void ctg_free(ctg_result* r) {
     }
     dev_free(r->stats);
     dev_free(r->stat_sums);
+    dev_free(r->counts);
+    dev_free(r->row_off);
     if (r->device >= 0 && r->device != d) hipSetDevice(d);
     delete r;
 }

@@ -451,6 +451,7 @@ hipError_t bounds_take_reduce(unsigned long long* h);
 hipError_t bounds_take_sort(unsigned long long* h);
 hipError_t bounds_take_mgpu(unsigned long long* h);
 hipError_t bounds_take_scan(unsigned long long* h);
+hipError_t bounds_take_overlap(unsigned long long* h);
 #endif
 
 }  // namespace ctg
@@ -469,6 +470,10 @@ struct ctg_result {
     double* features = nullptr;     // device (E,10) or null
     uint32_t* stats = nullptr;      // device wide records (E, WREC_WORDS) or null
     double2* stat_sums = nullptr;   // device (E,) (sum, sumsq) or null
+    // label-overlap tables (ctg_label_overlaps, ctg_merge_overlaps): edges holds
+    // the sorted (a, b) pairs, nodes the distinct a
+    uint64_t* counts = nullptr;     // device (E,) voxels of each pair, or null
+    int64_t* row_off = nullptr;     // device (N+1,) rows [row_off[j], row_off[j+1]) belong to nodes[j], or null
     int64_t n_records = 0;
     int64_t n_direct = 0;
     // affinity partial table (CTG_NO_ADJ_FILTER): a key is an edge only where
@@ -513,6 +518,27 @@ struct ReduceJob {
     int defer_stats = 0;               // CTG_DEFER_STATS (with keep_stats)
 };
 hipError_t reduce_records(Workspace& w, const ReduceJob& J, hipStream_t s, ctg_result* res);
+
+// ---------------------------------------------------------------------------
+// label overlaps (ctg_overlap.hip).  Call-sized pool buffers only: the
+// workspace's records, sort scratch and generation stay as they are.
+// ---------------------------------------------------------------------------
+// The table of the box [b, e) of two volumes (abits / bbits: 32 or 64) into r
+// (edges, counts, nodes, row_off; nothing where every voxel is ignored).
+// *overflow: bit 0 a label, bit 1 a value >= 2^32 was met -- r is untouched and
+// the caller relabels that side densely.
+hipError_t overlap_tables(Workspace& w, const void* A, int abits, const void* B, int bbits, const int64_t* shape,
+                          const int64_t* b, const int64_t* e, int with_ignore, uint64_t ignore, hipStream_t s,
+                          ctg_result* r, unsigned* overflow);
+// n > 0 (key = a << 32 | b, count) records -> r: equal keys add their counts
+hipError_t overlap_reduce(Workspace& w, const uint64_t* key, const uint64_t* cnt, int64_t n, hipStream_t s,
+                          ctg_result* r);
+hipError_t launch_overlap_pack(int64_t n, const uint64_t* pairs, uint64_t* key, hipStream_t s);
+hipError_t launch_overlap_map_back(int64_t E, uint64_t* pairs, const uint64_t* Ua, int64_t na, const uint64_t* Ub,
+                                   int64_t nb, hipStream_t s);
+hipError_t launch_overlap_find(const uint64_t* U, int64_t n, uint64_t x, uint32_t* out, hipStream_t s);
+hipError_t launch_overlap_argmax(const ctg_result* r, uint64_t lb, uint64_t le, uint64_t* out_l, uint64_t* out_c,
+                                 hipStream_t s);
 
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,

@@ -18,6 +18,11 @@ whole integration:
     serializeMergedGraph           multicut/reduce_problem.py:247-258
     Graph                          test/graph/test_graph.py:32,68,111;
                                    multicut/solve_subproblems.py:250
+    computeAndSerializeLabelOverlaps
+                                   node_labels/block_node_labels.py:161
+    mergeAndSerializeOverlaps      node_labels/merge_node_labels.py:149-155
+    deserializeOverlapChunk        test/node_labels/test_node_labels.py:124,144;
+                                   evaluation/measures.py:122
 
 Errors surface as RuntimeError (``_lib.CtgError``), as pybind11 raises for
 nifty's C++ exceptions, so a failing job never prints ``processed job N`` and
@@ -43,6 +48,9 @@ N_FEATURES = 10
 # float32 bits, 2 zero words) = 208 B (include/ctg.h, ctg_merge_stats)
 STATS_SUFFIX = '_stats'
 STATS_WORDS = 4 + rag.WIDE_WORDS
+# the other on-disk layout of this library's own: the overlap chunks of the node
+# labels (varlen uint64: node, n, then n x (label, count) per node, both
+# ascending) -- encode_overlap_chunk / decode_overlap_chunk below
 ORD_POS_INF = 0xFF800000   # order-preserving u32 code of +inf (ctg_internal.h f2ord)
 ORD_NEG_INF = 0x007FFFFF   # ... of -inf
 
@@ -859,3 +867,140 @@ def mergeFeatureBlocks(graphPath, subgraphKey, featuresPath, featuresKey, outPat
     with _open(outPath) as fo:
         fo[outKey][begin:end, :] = out
     _prof('merge_write', t)
+
+
+# ---------------------------------------------------------------------------
+# node labels (label overlaps)
+# ---------------------------------------------------------------------------
+
+# An overlap chunk (varlen uint64, written by computeAndSerializeLabelOverlaps
+# per block and by mergeAndSerializeOverlaps with max_overlap=False, read by
+# deserializeOverlapChunk): for every node in ascending order
+#     node, n, b_1, c_1, ..., b_n, c_n
+# -- the n labels b the node overlaps, ascending, each with its voxel count c.
+# nifty's own byte layout is not in the reference; all three functions that
+# touch these chunks are mirrored here, so the layout is this library's
+# (DESIGN.md 4).
+
+
+def encode_overlap_chunk(pairs, counts):
+    """Sorted (E,2) pairs + (E,) counts -> the chunk words above."""
+    pairs = np.asarray(pairs, dtype=np.uint64).reshape(-1, 2)
+    counts = np.asarray(counts, dtype=np.uint64).reshape(-1)
+    n_rows = pairs.shape[0]
+    nodes, start = np.unique(pairs[:, 0], return_index=True)
+    out = np.empty(2 * nodes.shape[0] + 2 * n_rows, dtype=np.uint64)
+    head = 2 * np.arange(nodes.shape[0], dtype=np.int64) + 2 * start
+    out[head] = nodes
+    out[head + 1] = np.diff(np.append(start, n_rows)).astype(np.uint64)
+    row = 2 * np.searchsorted(nodes, pairs[:, 0]) + 2 * np.arange(n_rows, dtype=np.int64) + 2
+    out[row] = pairs[:, 1]
+    out[row + 1] = counts
+    return out
+
+
+def decode_overlap_chunk(words):
+    """Chunk words -> (pairs (E,2), counts (E,)) in the chunk's order."""
+    w = np.asarray(words, dtype=np.uint64).reshape(-1)
+    a, rows, i = [], [], 0
+    while i < w.size:
+        if i + 2 > w.size or i + 2 + 2 * int(w[i + 1]) > w.size:
+            raise RuntimeError('overlap chunk: truncated row of node %d' % int(w[i]))
+        n = int(w[i + 1])
+        a.append(np.full(n, w[i], dtype=np.uint64))
+        rows.append(w[i + 2:i + 2 + 2 * n].reshape(n, 2))
+        i += 2 + 2 * n
+    if not rows:
+        return np.zeros((0, 2), np.uint64), np.zeros(0, np.uint64)
+    bc = np.concatenate(rows, axis=0)
+    return np.stack([np.concatenate(a), bc[:, 0]], axis=1), np.ascontiguousarray(bc[:, 1])
+
+
+def computeAndSerializeLabelOverlaps(labels, values, outPath, outKey, chunkId,  # noqa: N802,N803
+                                     withIgnoreLabel=False, ignoreLabel=0):  # noqa: N803
+    """The overlaps of ``labels`` (the block's watershed) with ``values`` (the
+    labels to map onto the nodes), as one varlen chunk of ``outKey`` at
+    ``chunkId`` (node_labels/block_node_labels.py:161).  With
+    ``withIgnoreLabel`` voxels whose *value* is ``ignoreLabel`` are skipped
+    (block_node_labels.py:152-156 applies the ignore label to that volume;
+    unpinned).  No chunk is written when no voxel counts."""
+    r = rag.label_overlaps_handle(labels, values, ignore_label=int(ignoreLabel) if withIgnoreLabel else None)
+    try:
+        if r.n_edges == 0:
+            return
+        words = encode_overlap_chunk(r.edges(), r.counts())
+    finally:
+        r.free()
+    with _open(outPath) as f:
+        f[outKey].write_chunk([int(c) for c in chunkId], words, True)
+
+
+def _grid_positions(ds):
+    import itertools
+    return list(itertools.product(*[range((int(s) + int(c) - 1) // int(c)) for s, c in zip(ds.shape, ds.chunks)]))
+
+
+def mergeAndSerializeOverlaps(inputPath, inputKey, outputPath, outputKey, max_overlap,  # noqa: N802,N803
+                              labelBegin, labelEnd, numberOfThreads=1, ignoreLabel=0,  # noqa: N803
+                              serializeCount=False):  # noqa: N803
+    """Merge the block overlap chunks of ``inputKey`` for the nodes in
+    [labelBegin, labelEnd) (node_labels/merge_node_labels.py:149-155): equal
+    (node, label) pairs add their counts on the GPU.  ``max_overlap=True``
+    writes ``out[labelBegin:labelEnd]`` = the label of the largest overlap per
+    node (0 for nodes without a row; equal overlaps go to the smallest label),
+    as (n, 2) rows (label, count) with ``serializeCount``;
+    ``max_overlap=False`` writes the merged table as one varlen chunk of the
+    block format at ``labelBegin // chunk``.  ``ignoreLabel`` is accepted and
+    has no further effect: the block stage already dropped those pairs, and the
+    caller passes 0 both for "none" and for "0" (merge_node_labels.py:154)."""
+    begin, end = int(labelBegin), int(labelEnd)
+    with _open(inputPath, 'r') as f:
+        ds = f[inputKey]
+        chunks = ds.read_chunks(_grid_positions(ds), numberOfThreads)
+    parts = []
+    for c in chunks:
+        if c is None or not len(c):
+            continue
+        p, n = decode_overlap_chunk(c)
+        sel = (p[:, 0] >= begin) & (p[:, 0] < end)
+        if sel.any():
+            parts.append((p[sel], n[sel]))
+    pairs = np.concatenate([p for p, _ in parts]) if parts else np.zeros((0, 2), np.uint64)
+    counts = np.concatenate([n for _, n in parts]) if parts else np.zeros(0, np.uint64)
+    r = rag.merge_overlaps_handle(pairs, counts)
+    try:
+        with _open(outputPath) as f:
+            out = f[outputKey]
+            if max_overlap:
+                best, n_best = rag.max_overlaps(r, begin, end)
+                if serializeCount:
+                    out[begin:end, :] = np.stack([best, n_best], axis=1)
+                else:
+                    out[begin:end] = best
+            elif r.n_edges:
+                out.write_chunk([begin // int(out.chunks[0])] + [0] * (out.ndim - 1),
+                                encode_overlap_chunk(r.edges(), r.counts()), True)
+    finally:
+        r.free()
+
+
+def deserializeOverlapChunk(path, key, chunkId=None):  # noqa: N802,N803
+    """({node: {label: count}}, largest node id in the chunk) of the overlap
+    chunk at ``chunkId`` (test/node_labels/test_node_labels.py:124,144,
+    evaluation/measures.py:122); ({}, 0) for a missing chunk.  The
+    two-argument form (dataset_path, chunkId) of
+    lifted_features/lifted_feature_workflow.py:42 names the dataset by its path
+    inside the container.  The second element is unpinned: every caller in the
+    reference discards it."""
+    if chunkId is None:
+        chunkId = key
+        path, key = _split_container_path(str(path))
+    with _open(path, 'r') as f:
+        words = f[key].read_chunk([int(c) for c in chunkId])
+    if words is None or not len(words):
+        return {}, 0
+    pairs, counts = decode_overlap_chunk(words)
+    out = {}
+    for (a, b), c in zip(pairs.tolist(), counts.tolist()):
+        out.setdefault(a, {})[b] = c
+    return out, int(pairs[:, 0].max())

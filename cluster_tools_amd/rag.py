@@ -92,7 +92,18 @@ class Result:
         L.check(L.load().ctg_result_copy_stats(self.handle, _ptr(s), _ptr(r), L.CTG_MEM_HOST), 'copy_stats')
         return s, r
 
+    def counts(self):
+        """(E,) uint64 voxel counts of an overlaps result."""
+        out = np.empty(self.n_edges, dtype=np.uint64)
+        L.check(L.load().ctg_result_copy_counts(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_counts')
+        return out
+
     # --- device copies (torch)
+    def counts_torch(self):
+        """(E,) int64 tensor of the uint64 counts of an overlaps result."""
+        import torch
+        return self._torch_copy((self.n_edges,), torch.int64, L.load().ctg_result_copy_counts)
+
     def _torch_copy(self, shape, dtype, fn):
         import torch
         t = torch.empty(shape, dtype=dtype, device='cuda:%d' % self.device)
@@ -529,6 +540,131 @@ def map_edge_ids(global_edges, query):
     rc = lib.ctg_map_edge_ids(_ptr(g), g.shape[0], _ptr(q), q.shape[0], _ptr(out), L.CTG_MEM_HOST, None)
     L.check(rc, 'ctg_map_edge_ids')
     return out
+
+
+def _label_volume(x, name):
+    """A label volume argument -> (array, bits): a contiguous CUDA tensor as it
+    is, anything else as a C-contiguous numpy array of 32- or 64-bit labels."""
+    if _is_torch(x):
+        if not (x.is_cuda and x.is_contiguous()) or x.element_size() not in (4, 8) or x.is_floating_point():
+            raise ValueError('%s must be a contiguous CUDA tensor of 32- or 64-bit integers' % name)
+        return x, x.element_size() * 8
+    x = np.asarray(x)
+    if x.dtype.kind not in 'ui':
+        raise TypeError('%s must hold integer labels, got %s' % (name, x.dtype))
+    if x.dtype not in (np.uint64, np.uint32, np.int64, np.int32):
+        x = x.astype(np.uint64)
+    return np.ascontiguousarray(x), x.dtype.itemsize * 8
+
+
+def label_overlaps_handle(labels, values, begin=None, end=None, ignore_label=None, stream=None):
+    """ctg_label_overlaps -> the device-resident ``Result``: edges() = the
+    distinct (labels[p], values[p]) pairs of the box [begin, end), sorted;
+    counts() = their voxel counts; nodes() = the distinct labels.  Voxels whose
+    *value* equals ``ignore_label`` are skipped (None: every voxel counts,
+    zeros included).  Both volumes numpy arrays or both CUDA tensors, (Z,Y,X),
+    32- or 64-bit integers."""
+    if _is_torch(labels) != _is_torch(values):
+        raise ValueError('labels and values must both be numpy arrays or both CUDA tensors')
+    labels, lbits = _label_volume(labels, 'labels')
+    values, vbits = _label_volume(values, 'values')
+    shape = tuple(labels.shape)
+    if len(shape) != 3:
+        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
+    if tuple(values.shape) != shape:
+        raise ValueError('values shape %s != labels shape %s' % (tuple(values.shape), shape))
+    for box in (begin, end):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end must have 3 entries')
+    if ignore_label is not None and not 0 <= int(ignore_label) < 1 << 64:
+        raise ValueError('ignore_label must be a uint64 value or None, got %r' % (ignore_label,))
+    lib = L.load()
+    dev = L.init_device()
+    on_dev = _is_torch(labels)
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_label_overlaps(_ptr(labels), lbits, _ptr(values), vbits, _shape_arr(shape),
+                                _shape_arr(begin) if begin is not None else None,
+                                _shape_arr(end) if end is not None else None,
+                                int(ignore_label is not None), int(ignore_label or 0),
+                                L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+    L.check(rc, 'ctg_label_overlaps')
+    return Result(h, dev)
+
+
+def _overlap_tables(r):
+    return dict(pairs=r.edges(), counts=r.counts(), nodes=r.nodes())
+
+
+def label_overlaps(labels, values, begin=None, end=None, ignore_label=None):
+    """Host convenience of label_overlaps_handle: dict(pairs (E,2), counts (E,),
+    nodes (N,)) as uint64 numpy arrays (+ n_records, n_direct)."""
+    r = label_overlaps_handle(labels, values, begin, end, ignore_label)
+    out = _overlap_tables(r)
+    out['n_records'], out['n_direct'] = r.info()
+    r.free()
+    return out
+
+
+def merge_overlaps_handle(pairs, counts, stream=None):
+    """ctg_merge_overlaps: rows (a, b) with counts, in any order -> the sorted
+    table in which equal pairs have added their counts (``Result``)."""
+    on_dev = _is_torch(pairs)
+    if on_dev != _is_torch(counts):
+        raise ValueError('pairs and counts must both be numpy arrays or both CUDA tensors')
+    if on_dev:
+        for t in (pairs, counts):
+            if not (t.is_cuda and t.is_contiguous()) or t.element_size() != 8 or t.is_floating_point():
+                raise ValueError('merge inputs must be contiguous 64-bit integer CUDA tensors')
+        n = int(counts.numel())
+        if int(pairs.numel()) != 2 * n:
+            raise ValueError('%d pair entries for %d counts' % (int(pairs.numel()), n))
+    else:
+        pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
+        counts = np.ascontiguousarray(np.asarray(counts, dtype=np.uint64).reshape(-1))
+        n = counts.shape[0]
+        if pairs.shape[0] != n:
+            raise ValueError('%d pairs for %d counts' % (pairs.shape[0], n))
+    lib = L.load()
+    dev = L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_merge_overlaps(_ptr(pairs), _ptr(counts), n, L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream,
+                                ctypes.byref(h))
+    L.check(rc, 'ctg_merge_overlaps')
+    return Result(h, dev)
+
+
+def merge_overlaps(pairs, counts):
+    """Host convenience of merge_overlaps_handle: dict(pairs, counts, nodes)."""
+    r = merge_overlaps_handle(pairs, counts)
+    out = _overlap_tables(r)
+    r.free()
+    return out
+
+
+def max_overlaps(handle_or_tables, label_begin, label_end):
+    """Per label in [label_begin, label_end) the value it overlaps most and
+    that overlap: (labels, counts), uint64 arrays of label_end - label_begin
+    entries, 0 / 0 for labels without a row; equal counts go to the smallest
+    value.  ``handle_or_tables``: a ``Result`` of label_overlaps_handle /
+    merge_overlaps_handle, or a dict with 'pairs' and 'counts' (merged first)."""
+    lb, le = int(label_begin), int(label_end)
+    if lb < 0 or le < lb:
+        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
+    own = not isinstance(handle_or_tables, Result)
+    r = merge_overlaps_handle(handle_or_tables['pairs'], handle_or_tables['counts']) if own else handle_or_tables
+    out_l = np.zeros(le - lb, dtype=np.uint64)
+    out_c = np.zeros(le - lb, dtype=np.uint64)
+    try:
+        L.check(L.load().ctg_max_overlaps(r.handle, lb, le, _ptr(out_l), _ptr(out_c), L.CTG_MEM_HOST, None),
+                'ctg_max_overlaps')
+    finally:
+        if own:
+            r.free()
+    return out_l, out_c
 
 
 def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_offset=0, noise_amp=0.1,

@@ -16,6 +16,11 @@ datasets and attributes it creates, and its jobs -- ``block_list[k::n_jobs]``
                        filter branch _accumulate_with_filters :151-272 on the GPU filters)
     MergeEdgeFeatures  merge_edge_features.py:35-84, job :110-149
 
+and ``NodeLabelWorkflow`` (node_labels/node_label_workflow.py), full-volume labels:
+
+    BlockNodeLabels    node_labels/block_node_labels.py:48-102, job :133-165
+    MergeNodeLabels    node_labels/merge_node_labels.py:42-88, job :121-156
+
 Job execution (``mode``):
   * ``'processes'`` -- the reference's process model: ``LocalTask._submit``
     starts every job as its own process (``call([script, config])`` in a
@@ -207,6 +212,74 @@ def graph_workflow(input_path, input_key, graph_path, output_key, block_shape, m
                               compression='gzip', dtype='uint64')
         _run_single(functools.partial(_map_edge_ids_job, graph_path, output_key, block_list, threads_per_job),
                     mode)
+    return timer
+
+
+def _block_node_labels_job(ws_path, ws_key, input_path, input_key, output_path, output_key, block_shape,
+                           ignore_label, blocks):
+    """block_node_labels.py:133-165 (_labels_for_block), full-volume labels."""
+    with ndist._open(ws_path, 'r') as fw, ndist._open(input_path, 'r') as fl:
+        ds_ws, ds_labels = fw[ws_key], fl[input_key]
+        blk = blocking([0, 0, 0], list(ds_ws.shape), list(block_shape))
+        for b in blocks:
+            block = blk.getBlock(b)
+            bb = tuple(slice(x, y) for x, y in zip(block.begin, block.end))
+            ws = ds_ws[bb]
+            if ws.sum() == 0:                                     # :143-146 empty watershed block
+                continue
+            labs = ds_labels[bb].astype('uint64')
+            if ignore_label is not None and np.sum(labs == ignore_label) == labs.size:   # :152-156
+                continue
+            chunk_id = tuple(x // c for x, c in zip(block.begin, block_shape))
+            ndist.computeAndSerializeLabelOverlaps(ws, labs, output_path, output_key, chunk_id,
+                                                   withIgnoreLabel=ignore_label is not None,
+                                                   ignoreLabel=0 if ignore_label is None else ignore_label)
+
+
+def _merge_node_labels_job(input_path, input_key, output_path, output_key, max_overlap, node_shape, node_chunks,
+                           ignore_label, serialize_counts, threads_per_job, blocks):
+    """merge_node_labels.py:142-155."""
+    blk = blocking([0], list(node_shape), list(node_chunks))
+    for b in blocks:
+        block = blk.getBlock(b)
+        ndist.mergeAndSerializeOverlaps(input_path, input_key, output_path, output_key, max_overlap=max_overlap,
+                                        labelBegin=block.begin[0], labelEnd=block.end[0],
+                                        numberOfThreads=threads_per_job,
+                                        ignoreLabel=0 if ignore_label is None else ignore_label,
+                                        serializeCount=serialize_counts)
+
+
+def node_label_workflow(ws_path, ws_key, input_path, input_key, output_path, output_key, block_shape, max_id,
+                        max_overlap=True, ignore_label=None, serialize_counts=False, node_chunk=100000,
+                        prefix='', max_jobs=1, threads_per_job=4, timer=None, mode='threads'):
+    """NodeLabelWorkflow (node_labels/node_label_workflow.py): BlockNodeLabels
+    into the varlen dataset ``label_overlaps_<prefix>`` (block_node_labels.py:
+    65-86; ``max_id`` is the watershed's maxId attribute), then MergeNodeLabels
+    over node ranges of ``node_chunk`` (merge_node_labels.py:50-77; 100000 in
+    the reference) into ``output_key``."""
+    timer = timer or Timer()
+    tmp_key = 'label_overlaps_%s' % prefix
+    with ndist._open(ws_path, 'r') as f:
+        shape = list(f[ws_key].shape)
+    block_list = blocks_in_volume(shape, block_shape)
+    with timer.stage('block_node_labels'):
+        with ndist._open(output_path) as f:                     # block_node_labels.py:78-86
+            ds = f.require_dataset(tmp_key, shape=shape, dtype='uint64', compression='gzip',
+                                   chunks=[min(b, s) for b, s in zip(block_shape, shape)])
+            ds.attrs['maxId'] = int(max_id)
+        job = functools.partial(_block_node_labels_job, ws_path, ws_key, input_path, input_key, output_path, tmp_key,
+                                list(block_shape), ignore_label)
+        _run_jobs(job, _jobs(block_list, max_jobs), mode)
+    with timer.stage('merge_node_labels'):
+        n_labels = int(max_id) + 1                                # merge_node_labels.py:50-55
+        node_shape, node_chunks = (n_labels,), (min(n_labels, int(node_chunk)),)
+        ds_shape = node_shape + (2,) if serialize_counts else node_shape      # :69-77
+        ds_chunks = node_chunks + (1,) if serialize_counts else node_chunks
+        with ndist._open(output_path) as f:
+            f.require_dataset(output_key, shape=ds_shape, chunks=ds_chunks, compression='gzip', dtype='uint64')
+        job = functools.partial(_merge_node_labels_job, output_path, tmp_key, output_path, output_key, max_overlap,
+                                node_shape, node_chunks, ignore_label, serialize_counts, threads_per_job)
+        _run_jobs(job, _jobs(blocks_in_volume(node_shape, node_chunks), max_jobs), mode)
     return timer
 
 

@@ -25,6 +25,10 @@
  *   ctg_merge_feature_rows            <- ndist.mergeFeatureBlocks on reference-layout
  *                                        (10-column) sub_features rows,
  *                                        features/merge_edge_features.py:141-147
+ *   ctg_label_overlaps                <- ndist.computeAndSerializeLabelOverlaps
+ *                                        node_labels/block_node_labels.py:161
+ *   ctg_merge_overlaps, ctg_max_overlaps <- ndist.mergeAndSerializeOverlaps
+ *                                        node_labels/merge_node_labels.py:149
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -231,6 +235,47 @@ int ctg_merge_feature_rows(const uint64_t* ids, const double* rows, int64_t n, i
  * edge lists, ndist.mergeSubgraphs); result nodes = unique endpoints */
 int ctg_unique_pairs(const uint64_t* pairs, int64_t n, int mem, void* stream, ctg_result** out);
 
+/*
+ * Label overlaps (NodeLabelWorkflow): the contingency table of two label
+ * volumes over the box [begin, end) (NULL = 0 / shape) -- for every pair
+ * (a, b) = (labels[p], values[p]) that occurs, the number of voxels p.
+ * Replaces the array work of ndist.computeAndSerializeLabelOverlaps
+ * (node_labels/block_node_labels.py:161; its N5 chunk is written by
+ * cluster_tools_amd/ndist.py).
+ *   labels, values  uint64 (bits = 64) or uint32 (bits = 32), C-order (Z,Y,X),
+ *                   both of `shape`; any label value, 2^32 and above included
+ *   with_ignore     skip voxels whose *value* equals ignore_label
+ *                   (block_node_labels.py:152-156 applies it to that volume)
+ * Result: edges = the distinct (a, b) pairs, sorted lexicographically;
+ * ctg_result_copy_counts = their voxel counts (uint64); nodes = the distinct a,
+ * ascending.  An empty box, or one whose every voxel is ignored, gives an
+ * empty result; a box outside the array is CTG_ERR_ARG; a box of 2^32 voxels
+ * or more is CTG_ERR_UNSUPPORTED.  ctg_result_info: the (pair, count) records
+ * the scan wrote, and how many of them bypassed the workgroup tables.
+ * The overlaps calls keep their records in buffers of their own: they leave the
+ * workspace's records alone, so a CTG_DEFER_STATS handle of the same device
+ * stays valid across them.
+ */
+int ctg_label_overlaps(const void* labels, int label_bits, const void* values, int value_bits,
+                       const int64_t* shape, const int64_t* begin, const int64_t* end,
+                       int with_ignore, uint64_t ignore_label, int mem, void* stream, ctg_result** out);
+
+/* Combine partial overlap tables -- n rows (a, b) with uint64 counts, in any
+ * order -- into one table of the form above: equal pairs add their counts.
+ * The array work of ndist.mergeAndSerializeOverlaps
+ * (node_labels/merge_node_labels.py:149). */
+int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n, int mem, void* stream,
+                       ctg_result** out);
+
+/* Per label a in [label_begin, label_end): out_labels[a - label_begin] = the b
+ * with the largest count in the overlaps result r, out_counts (may be NULL) =
+ * that count; 0 / 0 for labels without a row.  Equal counts go to the smallest
+ * b (nifty's rule is not in the reference; test/node_labels/test_node_labels.py:31-33
+ * masks ties out).  The max_overlap branch of ndist.mergeAndSerializeOverlaps
+ * (node_labels/merge_node_labels.py:149-155). */
+int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_end, uint64_t* out_labels,
+                     uint64_t* out_counts, int mem, void* stream);
+
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
                      const uint64_t* query, int64_t n_query, int64_t* out_ids,
@@ -243,6 +288,8 @@ int ctg_result_copy_edges(const ctg_result* r, uint64_t* dst, int mem);
 int ctg_result_copy_nodes(const ctg_result* r, uint64_t* dst, int mem);
 int ctg_result_copy_features(const ctg_result* r, double* dst, int mem);
 int ctg_result_copy_stats(const ctg_result* r, double* sums_dst, uint32_t* records_dst, int mem);
+/* the (E,) uint64 voxel counts of an overlaps result (ctg_label_overlaps, ctg_merge_overlaps) */
+int ctg_result_copy_counts(const ctg_result* r, uint64_t* dst, int mem);
 /* device pointers for zero-copy consumers (valid until ctg_free) */
 const uint64_t* ctg_result_device_edges(const ctg_result* r);
 const double* ctg_result_device_features(const ctg_result* r);
@@ -319,7 +366,8 @@ int ctg_trim(void);
 
 /* profiling: per-phase device milliseconds of the last ctg_rag_features call
  * (HIP events on the call's stream): [0] face scan, [1] key pack, [2] sort,
- * [3] segment, [4] reduce+finalize, [5] nodes, [6] total */
+ * [3] segment, [4] reduce+finalize, [5] nodes, [6] total; of a ctg_label_overlaps
+ * call: [0] scan, [2] sort, [3] run heads + prefix sums, [4] run sums, [6] total */
 int ctg_set_profiling(int on);
 int ctg_last_timings(double* ms, int n);
 
@@ -328,7 +376,7 @@ int ctg_last_timings(double* ms, int n);
  * run tables, permutations, node bitmaps, exchange rows) that reached past
  * the current call's count since the last query.  Returns 0 (none) or 1 with
  * out[0] = source file (1 ctg_api, 2 ctg_scan, 3 ctg_sort, 4 ctg_reduce,
- * 5 ctg_mgpu), out[1] = line, out[2] = index, out[3] = bound; clears them.
+ * 5 ctg_mgpu, 6 ctg_overlap), out[1] = line, out[2] = index, out[3] = bound; clears them.
  * Product builds: CTG_ERR_UNSUPPORTED. */
 int ctg_diag_bounds(uint64_t* out);
 
