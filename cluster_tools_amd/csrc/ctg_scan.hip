@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "ctg_internal.h"
+#include "ctg_stats.h"
 
 #ifndef CTG_ROWS
 #define CTG_ROWS 4
@@ -42,6 +43,14 @@
 namespace ctg {
 
 enum { MODE_GRAPH = 0, MODE_BOUNDARY = 1, MODE_AFFINITY = 2, MODE_AFF_NN = 3, MODE_AFF_MIX = 4 };
+
+// Face kernels (graph, boundary map, nearest-neighbour faces) stage a face as
+// its push site holds it and leave the key's order, the block tag and the
+// cheaper FAST40 slot rule to the fold.  The channel-loop kernels keep the
+// ordering at the site and the compare ladder: they sit at 126-128 VGPRs, and
+// with the face kernels' forms MODE_AFF_MIX took 32 B of scratch per lane (the
+// 12-channel scan 42.9 -> 51.5 ms).
+constexpr bool raw_sites(int mode) { return mode != MODE_AFFINITY && mode != MODE_AFF_MIX; }
 
 // y rows per wave, held in registers: 4, or 1 for highly fragmented volumes
 // (the workgroup's tile cross-section, hence its live edge set, shrinks: the
@@ -301,22 +310,6 @@ __device__ __forceinline__ uint32_t load_lo(const LabelT* L, int64_t i) {
     else return (uint32_t)L[i];
 }
 
-// vigra RangeHistogramBase binning of one sample -> slot in [0, NSLOTS)
-// (hist_slot's rule, ctg_internal.h), branch-free on the f64 value the sums
-// use anyway: m = scale * (x - offset); FAST40 (offset 0, scale 40) skips the
-// subtraction -- 40 * x is exact in f64 for every float x, so the slot is the
-// double-precision rule's.  Selects instead of branches: no exec-mask
-// juggling in the fold.
-template <bool FAST40>
-__device__ __forceinline__ int sample_slot(double dx, double scale, double offset) {
-    const double m = FAST40 ? dx * 40.0 : scale * (dx - offset);
-    int s = (int)m + 1;                              // trunc toward zero (v_cvt_i32_f64 saturates)
-    s = m <= -1.0 ? 0 : s;                           // left outlier
-    s = !(m < (double)NBINS) ? NBINS + 1 : s;        // right outlier
-    s = m != m ? 0 : s;                              // NaN -> left
-    return m == (double)NBINS ? NBINS : s;           // index nbins-1
-}
-
 // 2-sample histogram add: one atomic when both samples share a word
 __device__ __forceinline__ void hist_add2(Table& T, int e, int sa, int sb) {
     const uint32_t ia = 1u << ((sa & 1) * 16), ib = 1u << ((sb & 1) * 16);
@@ -419,8 +412,8 @@ __device__ __forceinline__ void fold_stats(Table& T, const StageT& e, int s, uin
         const float b = two ? __uint_as_float(e.w) : a;
         const uint32_t n = adj ? 0u : (two ? 2u : 1u);
         const double da = (double)a, db = (double)b;
-        const int sa = adj ? -1 : sample_slot<FAST40>(da, scale, offset);
-        const int sb = (two && !adj) ? sample_slot<FAST40>(db, scale, offset) : -1;
+        const int sa = adj ? -1 : sample_slot<FAST40, !raw_sites(MODE)>(da, scale, offset);
+        const int sb = (two && !adj) ? sample_slot<FAST40, !raw_sites(MODE)>(db, scale, offset) : -1;
         const uint32_t mn = f2ord(fminf(a, b)), mx = f2ord(fmaxf(a, b));
         const uint32_t mine = pivot_bits(a);
         if (s < 0) {   // a direct record is its own entry: pivot = its first sample
@@ -527,8 +520,8 @@ __device__ __forceinline__ void fold_grouped(Table& T, const StageT (&e)[NPER], 
         const float b = two ? __uint_as_float(e[i].w) : a;
         const double da = (double)a, db = (double)b;
         if (v && !(ablate & 128)) {   // (diagnostic 128: no histogram)
-            const int sa = sample_slot<FAST40>(da, scale, offset);
-            if (two) hist_add2(T, sl, sa, sample_slot<FAST40>(db, scale, offset));
+            const int sa = sample_slot<FAST40, !raw_sites(MODE)>(da, scale, offset);
+            if (two) hist_add2(T, sl, sa, sample_slot<FAST40, !raw_sites(MODE)>(db, scale, offset));
             else atomicAdd(&T.w[sl][sa >> 1], 1u << ((sa & 1) * 16));
         }
         // the entry's pivot: the first sample that claims the empty word (CAS)
@@ -575,15 +568,26 @@ __device__ __forceinline__ void fold_grouped(Table& T, const StageT (&e)[NPER], 
 
 // Fold the wave's nb staged entries into the LDS edge table: NPER entries per
 // lane (lane, lane+64, ...), their stage reads and home-bucket reads issued
-// together so the LDS round trips of the entries overlap.
+// together so the LDS round trips of the entries overlap.  With raw_sites()
+// the stage holds each face's two labels as its push site saw them; the key's
+// (smaller, larger) order -- and, for batched blocks, the block tag or-ed into
+// the smaller label -- is made here, at two instructions per 64 entries.
 template <int MODE, bool FAST40, bool BATCH, typename StageT, int NPER>
-__device__ __forceinline__ void fold_batch(Table& T, const StageT* __restrict__ stage, int nb, int lane, RecordBuf R,
-                                           Counters* C, double scale, double offset, bool& need, int ablate) {
+__device__ __forceinline__ void fold_batch(Table& T, const StageT* __restrict__ stage, int nb, int lane, uint32_t tag,
+                                           RecordBuf R, Counters* C, double scale, double offset, bool& need,
+                                           int ablate) {
     StageT e[NPER];
     uint32_t h[NPER];
     uint4 b01[NPER], b23[NPER];
 #pragma unroll
-    for (int i = 0; i < NPER; ++i) e[i] = stage[lane + WAVE * i];   // past nb: stale, ignored
+    for (int i = 0; i < NPER; ++i) {
+        e[i] = stage[lane + WAVE * i];   // past nb: stale, ignored
+        if constexpr (raw_sites(MODE)) {
+            const uint32_t u = min(e[i].x, e[i].y), v = max(e[i].x, e[i].y);
+            e[i].x = BATCH ? (u | tag) : u;
+            e[i].y = v;
+        }
+    }
     if (ablate & 32) {   // diagnostic: staging only, no fold
 #pragma unroll
         for (int i = 0; i < NPER; ++i)
@@ -938,7 +942,8 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
                 wsamp += add;
             }
             const uint64_t t0 = stamps ? stamp_now() : 0;
-            fold_batch<MODE, FAST40, BATCH, StageT, NP>(T, stage, nbuf, lane, R, C, scale, offset, need, ablate);
+            fold_batch<MODE, FAST40, BATCH, StageT, NP>(T, stage, nbuf, lane, tag, R, C, scale, offset, need,
+                                                        ablate);
             nbuf = 0;
             if (stamps) t_fold += stamp_now() - t0;
             poll();   // after every fold batch (only at plane ends: slower)
@@ -953,10 +958,15 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
         const int k = __popcll(m);
         if (nbuf + k > STAGE_CAP) flush_stage();
         const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        // the face as the site holds it: a site has ~10 live lanes of 64, so
+        // the key's (min, max) order and the block tag are left to the fold,
+        // whose lanes are dense (fold_batch); the channel-loop kernels order
+        // here (raw_sites)
         if (act) {
-            const uint32_t lo_l = BATCH ? (min(a, b) | tag) : min(a, b);
-            if constexpr (STATS) stage[nbuf + rank] = make_uint4(lo_l, max(a, b), za, zb);
-            else stage[nbuf + rank] = make_uint2(lo_l, max(a, b));
+            const uint32_t u = raw_sites(MODE) ? a : (BATCH ? (min(a, b) | tag) : min(a, b));
+            const uint32_t v = raw_sites(MODE) ? b : max(a, b);
+            if constexpr (STATS) stage[nbuf + rank] = make_uint4(u, v, za, zb);
+            else stage[nbuf + rank] = make_uint2(u, v);
         }
         nbuf += k;
     };

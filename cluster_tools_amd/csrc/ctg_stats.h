@@ -9,6 +9,51 @@
 namespace ctg {
 
 // ---------------------------------------------------------------------------
+// histogram slot of one sample in the face scan's fold (ctg_scan.hip)
+// ---------------------------------------------------------------------------
+// f64 -> i32 as v_cvt_i32_f64 does it: toward zero, saturating, NaN -> 0 (the
+// host form spells the same rule out for tools/slot_exact.hip)
+__host__ __device__ __forceinline__ int trunc_sat_i32(double m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (int)m;
+#else
+    return m != m ? 0 : m >= 2147483647.0 ? 2147483647 : m <= -2147483648.0 ? (-2147483647 - 1) : (int)m;
+#endif
+}
+
+// vigra RangeHistogramBase binning of one sample -> slot in [0, NSLOTS)
+// (hist_slot's rule, ctg_internal.h), branch-free on the f64 value the sums
+// use anyway: m = scale * (x - offset).  Selects instead of branches: no
+// exec-mask juggling in the fold.
+//
+// FAST40 (offset 0, scale 40) skips the subtraction -- 40 * x is exact in f64
+// for every float x, so the slot is the double-precision rule's -- and needs no
+// compare ladder: trunc(m) clamped to [-1, 40] (one v_med3_i32; the saturating
+// conversion keeps +-inf and huge values on their side) plus one is the slot
+// of every m except the two whose slot is not trunc(m) + 1: m == 40 (the last
+// bin, slot 40) and NaN (converted to 0, slot 0).  Both are exactly the m for
+// which "m < 40 or m > 40" is false, so that one ordered compare is the
+// increment.  Bit-identical to the ladder for all 2^32 floats
+// (tools/slot_exact.hip, tests/test_slot_exact.py).  LADDER keeps the compare /
+// select form for FAST40 too (the scan's channel-loop kernels, ctg_scan.hip).
+template <bool FAST40, bool LADDER = false>
+__host__ __device__ __forceinline__ int sample_slot(double dx, double scale, double offset) {
+    if constexpr (FAST40 && !LADDER) {
+        const double m = dx * 40.0;
+        const int t = trunc_sat_i32(m);
+        const int c = t < -1 ? -1 : (t > NBINS ? NBINS : t);
+        return c + ((m < (double)NBINS || m > (double)NBINS) ? 1 : 0);
+    } else {
+        const double m = FAST40 ? dx * 40.0 : scale * (dx - offset);
+        int s = trunc_sat_i32(m) + 1;                    // trunc toward zero (v_cvt_i32_f64 saturates)
+        s = m <= -1.0 ? 0 : s;                           // left outlier
+        s = !(m < (double)NBINS) ? NBINS + 1 : s;        // right outlier
+        s = m != m ? 0 : s;                              // NaN -> left
+        return m == (double)NBINS ? NBINS : s;           // index nbins-1
+    }
+}
+
+// ---------------------------------------------------------------------------
 // vigra computeStandardQuantiles as a single streaming walk over the bins
 // ---------------------------------------------------------------------------
 // The keypoints (mapped value, cumulative count) are generated in order; the
