@@ -325,8 +325,9 @@ static int scan_records(Workspace& w, const ScanParams& P, int64_t V, hipStream_
         }
     }
     if (P.ablate & 256)   // diagnostic s_memtime stamps, summed over waves
-        fprintf(stderr, "stamps total %llu fold %llu flush %llu wait %llu\n", w.counters_host->pad[2],
-                w.counters_host->pad[3], w.counters_host->pad[4], w.counters_host->pad[5]);
+        fprintf(stderr, "stamps total %llu fold %llu flush %llu wait %llu drain %llu floor %llu\n",
+                w.counters_host->pad[2], w.counters_host->pad[3], w.counters_host->pad[4], w.counters_host->pad[5],
+                w.counters_host->pad[7], w.counters_host->pad[0]);
 #ifdef CTG_DIAG
     if (PW.wg_times) {   // raw (start, end) pairs; unused slots stay 0; then the flush count
         std::vector<unsigned long long> h(wg_n * 2);
@@ -836,7 +837,8 @@ int ctg_rag_blocks(const void* labels, int label_bits, const void* data, int dat
         int64_t V = 1;
         for (int k = 0; k < 3; ++k) {
             V *= d.shape[k];
-            if (d.shape[k] < 0 || d.shape[k] > 0x7FFFFFFF || d.own_begin[k] < 0 || d.own_end[k] > d.shape[k] ||
+            if (d.shape[k] < 0 || d.shape[k] > (k == 2 ? scan_max_x() : 0x7FFFFFFF) || d.own_begin[k] < 0 ||
+                d.own_end[k] > d.shape[k] ||
                 d.graph_begin[k] < 0 || d.graph_end[k] > d.shape[k]) {
                 set_error("ctg_rag_blocks: block " + std::to_string(b) + ": box outside its array");
                 return CTG_ERR_ARG;

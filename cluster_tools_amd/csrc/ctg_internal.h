@@ -381,6 +381,7 @@ struct Ev {   // phase marks of a profiled call
 // ---------------------------------------------------------------------------
 // ctg_scan.hip
 hipError_t launch_face_scan(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s);
+int64_t scan_max_x();   // widest array (along x) the face scan takes
 int scan_tile_rows();
 int scan_tile_rows_narrow();
 hipError_t launch_density(const void* L, int label_bits, const int64_t* shape, int n_rows, uint32_t* out,

@@ -52,6 +52,17 @@ enum { MODE_GRAPH = 0, MODE_BOUNDARY = 1, MODE_AFFINITY = 2, MODE_AFF_NN = 3, MO
 // 12-channel scan 42.9 -> 51.5 ms).
 constexpr bool raw_sites(int mode) { return mode != MODE_AFFINITY && mode != MODE_AFF_MIX; }
 
+// The face kernels load their plane rows as raw buffer loads: a per-plane
+// descriptor in SGPRs (the wave's rows of one plane), the row offset a scalar,
+// the lane's byte offset a loop-invariant 32-bit VGPR -- no 64-bit vector
+// address arithmetic in the plane loop (load_plane in k_face_scan).  The
+// channel-loop kernels keep per-lane 64-bit pointers: they have no SGPRs or
+// VGPRs to spare (raw_sites above).
+constexpr bool scalar_loads(int mode) { return raw_sites(mode); }
+// byte offsets are 32 bits: the rows a wave reads of one plane (ROWS + 1 of X
+// labels) must stay below 4 GiB (launch_scan_r refuses wider rows)
+constexpr int64_t SCALAR_LOAD_SPAN = 0xFFFFFFFFll;
+
 // y rows per wave, held in registers: 4, or 1 for highly fragmented volumes
 // (the workgroup's tile cross-section, hence its live edge set, shrinks: the
 // table then holds it and flushes -- records -- drop; 2 rows at cell 5: 131 M
@@ -301,6 +312,42 @@ __device__ __forceinline__ float load_val(const DataT* p, int64_t i) {
     } else {
         return p[i];
     }
+}
+
+// a 64-bit value every lane holds alike, in a form the compiler can prove
+// uniform (it then lives in SGPRs)
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
+// Raw buffer descriptor over `bytes` bytes at the uniform address `base`
+// (stride 0, untyped 32-bit data format).  Callers clamp their offsets
+// themselves; the range only bounds what a wrong offset could reach.
+using BufRsrc = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ BufRsrc buf_rsrc(uint64_t base, uint32_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
+}
+
+// element loads through a descriptor: voff the lane's byte offset (VGPR),
+// soff the row's (SGPR); NT: non-temporal, as load_val_stream
+template <typename LabelT>
+__device__ __forceinline__ LabelT buf_label(BufRsrc r, uint32_t voff, uint32_t soff) {
+    if constexpr (sizeof(LabelT) == 8) {
+        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0);
+        return ((uint64_t)v.y << 32) | v.x;
+    } else {
+        return (LabelT)__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0);
+    }
+}
+template <typename DataT, bool NT>
+__device__ __forceinline__ float buf_val(BufRsrc r, uint32_t voff, uint32_t soff) {
+    constexpr int aux = (NT && CTG_NT_AFF) ? 2 : 0;   // bit 1: nt
+    if constexpr (sizeof(DataT) == 1)
+        return __fdiv_rn((float)__builtin_amdgcn_raw_buffer_load_b8(r, (int)voff, (int)soff, aux), 255.0f);
+    else
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, aux));
 }
 
 // low 32 bits of label i (a 4-B gather for 64-bit labels; little-endian)
@@ -838,6 +885,15 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
         if (batch && y < Y && y >= gby && y < gey) grow_x |= 1u << r;
         if (batch && y + 1 < gey && y >= gby) grow_y |= 1u << r;
     }
+    // ... held as scalars from here on: the plane loop picks its site masks
+    // with scalar selects, not a v_cndmask + v_readfirstlane per mask and plane
+    // (the channel-loop kernels keep their code as it was, see scalar_loads)
+    if constexpr (scalar_loads(MODE)) {
+        row_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_x);
+        row_y = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_y);
+        grow_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)grow_x);
+        grow_y = (uint32_t)__builtin_amdgcn_readfirstlane((int)grow_y);
+    }
     // adjacency markers of nearest-neighbour faces (affinities); batched
     // blocks always push them (the block's sub-graph is the edge filter)
     const bool adj_marks = AFF && (batch || !P.skip_adj_marks);
@@ -872,8 +928,56 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
     const int xcl = min(x, X - 1);
     const int xhc = min(xh, X - 1);
     const int64_t csz = (int64_t)Z * sz;   // channel stride (NN3)
+    // scalar_loads(): the same clamped addresses as (uniform base) + (uniform
+    // row offset) + (per-lane offset).  The base is the wave's first row,
+    // clamped to the last row of the plane (waves past Y read that row, as
+    // min(r, rmax) < 0 makes them below); l_off / d_off and the NN3 channel
+    // strides are part of it.  Row r sits rofs[r] elements on, the lane at
+    // xcl, the x-halo lane at its row's start + xhc.
+    const int ywc = min(yw, Y - 1);
+    const int rmaxc = Y - 1 - ywc;   // >= 0
+    const uint64_t lbase = scalar_loads(MODE) ? uniform64((uint64_t)(L + (int64_t)ywc * X)) : 0;
+    const uint64_t dbase = scalar_loads(MODE) && (BND || NN3)
+                               ? uniform64((uint64_t)(D + (NN3 ? (int64_t)P.nn_ch[2] * csz : 0) + (int64_t)ywc * X))
+                               : 0;
+    const uint64_t aybase = scalar_loads(MODE) && NN3 ? uniform64((uint64_t)(D + (int64_t)P.nn_ch[1] * csz + (int64_t)ywc * X)) : 0;
+    const uint64_t azbase = scalar_loads(MODE) && NN3 ? uniform64((uint64_t)(D + (int64_t)P.nn_ch[0] * csz + (int64_t)ywc * X)) : 0;
+    const uint32_t win = (uint32_t)__builtin_amdgcn_readfirstlane((min(ROWS, rmaxc) + 1) * X);   // elements a wave reads of a plane
+    const uint32_t xh_el = (uint32_t)(min(min(lane, ROWS - 1), rmaxc) * X + xhc);                // x-halo lane's element
+    uint32_t rofs[ROWS + 1];
+#pragma unroll
+    for (int r = 0; r <= ROWS; ++r) rofs[r] = (uint32_t)__builtin_amdgcn_readfirstlane(min(r, rmaxc) * X);
     auto load_plane = [&](int z, LabelT (&Lb)[ROWS + 1], float (&Db)[ROWS + 1], LabelT& XL, float& XD,
                           float (&Dyb)[ROWS + 1], float (&Dzb)[ROWS], bool with_z) {
+        if constexpr (scalar_loads(MODE)) {
+            const uint64_t pz = (uint64_t)z * (uint64_t)sz;   // plane offset in elements (uniform)
+            const BufRsrc Lr = buf_rsrc(lbase + pz * sizeof(LabelT), win * (uint32_t)sizeof(LabelT));
+            const BufRsrc Dr = buf_rsrc(dbase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
+            const uint32_t xl = (uint32_t)xcl * (uint32_t)sizeof(LabelT), xd = (uint32_t)xcl * (uint32_t)sizeof(DataT);
+#pragma unroll
+            for (int r = 0; r <= ROWS; ++r) {
+                Lb[r] = buf_label<LabelT>(Lr, xl, rofs[r] * (uint32_t)sizeof(LabelT));
+                if constexpr (BND || NN3) Db[r] = buf_val<DataT, false>(Dr, xd, rofs[r] * (uint32_t)sizeof(DataT));
+                else Db[r] = 0.f;
+            }
+            if constexpr (NN3) {
+                const BufRsrc Yr = buf_rsrc(aybase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
+#pragma unroll
+                for (int r = 1; r <= ROWS; ++r)
+                    Dyb[r] = buf_val<DataT, true>(Yr, xd, rofs[r] * (uint32_t)sizeof(DataT));
+                if (with_z) {
+                    const BufRsrc Zr = buf_rsrc(azbase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
+#pragma unroll
+                    for (int r = 0; r < ROWS; ++r)
+                        Dzb[r] = buf_val<DataT, true>(Zr, xd, rofs[r] * (uint32_t)sizeof(DataT));
+                }
+            }
+            // x-halo (lane r < ROWS: row r's voxel at x = x0 + 64, see below)
+            XL = buf_label<LabelT>(Lr, xh_el * (uint32_t)sizeof(LabelT), 0u);
+            if constexpr (BND || NN3) XD = buf_val<DataT, false>(Dr, xh_el * (uint32_t)sizeof(DataT), 0u);
+            else XD = 0.f;
+            return;
+        }
         const LabelT* Lz = L + (int64_t)z * sz + (int64_t)yw * X;
         const DataT* Dz = BND ? D + (int64_t)z * sz + (int64_t)yw * X
                               : NN3 ? D + (int64_t)P.nn_ch[2] * csz + (int64_t)z * sz + (int64_t)yw * X : nullptr;
@@ -914,7 +1018,7 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
     uint32_t wsamp = 0;   // samples this wave folded since the last flush (wave-uniform)
     // diagnostic 256: s_memtime stamps per wave (fold, flush, prefetch wait, total)
     const bool stamps = (ablate & 256) != 0;
-    uint64_t t_fold = 0, t_flush = 0, t_wait = 0;
+    uint64_t t_fold = 0, t_flush = 0, t_wait = 0, t_drain = 0, t_floor = 0;
     const uint64_t t_start = stamps ? stamp_now() : 0;
     auto poll = [&]() {
         if (__ballot(need)) {
@@ -945,6 +1049,19 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
             fold_batch<MODE, FAST40, BATCH, StageT, NP>(T, stage, nbuf, lane, tag, R, C, scale, offset, need,
                                                         ablate);
             nbuf = 0;
+            if (stamps) {
+                // what a flag read behind the fold waits for: LDS returns in
+                // order, so its s_waitcnt drains the batch's atomics.  The
+                // first stamp is issued behind them and waited for together
+                // with them; the second pair, with nothing outstanding, is
+                // the stamps' own latency (t_floor)
+                uint64_t a, b, c, d;
+                asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)\n\t"
+                             "s_memtime %2\n\ts_waitcnt lgkmcnt(0)\n\ts_memtime %3\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d)::"memory");
+                t_drain += b - a;
+                t_floor += d - c;
+            }
             if (stamps) t_fold += stamp_now() - t0;
             poll();   // after every fold batch (only at plane ends: slower)
         }
@@ -1231,6 +1348,8 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
         atomicAdd(&C->pad[3], (unsigned long long)t_fold);
         atomicAdd(&C->pad[4], (unsigned long long)t_flush);
         atomicAdd(&C->pad[5], (unsigned long long)t_wait);
+        atomicAdd(&C->pad[7], (unsigned long long)t_drain);
+        atomicAdd(&C->pad[0], (unsigned long long)t_floor);   // (free under 256: pad[0] is ablation 8's)
     }
 }
 
@@ -1277,6 +1396,7 @@ static hipError_t launch_scan_r(const ScanParams& P, const RecordBuf& R, Counter
     }
     if (nwg <= 0) return hipSuccess;
     if (nwg > 0x7FFFFFFF) return hipErrorInvalidValue;
+    if (scalar_loads(MODE) && !P.blocks && P.shape[2] > scan_max_x()) return hipErrorInvalidValue;
     dim3 grid((unsigned)nwg);
     constexpr unsigned pad = 0;   // dynamic LDS
     if (P.blocks) {
@@ -1372,6 +1492,8 @@ hipError_t launch_density(const void* L, int label_bits, const int64_t* shape, i
     return hipGetLastError();
 }
 
+// widest row (voxels along x) the face kernels' 32-bit byte offsets reach
+int64_t scan_max_x() { return SCALAR_LOAD_SPAN / (8 * (std::max(ROWS_WIDE, ROWS_NARROW) + 1)); }
 int scan_tile_rows() { return WG_ROWS; }
 int scan_tile_rows_narrow() { return ROWS_NARROW * WAVES; }
 

@@ -93,7 +93,9 @@ int ctg_device_count(int* count);
 
 /*
  * RAG (+ edge features) of one 3-D label array.
- *   labels     uint64 (label_bits=64) or uint32 (label_bits=32), C-order (Z,Y,X)
+ *   labels     uint64 (label_bits=64) or uint32 (label_bits=32), C-order (Z,Y,X);
+ *              X at most 2^32 / 40 (107 M) voxels: the scan's row loads carry
+ *              32-bit byte offsets (wider arrays are refused)
  *   data       NULL, boundary map (Z,Y,X) or channel-first affinities (C,Z,Y,X)
  *   offsets    NULL for a boundary map, else n_channels x 3 int32 (z,y,x) offsets
  *   own_begin, own_end  faces / samples are counted only when their owning
