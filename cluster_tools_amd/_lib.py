@@ -29,6 +29,7 @@ CTG_MAX_CHANNELS = 24
 CTG_N_FEATURES = 10
 CTG_NBINS = 40
 CTG_WIDE_RECORD_WORDS = 48
+CTG_MORPH_COLS = 11
 CTG_MGPU_SAMPLES = 1024
 CTG_MGPU_ROW_WORDS = 28
 CTG_MGPU_MAX_WORLD = 32
@@ -83,6 +84,11 @@ PROTOTYPES = {
     'ctg_merge_overlaps': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
     'ctg_max_overlaps': (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_copy_counts': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
+    'ctg_morphology': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp,
+                                      ctypes.POINTER(c_vp)]),
+    'ctg_merge_morphology': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_result_copy_moments': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
+    'ctg_morphology_rows': (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_int, c_vp]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

@@ -553,15 +553,16 @@ int ctg_diag_bounds(uint64_t* out) {
 #ifdef CTG_DIAG
     if (!out) return CTG_ERR_ARG;
     CTG_CHECK(hipDeviceSynchronize());
-    hipError_t (*take[6])(unsigned long long*) = {bounds_take_api,    bounds_take_scan, bounds_take_sort,
-                                                   bounds_take_reduce, bounds_take_mgpu, bounds_take_overlap};
+    hipError_t (*take[7])(unsigned long long*) = {bounds_take_api,    bounds_take_scan, bounds_take_sort,
+                                                   bounds_take_reduce, bounds_take_mgpu, bounds_take_overlap,
+                                                   bounds_take_morph};
     out[0] = out[1] = out[2] = out[3] = 0;
     int found = 0;
-    for (int f = 0; f < 6; ++f) {
+    for (int f = 0; f < 7; ++f) {
         unsigned long long h[3] = {0, 0, 0};
         CTG_CHECK(take[f](h));
         if (h[0] && !found) {
-            out[0] = (uint64_t)f + 1;   // 1 api, 2 scan, 3 sort, 4 reduce, 5 mgpu, 6 overlap
+            out[0] = (uint64_t)f + 1;   // 1 api, 2 scan, 3 sort, 4 reduce, 5 mgpu, 6 overlap, 7 morph
             out[1] = h[0];
             out[2] = h[1];
             out[3] = h[2];
@@ -1249,24 +1250,25 @@ static ResultPtr empty_overlaps(int device) {
     return r;
 }
 
-// One side of ctg_label_overlaps whose labels reach 2^32: the box's sorted
-// unique labels U and the whole array as 32-bit ranks in U (monotone; voxels
-// outside the box get some rank and are never read).
+// A label volume of ctg_label_overlaps / ctg_morphology whose labels reach
+// 2^32: the box's sorted unique labels U and the whole array as 32-bit ranks in
+// U (monotone; voxels outside the box get some rank and are never read).
 struct DenseSide {
     ResultPtr U;
     DevBuf<uint32_t> ids;
-    int build(const void* vol, const int64_t* shape, const int64_t* b, const int64_t* e, void* stream) {
+    int build(const void* vol, const int64_t* shape, const int64_t* b, const int64_t* e, void* stream,
+              const char* who = "ctg_label_overlaps") {
         int rc = nested(U, [&](ctg_result** u) {
             return ctg_unique_labels((const uint64_t*)vol, shape, b, e, CTG_MEM_DEVICE, stream, u);
         });
         if (rc) return rc;
         if (U->n_nodes > 0xFFFFFFFFll) {
-            set_error("ctg_label_overlaps: more than 2^32 distinct labels in one box");
+            set_error(std::string(who) + ": more than 2^32 distinct labels in one box");
             return CTG_ERR_UNSUPPORTED;
         }
         const int64_t V = shape[0] * shape[1] * shape[2];
         if (!ids.alloc((size_t)V * 4)) {
-            set_error("ctg_label_overlaps: out of device memory for the dense relabelling");
+            set_error(std::string(who) + ": out of device memory for the dense relabelling");
             return CTG_ERR_NOMEM;
         }
         CTG_CHECK(launch_remap_dense((const uint64_t*)vol, V, U->nodes, U->n_nodes, ids, (hipStream_t)stream));
@@ -1441,6 +1443,170 @@ int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_e
     return CTG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// segment morphology (kernels and back half: ctg_morph.hip)
+// ---------------------------------------------------------------------------
+// a morphology result without rows: the placeholders of empty_result plus the moments'
+static ResultPtr empty_morphology(int device) {
+    ResultPtr r = empty_result(device);
+    r->moments = (uint64_t*)dev_alloc(8);
+    return r;
+}
+
+int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, const int64_t* begin, const int64_t* end,
+                   const int64_t* origin, int mem, void* stream, ctg_result** out) {
+    DevLock dev_lock;
+    if (!labels || !shape || !out) {
+        set_error("ctg_morphology: null argument");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (label_bits != 32 && label_bits != 64) {
+        set_error("ctg_morphology: label_bits must be 32 or 64");
+        return CTG_ERR_ARG;
+    }
+    int64_t b[3], e[3], o[3];
+    for (int k = 0; k < 3; ++k) {
+        b[k] = begin ? begin[k] : 0;
+        e[k] = end ? end[k] : shape[k];
+        o[k] = origin ? origin[k] : 0;
+        if (shape[k] < 0 || b[k] < 0 || e[k] > shape[k] || b[k] > e[k]) {
+            set_error("ctg_morphology: box outside the array");
+            return CTG_ERR_ARG;
+        }
+        // a coordinate below 2^31 and fewer than 2^32 voxels: no sum reaches 2^63
+        if (o[k] < 0 || o[k] >= (1ll << 31) || o[k] + e[k] >= (1ll << 31)) {
+            set_error("ctg_morphology: origin + end must stay below 2^31 on every axis (origin >= 0)");
+            return CTG_ERR_ARG;
+        }
+    }
+    const int64_t nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
+    if (nb >= 0xFFFFFFFFll) {   // (a record per voxel at most; the run table numbers records in 32 bits)
+        set_error("ctg_morphology: boxes of 2^32 voxels or more are not supported");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    const int dev = current_device();
+    Workspace& w = ws(dev);
+    CTG_CHECK(ws_init(w));
+    hipStream_t s = (hipStream_t)stream;
+    ResultPtr r = empty_morphology(dev);
+    if (nb == 0) {
+        *out = r.release();
+        return CTG_OK;
+    }
+    const int64_t V = shape[0] * shape[1] * shape[2];
+    const void* dl = nullptr;
+    int rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
+    if (rc) return rc;
+    unsigned over = 0;
+    if ((rc = overlap_status(morph_tables(w, dl, label_bits, shape, b, e, o, s, r.get(), &over), "ctg_morphology")) !=
+        CTG_OK)
+        return rc;
+    if (over) {
+        // labels >= 2^32 do not fit the table's 32-bit keys: the scan runs again
+        // on the monotone dense ids, and the sorted labels map back
+        DenseSide d;
+        if ((rc = d.build(dl, shape, b, e, stream, "ctg_morphology")) != CTG_OK) return rc;
+        unsigned again = 0;
+        if ((rc = overlap_status(morph_tables(w, d.ids.p, 32, shape, b, e, o, s, r.get(), &again),
+                                 "ctg_morphology")) != CTG_OK)
+            return rc;
+        if (again) {
+            set_error("ctg_morphology: dense ids past 2^32");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        CTG_CHECK(launch_gather_labels(d.U->nodes, r->nodes, r->n_nodes, s));
+    }
+    if (w.profiling) {
+        if ((rc = read_phase_times(w, s)) != CTG_OK) return rc;
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    w.last_records = r->n_records;
+    w.last_direct = r->n_direct;
+    *out = r.release();
+    return CTG_OK;
+}
+
+int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
+    DevLock dev_lock;
+    if (!out || n < 0 || (n > 0 && !rows)) {
+        set_error("ctg_merge_morphology: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (n >= 0xFFFFFFFFll) {
+        set_error("ctg_merge_morphology: 2^32 rows or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    const int dev = current_device();
+    Workspace& w = ws(dev);
+    CTG_CHECK(ws_init(w));
+    hipStream_t s = (hipStream_t)stream;
+    ResultPtr r = empty_morphology(dev);
+    if (n == 0) {
+        *out = r.release();
+        return CTG_OK;
+    }
+    DevInput<double> dr;
+    int rc = dr.put(rows, (size_t)n * CTG_MORPH_COLS * 8, mem, s, "ctg_merge_morphology");
+    if (rc) return rc;
+    int bad = 0;
+    if ((rc = overlap_status(morph_merge(w, dr, n, s, r.get(), &bad), "ctg_merge_morphology")) != CTG_OK) return rc;
+    if (bad) {
+        set_error("ctg_merge_morphology: a row's id is not an integer in [0, 2^53), or its size, centre or box is "
+                  "negative or not finite");
+        return CTG_ERR_ARG;
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    *out = r.release();
+    return CTG_OK;
+}
+
+int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end, double* out, double* rows,
+                        int mem, void* stream) {
+    DevLock dev_lock;
+    if (!r || label_end < label_begin) {
+        set_error("ctg_morphology_rows: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (!r->moments) {
+        set_error("ctg_morphology_rows: not a morphology result (ctg_morphology, ctg_merge_morphology)");
+        return CTG_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = r->n_nodes;
+    if (N > 0) {   // the id column is a float64: the largest label (the last: nodes ascend) must fit it
+        uint64_t top = 0;
+        CTG_CHECK(hipMemcpyAsync(&top, r->nodes + (N - 1), 8, hipMemcpyDeviceToHost, s));
+        CTG_CHECK(hipStreamSynchronize(s));
+        if (top >= (1ull << 53)) {
+            set_error("ctg_morphology_rows: a label of 2^53 or more does not fit the float64 id column "
+                      "(ctg_result_copy_moments holds any label)");
+            return CTG_ERR_UNSUPPORTED;
+        }
+    }
+    const uint64_t n = label_end - label_begin;
+    if (n > (1ull << 40)) {
+        set_error("ctg_morphology_rows: label range too large");
+        return CTG_ERR_ARG;
+    }
+    const bool host = mem == CTG_MEM_HOST;
+    const size_t ob = out ? (size_t)n * CTG_MORPH_COLS * 8 : 0, rb = rows ? (size_t)N * CTG_MORPH_COLS * 8 : 0;
+    if (ob == 0 && rb == 0) return CTG_OK;
+    DevBuf<double> own_o, own_r;
+    double *d_o = ob ? out : nullptr, *d_r = rb ? rows : nullptr;
+    if (host && ((ob && !(d_o = own_o.alloc(ob))) || (rb && !(d_r = own_r.alloc(rb)))))
+        return overlap_status(hipErrorOutOfMemory, "ctg_morphology_rows");
+    if (ob) CTG_CHECK(hipMemsetAsync(d_o, 0, ob, s));
+    CTG_CHECK(launch_morph_rows(r, label_begin, label_end, d_o, d_r, s));
+    if (host) {
+        if (ob) CTG_CHECK(hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, s));
+        if (rb) CTG_CHECK(hipMemcpyAsync(rows, d_r, rb, hipMemcpyDeviceToHost, s));
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
+
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global, const uint64_t* query, int64_t n_query,
                      int64_t* out_ids, int mem, void* stream) {
     DevLock dev_lock;
@@ -1511,6 +1677,13 @@ int ctg_result_copy_counts(const ctg_result* r, uint64_t* dst, int mem) {
     }
     return copy_out(dst, r->counts, (size_t)r->n_edges * 8, mem);
 }
+int ctg_result_copy_moments(const ctg_result* r, uint64_t* dst, int mem) {
+    if (!r || !r->moments) {
+        set_error("result has no moments (not a morphology result)");
+        return CTG_ERR_ARG;
+    }
+    return copy_out(dst, r->moments, (size_t)r->n_nodes * MORPH_WORDS * 8, mem);
+}
 const uint64_t* ctg_result_device_edges(const ctg_result* r) { return r ? r->edges : nullptr; }
 const double* ctg_result_device_features(const ctg_result* r) { return r ? r->features : nullptr; }
 int ctg_result_info(const ctg_result* r, int64_t* n_records, int64_t* n_direct) {
@@ -1535,6 +1708,7 @@ void ctg_free(ctg_result* r) {
     dev_free(r->stat_sums);
     dev_free(r->counts);
     dev_free(r->row_off);
+    dev_free(r->moments);
     if (r->device >= 0 && r->device != d) hipSetDevice(d);
     delete r;
 }

@@ -117,6 +117,22 @@ __host__ __device__ inline uint32_t hash_key(uint64_t k) {
     return (uint32_t)k;
 }
 
+// 64-bit wave shuffles as two 32-bit ones (device code only)
+#ifdef __HIPCC__
+__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v) {
+    const uint32_t lo = __shfl_up((uint32_t)v, 1, WAVE), hi = __shfl_up((uint32_t)(v >> 32), 1, WAVE);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int o) {
+    const uint32_t lo = __shfl_down((uint32_t)v, o, WAVE), hi = __shfl_down((uint32_t)(v >> 32), o, WAVE);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t bcast0_u64(uint64_t v) {
+    const uint32_t lo = __shfl((uint32_t)v, 0, WAVE), hi = __shfl((uint32_t)(v >> 32), 0, WAVE);
+    return ((uint64_t)hi << 32) | lo;
+}
+#endif
+
 // Blocked Bloom filter of RAG edge keys (the long-range affinity prefilter),
 // blocked by OWNER label: an edge (u, v) is stored twice, as u -> v in the
 // 64-B block of u and as v -> u in the block of v; a probe from a voxel of
@@ -453,6 +469,7 @@ hipError_t bounds_take_sort(unsigned long long* h);
 hipError_t bounds_take_mgpu(unsigned long long* h);
 hipError_t bounds_take_scan(unsigned long long* h);
 hipError_t bounds_take_overlap(unsigned long long* h);
+hipError_t bounds_take_morph(unsigned long long* h);
 #endif
 
 }  // namespace ctg
@@ -475,6 +492,9 @@ struct ctg_result {
     // the sorted (a, b) pairs, nodes the distinct a
     uint64_t* counts = nullptr;     // device (E,) voxels of each pair, or null
     int64_t* row_off = nullptr;     // device (N+1,) rows [row_off[j], row_off[j+1]) belong to nodes[j], or null
+    // segment morphology (ctg_morphology, ctg_merge_morphology): nodes holds the
+    // distinct labels, ascending
+    uint64_t* moments = nullptr;    // device (N, MORPH_WORDS): n, sum z y x, min z y x, max z y x (inclusive), or null
     int64_t n_records = 0;
     int64_t n_direct = 0;
     // affinity partial table (CTG_NO_ADJ_FILTER): a key is an edge only where
@@ -534,12 +554,32 @@ hipError_t overlap_tables(Workspace& w, const void* A, int abits, const void* B,
 // n > 0 (key = a << 32 | b, count) records -> r: equal keys add their counts
 hipError_t overlap_reduce(Workspace& w, const uint64_t* key, const uint64_t* cnt, int64_t n, hipStream_t s,
                           ctg_result* r);
+hipError_t launch_overlap_heads(int64_t n, const uint64_t* key, uint64_t* flags, hipStream_t s);
 hipError_t launch_overlap_pack(int64_t n, const uint64_t* pairs, uint64_t* key, hipStream_t s);
 hipError_t launch_overlap_map_back(int64_t E, uint64_t* pairs, const uint64_t* Ua, int64_t na, const uint64_t* Ub,
                                    int64_t nb, hipStream_t s);
 hipError_t launch_overlap_find(const uint64_t* U, int64_t n, uint64_t x, uint32_t* out, hipStream_t s);
 hipError_t launch_overlap_argmax(const ctg_result* r, uint64_t lb, uint64_t le, uint64_t* out_l, uint64_t* out_c,
                                  hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// segment morphology (ctg_morph.hip).  Call-sized pool buffers only, as the
+// label overlaps.
+// ---------------------------------------------------------------------------
+constexpr int MORPH_WORDS = 10;   // u64 words of a moments row: n, sum z y x, min z y x, max z y x
+// The moments of the box [b, e) of a label volume (bits: 32 or 64) into r
+// (nodes, moments), coordinates = array index + origin.  *overflow: a label
+// >= 2^32 was met -- r is untouched and the caller relabels densely.
+hipError_t morph_tables(Workspace& w, const void* A, int bits, const int64_t* shape, const int64_t* b,
+                        const int64_t* e, const int64_t* origin, hipStream_t s, ctg_result* r, unsigned* overflow);
+// n > 0 rows of CTG_MORPH_COLS float64 (device), in any order -> r: rows of one
+// id combine.  *bad: some id was not an integer in [0, 2^53), or a size / box
+// entry was negative or not finite (r is untouched).
+hipError_t morph_merge(Workspace& w, const double* rows, int64_t n, hipStream_t s, ctg_result* r, int* bad);
+// moments -> float64 rows: compact into rows (N x CTG_MORPH_COLS) and / or
+// scattered into the zeroed dense table out over the labels [lb, le); either
+// may be null
+hipError_t launch_morph_rows(const ctg_result* r, uint64_t lb, uint64_t le, double* out, double* rows, hipStream_t s);
 
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,

@@ -31,19 +31,6 @@ constexpr int OV_CAP = 2048;      // LDS table entries (u64 key + u32 count: 24 
 constexpr int OV_PROBES = 32;     // linear probes before a head gives up on the table
 static_assert((OV_CAP & (OV_CAP - 1)) == 0 && OV_CAP % OV_THREADS == 0, "table capacity");
 
-__device__ __forceinline__ uint64_t shfl_up_u64(uint64_t v) {
-    const uint32_t lo = __shfl_up((uint32_t)v, 1, WAVE), hi = __shfl_up((uint32_t)(v >> 32), 1, WAVE);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int o) {
-    const uint32_t lo = __shfl_down((uint32_t)v, o, WAVE), hi = __shfl_down((uint32_t)(v >> 32), o, WAVE);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t bcast0_u64(uint64_t v) {
-    const uint32_t lo = __shfl((uint32_t)v, 0, WAVE), hi = __shfl((uint32_t)(v >> 32), 0, WAVE);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // One workgroup per 64 x TILE_Y x 16 tile of the box.  A wave takes one row at
 // a time: equal consecutive pairs collapse to their head lane (run length from
 // the ballot of heads), and only heads touch the table -- CAS on the key word,
@@ -410,6 +397,11 @@ hipError_t overlap_tables(Workspace& w, const void* A, int abits, const void* B,
         return hipSuccess;
     }
     return hipErrorOutOfMemory;   // (unreachable: the third attempt holds every voxel)
+}
+
+hipError_t launch_overlap_heads(int64_t n, const uint64_t* key, uint64_t* flags, hipStream_t s) {
+    hipLaunchKernelGGL(k_overlap_heads, grid_for(n), dim3(256), 0, s, n, key, flags);
+    return hipGetLastError();
 }
 
 hipError_t launch_overlap_pack(int64_t n, const uint64_t* pairs, uint64_t* key, hipStream_t s) {

@@ -23,6 +23,8 @@ whole integration:
     mergeAndSerializeOverlaps      node_labels/merge_node_labels.py:149-155
     deserializeOverlapChunk        test/node_labels/test_node_labels.py:124,144;
                                    evaluation/measures.py:122
+    computeAndSerializeMorphology  morphology/block_morphology.py:134
+    mergeAndSerializeMorphology    morphology/merge_morphology.py:130
 
 Errors surface as RuntimeError (``_lib.CtgError``), as pybind11 raises for
 nifty's C++ exceptions, so a failing job never prints ``processed job N`` and
@@ -50,7 +52,9 @@ STATS_SUFFIX = '_stats'
 STATS_WORDS = 4 + rag.WIDE_WORDS
 # the other on-disk layout of this library's own: the overlap chunks of the node
 # labels (varlen uint64: node, n, then n x (label, count) per node, both
-# ascending) -- encode_overlap_chunk / decode_overlap_chunk below
+# ascending) -- encode_overlap_chunk / decode_overlap_chunk below -- and the
+# morphology chunks (varlen float64: the block's (n, 11) rows, row-major, ids
+# ascending) -- encode_morphology_chunk / decode_morphology_chunk
 ORD_POS_INF = 0xFF800000   # order-preserving u32 code of +inf (ctg_internal.h f2ord)
 ORD_NEG_INF = 0x007FFFFF   # ... of -inf
 
@@ -1004,3 +1008,80 @@ def deserializeOverlapChunk(path, key, chunkId=None):  # noqa: N802,N803
     for (a, b), c in zip(pairs.tolist(), counts.tolist()):
         out.setdefault(a, {})[b] = c
     return out, int(pairs[:, 0].max())
+
+
+# ---------------------------------------------------------------------------
+# morphology
+# ---------------------------------------------------------------------------
+
+# A morphology chunk (varlen float64, written by computeAndSerializeMorphology
+# per block, read by mergeAndSerializeMorphology): the block's rows
+#     id, size, com_z, com_y, com_x, min_z, min_y, min_x, max_z, max_y, max_x
+# (block_morphology.py:128-133) one after the other, ids ascending, in the
+# coordinates of the whole volume; max is inclusive.  nifty's own byte layout is
+# not in the reference; both functions that touch these chunks are mirrored
+# here, so the layout is this library's.
+MORPH_COLS = rag.MORPH_COLS
+
+
+def encode_morphology_chunk(rows):
+    """(n, 11) float64 rows -> the chunk words above."""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.size % MORPH_COLS or (rows.ndim == 2 and rows.size and rows.shape[1] != MORPH_COLS):
+        raise ValueError('morphology rows have %d columns, got shape %s' % (MORPH_COLS, rows.shape))
+    return np.ascontiguousarray(rows).reshape(-1)
+
+
+def decode_morphology_chunk(words):
+    """Chunk words -> (n, 11) float64 rows in the chunk's order."""
+    w = np.asarray(words, dtype=np.float64).reshape(-1)
+    if w.size % MORPH_COLS:
+        raise RuntimeError('morphology chunk: truncated row (%d words, not a multiple of %d)' % (w.size, MORPH_COLS))
+    return w.reshape(-1, MORPH_COLS)
+
+
+def computeAndSerializeMorphology(labels, blockBegin, outPath, outKey, chunkId):  # noqa: N802,N803
+    """The morphology rows of ``labels`` (one block of the segmentation, whose
+    first voxel sits at ``blockBegin`` in the volume) as one varlen float64
+    chunk of ``outKey`` at ``chunkId`` (morphology/block_morphology.py:134):
+    per label its id, voxel count, centre of mass, and inclusive bounding box in
+    volume coordinates.  Label 0 gets a row like any other label.  No chunk is
+    written for an empty block."""
+    r = rag.morphology_handle(labels, origin=[int(b) for b in blockBegin])
+    try:
+        if r.n_nodes == 0:
+            return
+        words = encode_morphology_chunk(r.morph_rows())
+    finally:
+        r.free()
+    with _open(outPath) as f:
+        f[outKey].write_chunk([int(c) for c in chunkId], words, True)
+
+
+def mergeAndSerializeMorphology(inputPath, inputKey, outputPath, outputKey, labelBegin, labelEnd,  # noqa: N802,N803
+                                numberOfThreads=1):  # noqa: N803
+    """Merge the block morphology chunks of ``inputKey`` for the labels in
+    [labelBegin, labelEnd) (morphology/merge_morphology.py:130) on the GPU and
+    write ``out[labelBegin:labelEnd, :]``: sizes add, boxes fold, and the
+    centre of mass is the quotient of the added integer coordinate sums.
+    Labels without a row get a row of zeros."""
+    begin, end = int(labelBegin), int(labelEnd)
+    with _open(inputPath, 'r') as f:
+        ds = f[inputKey]
+        chunks = ds.read_chunks(_grid_positions(ds), numberOfThreads)
+    parts = []
+    for c in chunks:
+        if c is None or not len(c):
+            continue
+        rows = decode_morphology_chunk(c)
+        sel = (rows[:, 0] >= begin) & (rows[:, 0] < end)
+        if sel.any():
+            parts.append(rows[sel])
+    rows = np.concatenate(parts) if parts else np.zeros((0, MORPH_COLS), np.float64)
+    r = rag.merge_morphology_handle(rows)
+    try:
+        out = rag.morphology_rows(r, begin, end)
+    finally:
+        r.free()
+    with _open(outputPath) as f:
+        f[outputKey][begin:end, :] = out

@@ -19,6 +19,8 @@ N_FEATURES = L.CTG_N_FEATURES
 NBINS = L.CTG_NBINS
 WIDE_WORDS = L.CTG_WIDE_RECORD_WORDS
 NSLOTS = NBINS + 2   # histogram slots of a wide record: left outliers, the bins, right outliers
+MORPH_COLS = L.CTG_MORPH_COLS   # [id, size, com z y x, min z y x, max z y x]
+MORPH_WORDS = 10               # [n, sum z y x, min z y x, max z y x]
 
 
 def _is_torch(x):
@@ -98,7 +100,33 @@ class Result:
         L.check(L.load().ctg_result_copy_counts(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_counts')
         return out
 
+    def moments(self):
+        """(N,10) uint64 moments of a morphology result."""
+        out = np.empty((self.n_nodes, MORPH_WORDS), dtype=np.uint64)
+        L.check(L.load().ctg_result_copy_moments(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_moments')
+        return out
+
+    def morph_rows(self):
+        """(N,11) float64 rows of a morphology result, ids ascending."""
+        out = np.empty((self.n_nodes, MORPH_COLS), dtype=np.float64)
+        L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, _ptr(out), L.CTG_MEM_HOST, None),
+                'ctg_morphology_rows')
+        return out
+
     # --- device copies (torch)
+    def moments_torch(self):
+        """(N,10) int64 tensor of the uint64 moments of a morphology result."""
+        import torch
+        return self._torch_copy((self.n_nodes, MORPH_WORDS), torch.int64, L.load().ctg_result_copy_moments)
+
+    def morph_rows_torch(self):
+        """(N,11) float64 tensor of the rows of a morphology result."""
+        import torch
+        t = torch.empty((self.n_nodes, MORPH_COLS), dtype=torch.float64, device='cuda:%d' % self.device)
+        L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, ctypes.c_void_p(t.data_ptr()),
+                                             L.CTG_MEM_DEVICE, None), 'ctg_morphology_rows')
+        return t
+
     def counts_torch(self):
         """(E,) int64 tensor of the uint64 counts of an overlaps result."""
         import torch
@@ -665,6 +693,110 @@ def max_overlaps(handle_or_tables, label_begin, label_end):
         if own:
             r.free()
     return out_l, out_c
+
+
+def morphology_handle(labels, begin=None, end=None, origin=None, stream=None):
+    """ctg_morphology -> the device-resident ``Result``: nodes() = the distinct
+    labels of the box [begin, end), ascending; moments() = their (N,10) uint64
+    table [n, sum z y x, min z y x, max z y x] (max inclusive); morph_rows() =
+    the float64 rows [id, size, com z y x, min z y x, max z y x].  The
+    coordinate of the voxel at array index p is p + ``origin`` (the block's
+    begin when ``labels`` is one block of a volume).  A numpy array or a CUDA
+    tensor, (Z,Y,X), 32- or 64-bit integers; label 0 is a label like any other."""
+    labels, bits = _label_volume(labels, 'labels')
+    shape = tuple(labels.shape)
+    if len(shape) != 3:
+        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
+    for box in (begin, end, origin):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end / origin must have 3 entries')
+    lib = L.load()
+    dev = L.init_device()
+    on_dev = _is_torch(labels)
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_morphology(_ptr(labels), bits, _shape_arr(shape),
+                            _shape_arr(begin) if begin is not None else None,
+                            _shape_arr(end) if end is not None else None,
+                            _shape_arr(origin) if origin is not None else None,
+                            L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+    L.check(rc, 'ctg_morphology')
+    return Result(h, dev)
+
+
+def _morphology_tables(r):
+    return dict(nodes=r.nodes(), moments=r.moments(), rows=r.morph_rows())
+
+
+def morphology(labels, begin=None, end=None, origin=None):
+    """Host convenience of morphology_handle: dict(nodes (N,) uint64, moments
+    (N,10) uint64, rows (N,11) float64, n_records, n_direct).  A label of 2^53
+    or more does not fit the rows' id column: use the handle's nodes() and
+    moments() for such volumes."""
+    r = morphology_handle(labels, begin, end, origin)
+    try:
+        out = _morphology_tables(r)
+        out['n_records'], out['n_direct'] = r.info()
+    finally:
+        r.free()
+    return out
+
+
+def merge_morphology_handle(rows, stream=None):
+    """ctg_merge_morphology: (n,11) float64 rows of partial tables, in any
+    order -> the table in which the rows of one id are combined (``Result``):
+    sizes add, boxes fold, and the coordinate sums add as integers, so the
+    result equals one morphology call over the whole volume while every row's
+    sum is below 2^51."""
+    on_dev = _is_torch(rows)
+    if on_dev:
+        if not (rows.is_cuda and rows.is_contiguous()) or rows.element_size() != 8 or not rows.is_floating_point():
+            raise ValueError('rows must be a contiguous float64 CUDA tensor')
+        size = int(rows.numel())
+    else:
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
+        size = rows.size
+    if size % MORPH_COLS or (size and rows.ndim == 2 and rows.shape[1] != MORPH_COLS):
+        raise ValueError('morphology rows have %d columns, got %s' % (MORPH_COLS, tuple(rows.shape)))
+    lib = L.load()
+    dev = L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_merge_morphology(_ptr(rows), size // MORPH_COLS, L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
+                                  stream, ctypes.byref(h))
+    L.check(rc, 'ctg_merge_morphology')
+    return Result(h, dev)
+
+
+def merge_morphology(rows):
+    """Host convenience of merge_morphology_handle: dict(nodes, moments, rows)."""
+    r = merge_morphology_handle(rows)
+    try:
+        return _morphology_tables(r)
+    finally:
+        r.free()
+
+
+def morphology_rows(handle_or_tables, label_begin, label_end):
+    """The dense (label_end - label_begin, 11) float64 table of the labels in
+    [label_begin, label_end): the row of label a at a - label_begin, zeros for
+    absent labels.  ``handle_or_tables``: a ``Result`` of morphology_handle /
+    merge_morphology_handle, or a dict with 'rows' (merged first)."""
+    lb, le = int(label_begin), int(label_end)
+    if lb < 0 or le < lb:
+        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
+    own = not isinstance(handle_or_tables, Result)
+    r = merge_morphology_handle(handle_or_tables['rows']) if own else handle_or_tables
+    out = np.zeros((le - lb, MORPH_COLS), dtype=np.float64)
+    try:
+        L.check(L.load().ctg_morphology_rows(r.handle, lb, le, _ptr(out), None, L.CTG_MEM_HOST, None),
+                'ctg_morphology_rows')
+    finally:
+        if own:
+            r.free()
+    return out
 
 
 def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_offset=0, noise_amp=0.1,

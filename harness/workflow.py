@@ -283,6 +283,59 @@ def node_label_workflow(ws_path, ws_key, input_path, input_key, output_path, out
     return timer
 
 
+def _block_morphology_job(input_path, input_key, output_path, output_key, block_shape, blocks):
+    """block_morphology.py:111-137 (_morphology_for_block)."""
+    with ndist._open(input_path, 'r') as f:
+        ds_in = f[input_key]
+        blk = blocking([0, 0, 0], list(ds_in.shape), list(block_shape))
+        for b in blocks:
+            block = blk.getBlock(b)
+            seg = ds_in[tuple(slice(x, y) for x, y in zip(block.begin, block.end))]
+            if seg.sum() == 0:                                    # :120-123 empty segmentation block
+                continue
+            chunk_id = tuple(x // c for x, c in zip(block.begin, block_shape))
+            ndist.computeAndSerializeMorphology(seg, block.begin, output_path, output_key, chunk_id)
+
+
+def _merge_morphology_job(input_path, input_key, output_path, output_key, out_shape, out_chunks, threads_per_job,
+                          blocks):
+    """merge_morphology.py:123-132."""
+    blk = blocking([0], list(out_shape[:1]), list(out_chunks[:1]))
+    for b in blocks:
+        block = blk.getBlock(b)
+        ndist.mergeAndSerializeMorphology(input_path, input_key, output_path, output_key,
+                                          labelBegin=block.begin[0], labelEnd=block.end[0],
+                                          numberOfThreads=threads_per_job)
+
+
+def morphology_workflow(input_path, input_key, output_path, output_key, block_shape, max_id, node_chunk=100000,
+                        prefix='', max_jobs=1, threads_per_job=4, timer=None, mode='threads'):
+    """MorphologyWorkflow (morphology/morphology_workflow.py): BlockMorphology
+    into the varlen float64 dataset ``morphology_<prefix>`` with chunks =
+    ``block_shape`` (block_morphology.py:58-64), then MergeMorphology over label
+    ranges of ``node_chunk`` (merge_morphology.py:48-56; 100000 in the
+    reference) into the (max_id + 1, 11) float64 dataset ``output_key``."""
+    timer = timer or Timer()
+    tmp_key = 'morphology_%s' % prefix
+    with ndist._open(input_path, 'r') as f:
+        shape = list(f[input_key].shape)
+    block_list = blocks_in_volume(shape, block_shape)
+    with timer.stage('block_morphology'):
+        with ndist._open(output_path) as f:                     # block_morphology.py:60-64
+            f.require_dataset(tmp_key, shape=shape, dtype='float64', chunks=tuple(block_shape), compression='gzip')
+        job = functools.partial(_block_morphology_job, input_path, input_key, output_path, tmp_key, list(block_shape))
+        _run_jobs(job, _jobs(block_list, max_jobs), mode)
+    with timer.stage('merge_morphology'):
+        n_labels = int(max_id) + 1                                # merge_morphology.py:48-50
+        out_shape, out_chunks = (n_labels, 11), (min(n_labels, int(node_chunk)), 11)
+        with ndist._open(output_path) as f:                     # :53-56
+            f.require_dataset(output_key, shape=out_shape, chunks=out_chunks, compression='gzip', dtype='float64')
+        job = functools.partial(_merge_morphology_job, output_path, tmp_key, output_path, output_key, out_shape,
+                                out_chunks, threads_per_job)
+        _run_jobs(job, _jobs(blocks_in_volume(out_shape[:1], out_chunks[:1]), max_jobs), mode)
+    return timer
+
+
 def _normalize(x):
     """vu.normalize (utils/volume_utils.py:98-105): float32, min to 0, max to 1."""
     x = np.asarray(x, dtype=np.float32).copy()

@@ -29,6 +29,10 @@
  *                                        node_labels/block_node_labels.py:161
  *   ctg_merge_overlaps, ctg_max_overlaps <- ndist.mergeAndSerializeOverlaps
  *                                        node_labels/merge_node_labels.py:149
+ *   ctg_morphology                    <- ndist.computeAndSerializeMorphology
+ *                                        morphology/block_morphology.py:134
+ *   ctg_merge_morphology, ctg_morphology_rows <- ndist.mergeAndSerializeMorphology
+ *                                        morphology/merge_morphology.py:130
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -278,6 +282,58 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
 int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_end, uint64_t* out_labels,
                      uint64_t* out_counts, int mem, void* stream);
 
+/*
+ * Segment morphology (MorphologyWorkflow): per label of the box [begin, end)
+ * (NULL = 0 / shape) of a label volume the voxel count, the integer coordinate
+ * sums and the bounding box.  The coordinate of the voxel at array index p is
+ * p + origin (NULL = 0; the block's begin when `labels` is one block of a
+ * volume).  Replaces the array work of ndist.computeAndSerializeMorphology
+ * (morphology/block_morphology.py:134; its N5 chunk is written by
+ * cluster_tools_amd/ndist.py).
+ *   labels   uint64 (label_bits = 64) or uint32 (32), C-order (Z,Y,X) of `shape`;
+ *            any label value, 2^32 and above included; label 0 is a label like
+ *            any other
+ * Result: nodes = the distinct labels, ascending; ctg_result_copy_moments = an
+ * (N,10) uint64 table [n, sum z, sum y, sum x, min z, min y, min x, max z,
+ * max y, max x] (max inclusive); ctg_morphology_rows = the float64 rows
+ *   [id, size, com_z, com_y, com_x, min_z, min_y, min_x, max_z, max_y, max_x]
+ * of block_morphology.py:128-133, com = (double)sum / (double)n.  An empty box
+ * gives an empty result; a box outside the array is CTG_ERR_ARG; a box of 2^32
+ * voxels or more is CTG_ERR_UNSUPPORTED; origin + end must stay below 2^31 on
+ * every axis (CTG_ERR_ARG), so no sum reaches 2^63.  ctg_result_info: the
+ * records the scan wrote, and how many of them bypassed the workgroup tables.
+ * Like the overlaps calls these keep their records in buffers of their own: a
+ * CTG_DEFER_STATS handle of the same device stays valid across them.
+ */
+#define CTG_MORPH_COLS 11
+int ctg_morphology(const void* labels, int label_bits, const int64_t* shape,
+                   const int64_t* begin, const int64_t* end, const int64_t* origin,
+                   int mem, void* stream, ctg_result** out);
+
+/* Combine partial morphology tables -- n rows of the 11-column float64 form, in
+ * any order -- into one result of the form above: per id the sizes add, the
+ * boxes fold, and the coordinate sums add as integers, each row's sum recovered
+ * as rint(com * size).  The recovery is exact while a row's sum is below 2^51
+ * (a block of 2^32 voxels at coordinates up to 2^19), and the merged table then
+ * equals one ctg_morphology call over the whole volume bit for bit; past that
+ * bound the sums are rounded.  Rows of size 0 (the zero rows of absent labels)
+ * add nothing.  An id that is not an integer in [0, 2^53), or a negative or
+ * non-finite entry, is CTG_ERR_ARG.  The array work of
+ * ndist.mergeAndSerializeMorphology (morphology/merge_morphology.py:130). */
+int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, ctg_result** out);
+
+/* the (N,10) uint64 moments of a morphology result */
+int ctg_result_copy_moments(const ctg_result* r, uint64_t* dst, int mem);
+
+/* The float64 rows of a morphology result: `rows` (may be NULL) receives the
+ * (N,11) rows of its labels in ascending order; `out` (may be NULL) is a dense
+ * (label_end - label_begin, 11) table that receives the row of every label in
+ * [label_begin, label_end) at label - label_begin and zeros for absent labels
+ * (what an unwritten chunk of the output dataset reads as).  A table with a
+ * label of 2^53 or more is CTG_ERR_UNSUPPORTED: the id column cannot hold it. */
+int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end,
+                        double* out, double* rows, int mem, void* stream);
+
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
                      const uint64_t* query, int64_t n_query, int64_t* out_ids,
@@ -369,7 +425,8 @@ int ctg_trim(void);
 /* profiling: per-phase device milliseconds of the last ctg_rag_features call
  * (HIP events on the call's stream): [0] face scan, [1] key pack, [2] sort,
  * [3] segment, [4] reduce+finalize, [5] nodes, [6] total; of a ctg_label_overlaps
- * call: [0] scan, [2] sort, [3] run heads + prefix sums, [4] run sums, [6] total */
+ * or ctg_morphology call: [0] scan, [2] sort, [3] run heads + prefix sums,
+ * [4] run sums / folds, [6] total */
 int ctg_set_profiling(int on);
 int ctg_last_timings(double* ms, int n);
 
@@ -378,7 +435,7 @@ int ctg_last_timings(double* ms, int n);
  * run tables, permutations, node bitmaps, exchange rows) that reached past
  * the current call's count since the last query.  Returns 0 (none) or 1 with
  * out[0] = source file (1 ctg_api, 2 ctg_scan, 3 ctg_sort, 4 ctg_reduce,
- * 5 ctg_mgpu, 6 ctg_overlap), out[1] = line, out[2] = index, out[3] = bound; clears them.
+ * 5 ctg_mgpu, 6 ctg_overlap, 7 ctg_morph), out[1] = line, out[2] = index, out[3] = bound; clears them.
  * Product builds: CTG_ERR_UNSUPPORTED. */
 int ctg_diag_bounds(uint64_t* out);
 
