@@ -80,6 +80,28 @@ struct DevInput {
     operator const T*() const { return p; }
 };
 
+// A dense output table that may live on the host: kernels write d, which is
+// the caller's pointer (mem device) or a device buffer of this object's, copied
+// out by copy_back().  An absent table (null, or no bytes) has d null.
+template <class T>
+struct DenseOut {
+    DevBuf<T> own;
+    T* d = nullptr;
+    T* dst = nullptr;
+    size_t bytes = 0;
+    hipError_t open(T* out, size_t nbytes, int mem, bool zero, hipStream_t s) {
+        if (!out || nbytes == 0) return hipSuccess;
+        dst = out;
+        bytes = nbytes;
+        d = mem == CTG_MEM_HOST ? own.alloc(bytes) : out;
+        if (!d) return hipErrorOutOfMemory;
+        return zero ? hipMemsetAsync(d, 0, bytes, s) : hipSuccess;
+    }
+    hipError_t copy_back(hipStream_t s) {
+        return own ? hipMemcpyAsync(dst, d, bytes, hipMemcpyDeviceToHost, s) : hipSuccess;
+    }
+};
+
 // n u64 values -> their sorted distinct values in out (room for n), the count
 // in *count_dev (device); key bits [0, end_bit) are compared
 static hipError_t sort_unique_u64(Workspace& w, const uint64_t* in, int64_t n, uint64_t* out, uint32_t* count_dev,
@@ -1235,20 +1257,78 @@ int ctg_unique_pairs(const uint64_t* pairs, int64_t n, int mem, void* stream, ct
 }
 
 // ---------------------------------------------------------------------------
-// label overlaps (kernels and back half: ctg_overlap.hip)
+// label overlaps and segment morphology (kernels and back halves:
+// ctg_overlap.hip, ctg_morph.hip).  What the entry points share comes first.
 // ---------------------------------------------------------------------------
-static int overlap_status(hipError_t e, const char* who) {
+static int hip_status(hipError_t e, const char* who) {
     if (e == hipSuccess) return CTG_OK;
     set_error(std::string(who) + ": " + hipGetErrorString(e));
     return e == hipErrorOutOfMemory ? CTG_ERR_NOMEM : CTG_ERR_HIP;
 }
 
-// an overlaps result without rows: the placeholders of empty_result plus the counts'
+// the box [b, e) of a call: begin / end default to the whole array, the box
+// lies inside it and holds *nb < 2^32 - 1 voxels
+static int box_of(const char* who, const int64_t* shape, const int64_t* begin, const int64_t* end, int64_t* b,
+                  int64_t* e, int64_t* nb) {
+    for (int k = 0; k < 3; ++k) {
+        b[k] = begin ? begin[k] : 0;
+        e[k] = end ? end[k] : shape[k];
+        if (shape[k] < 0 || b[k] < 0 || e[k] > shape[k] || b[k] > e[k]) {
+            set_error(std::string(who) + ": box outside the array");
+            return CTG_ERR_ARG;
+        }
+    }
+    *nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
+    if (*nb >= 0xFFFFFFFFll) {   // (a record per voxel at most; the run table numbers records in 32 bits)
+        set_error(std::string(who) + ": boxes of 2^32 voxels or more are not supported");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    return CTG_OK;
+}
+
+// an overlaps / a morphology result without rows: the placeholders of
+// empty_result plus the counts' / the moments'
 static ResultPtr empty_overlaps(int device) {
     ResultPtr r = empty_result(device);
     r->counts = (uint64_t*)dev_alloc(8);
     return r;
 }
+static ResultPtr empty_morphology(int device) {
+    ResultPtr r = empty_result(device);
+    r->moments = (uint64_t*)dev_alloc(8);
+    return r;
+}
+
+// A table call on the current device: its initialised workspace, its stream
+// and its result, which starts as `empty` makes it.  begin(), the work, then
+// end() -- or, with nothing to do, hand r out as it is.
+struct TableCall {
+    Workspace* wp = nullptr;
+    hipStream_t s = nullptr;
+    ResultPtr r;
+    int begin(void* stream, ResultPtr (*empty)(int)) {
+        const int dev = current_device();
+        Workspace& w = ws(dev);
+        CTG_CHECK(ws_init(w));
+        wp = &w;
+        s = (hipStream_t)stream;
+        r = empty(dev);
+        return CTG_OK;
+    }
+    // a scan's epilogue: the phase times of a profiled call (timed: it ran the phases), the workspace's record counts
+    int end(bool timed, ctg_result** out) {
+        Workspace& w = *wp;
+        if (w.profiling && timed) {
+            const int rc = read_phase_times(w, s);
+            if (rc != CTG_OK) return rc;
+        }
+        CTG_CHECK(hipStreamSynchronize(s));
+        w.last_records = r->n_records;
+        w.last_direct = r->n_direct;
+        *out = r.release();
+        return CTG_OK;
+    }
+};
 
 // A label volume of ctg_label_overlaps / ctg_morphology whose labels reach
 // 2^32: the box's sorted unique labels U and the whole array as 32-bit ranks in
@@ -1257,7 +1337,7 @@ struct DenseSide {
     ResultPtr U;
     DevBuf<uint32_t> ids;
     int build(const void* vol, const int64_t* shape, const int64_t* b, const int64_t* e, void* stream,
-              const char* who = "ctg_label_overlaps") {
+              const char* who) {
         int rc = nested(U, [&](ctg_result** u) {
             return ctg_unique_labels((const uint64_t*)vol, shape, b, e, CTG_MEM_DEVICE, stream, u);
         });
@@ -1279,6 +1359,7 @@ struct DenseSide {
 int ctg_label_overlaps(const void* labels, int label_bits, const void* values, int value_bits, const int64_t* shape,
                        const int64_t* begin, const int64_t* end, int with_ignore, uint64_t ignore_label, int mem,
                        void* stream, ctg_result** out) {
+    const char* who = "ctg_label_overlaps";
     DevLock dev_lock;
     if (!labels || !values || !shape || !out) {
         set_error("ctg_label_overlaps: null argument");
@@ -1289,78 +1370,64 @@ int ctg_label_overlaps(const void* labels, int label_bits, const void* values, i
         set_error("ctg_label_overlaps: label_bits and value_bits must be 32 or 64");
         return CTG_ERR_ARG;
     }
-    int64_t b[3], e[3];
-    for (int k = 0; k < 3; ++k) {
-        b[k] = begin ? begin[k] : 0;
-        e[k] = end ? end[k] : shape[k];
-        if (shape[k] < 0 || b[k] < 0 || e[k] > shape[k] || b[k] > e[k]) {
-            set_error("ctg_label_overlaps: box outside the array");
-            return CTG_ERR_ARG;
-        }
-    }
-    const int64_t nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
-    if (nb >= 0xFFFFFFFFll) {   // (a record per voxel at most; the run table numbers records in 32 bits)
-        set_error("ctg_label_overlaps: boxes of 2^32 voxels or more are not supported");
-        return CTG_ERR_UNSUPPORTED;
-    }
-    const int dev = current_device();
-    Workspace& w = ws(dev);
-    CTG_CHECK(ws_init(w));
-    hipStream_t s = (hipStream_t)stream;
-    ResultPtr r = empty_overlaps(dev);
+    int64_t b[3], e[3], nb = 0;
+    int rc = box_of(who, shape, begin, end, b, e, &nb);
+    if (rc) return rc;
+    TableCall c;
+    if ((rc = c.begin(stream, empty_overlaps)) != CTG_OK) return rc;
     if (nb == 0) {
-        *out = r.release();
+        *out = c.r.release();
         return CTG_OK;
     }
+    Workspace& w = *c.wp;
+    hipStream_t s = c.s;
+    ctg_result* r = c.r.get();
     const int64_t V = shape[0] * shape[1] * shape[2];
     const void *dl = nullptr, *dv = nullptr;
-    int rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
+    rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
     if (!rc) rc = stage_in(w.stage[1], values, (size_t)V * (value_bits / 8), mem, s, &dv);
     if (rc) return rc;
     unsigned over = 0;
-    if ((rc = overlap_status(overlap_tables(w, dl, label_bits, dv, value_bits, shape, b, e, with_ignore, ignore_label,
-                                            s, r.get(), &over),
-                             "ctg_label_overlaps")) != CTG_OK)
+    if ((rc = hip_status(overlap_tables(w, dl, label_bits, dv, value_bits, shape, b, e, with_ignore, ignore_label, s,
+                                        r, &over),
+                         who)) != CTG_OK)
         return rc;
     if (over) {
-        // labels >= 2^32 do not fit the 32 + 32 bit keys: the side(s) that hold
-        // them run again as dense ids, and the sorted tables map back
+        // labels >= 2^32 do not fit the 32 + 32 bit keys.  1: the side(s) that
+        // hold them become monotone dense ids
         DenseSide da, db;
-        if ((over & 1u) && (rc = da.build(dl, shape, b, e, stream)) != CTG_OK) return rc;
-        if ((over & 2u) && (rc = db.build(dv, shape, b, e, stream)) != CTG_OK) return rc;
-        if ((over & 2u) && with_ignore) {   // the ignore label's dense id (absent from the box: nothing to skip)
+        if ((over & 1u) && (rc = da.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
+        if ((over & 2u) && (rc = db.build(dv, shape, b, e, stream, who)) != CTG_OK) return rc;
+        // 2: so does the ignore label (absent from the box: nothing to skip)
+        if ((over & 2u) && with_ignore) {
             DevBuf<uint32_t> rank(4);
             uint32_t h = 0;
-            if (!rank) return overlap_status(hipErrorOutOfMemory, "ctg_label_overlaps");
+            if (!rank) return hip_status(hipErrorOutOfMemory, who);
             CTG_CHECK(launch_overlap_find(db.U->nodes, db.U->n_nodes, ignore_label, rank, s));
             CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
             CTG_CHECK(hipStreamSynchronize(s));
             with_ignore = h != 0xFFFFFFFFu;
             ignore_label = h;
         }
+        // 3: the scan runs again on the ids
         unsigned again = 0;
-        if ((rc = overlap_status(overlap_tables(w, da.U ? (const void*)da.ids.p : dl, da.U ? 32 : label_bits,
-                                                db.U ? (const void*)db.ids.p : dv, db.U ? 32 : value_bits, shape, b,
-                                                e, with_ignore, ignore_label, s, r.get(), &again),
-                                 "ctg_label_overlaps")) != CTG_OK)
+        if ((rc = hip_status(overlap_tables(w, da.U ? (const void*)da.ids.p : dl, da.U ? 32 : label_bits,
+                                            db.U ? (const void*)db.ids.p : dv, db.U ? 32 : value_bits, shape, b, e,
+                                            with_ignore, ignore_label, s, r, &again),
+                             who)) != CTG_OK)
             return rc;
+        // 4: which cannot overflow
         if (again) {
             set_error("ctg_label_overlaps: dense ids past 2^32");
             return CTG_ERR_UNSUPPORTED;
         }
+        // 5: the sorted tables map back to labels
         CTG_CHECK(launch_overlap_map_back(r->n_edges, r->edges, da.U ? da.U->nodes : nullptr,
                                           da.U ? da.U->n_nodes : 0, db.U ? db.U->nodes : nullptr,
                                           db.U ? db.U->n_nodes : 0, s));
         if (da.U) CTG_CHECK(launch_gather_labels(da.U->nodes, r->nodes, r->n_nodes, s));
     }
-    if (w.profiling && r->n_records > 0) {
-        if ((rc = read_phase_times(w, s)) != CTG_OK) return rc;
-    }
-    CTG_CHECK(hipStreamSynchronize(s));
-    w.last_records = r->n_records;
-    w.last_direct = r->n_direct;
-    *out = r.release();
-    return CTG_OK;
+    return c.end(r->n_records > 0, out);
 }
 
 int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n, int mem, void* stream,
@@ -1375,17 +1442,18 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
         set_error("ctg_merge_overlaps: 2^32 rows or more in one call");
         return CTG_ERR_UNSUPPORTED;
     }
-    const int dev = current_device();
-    Workspace& w = ws(dev);
-    CTG_CHECK(ws_init(w));
-    hipStream_t s = (hipStream_t)stream;
-    ResultPtr r = empty_overlaps(dev);
+    TableCall c;
+    int rc = c.begin(stream, empty_overlaps);
+    if (rc) return rc;
     if (n == 0) {
-        *out = r.release();
+        *out = c.r.release();
         return CTG_OK;
     }
+    Workspace& w = *c.wp;
+    hipStream_t s = c.s;
+    ResultPtr& r = c.r;
     DevInput<uint64_t> dp, dc;
-    int rc = dp.put(pairs, (size_t)n * 16, mem, s, "ctg_merge_overlaps");
+    rc = dp.put(pairs, (size_t)n * 16, mem, s, "ctg_merge_overlaps");
     if (!rc) rc = dc.put(counts, (size_t)n * 8, mem, s, "ctg_merge_overlaps");
     if (rc) return rc;
     CTG_CHECK(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
@@ -1403,9 +1471,9 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
         src = dense.dense;
     }
     DevBuf<uint64_t> key((size_t)n * 8);
-    if (!key) return overlap_status(hipErrorOutOfMemory, "ctg_merge_overlaps");
+    if (!key) return hip_status(hipErrorOutOfMemory, "ctg_merge_overlaps");
     CTG_CHECK(launch_overlap_pack(n, src, key, s));
-    if ((rc = overlap_status(overlap_reduce(w, key, dc, n, s, r.get()), "ctg_merge_overlaps")) != CTG_OK) return rc;
+    if ((rc = hip_status(overlap_reduce(w, key, dc, n, s, r.get()), "ctg_merge_overlaps")) != CTG_OK) return rc;
     CTG_CHECK(dense.map_back(r.get(), s));
     CTG_CHECK(hipStreamSynchronize(s));
     r->n_records = n;
@@ -1427,34 +1495,20 @@ int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_e
     const uint64_t n = label_end - label_begin;
     if (n == 0) return CTG_OK;
     hipStream_t s = (hipStream_t)stream;
-    const bool host = mem == CTG_MEM_HOST;
-    DevBuf<uint64_t> own_l, own_c;
-    uint64_t *dl = out_labels, *dc = out_counts;
-    if (host && (!(dl = own_l.alloc(n * 8)) || (out_counts && !(dc = own_c.alloc(n * 8)))))
-        return overlap_status(hipErrorOutOfMemory, "ctg_max_overlaps");
-    CTG_CHECK(hipMemsetAsync(dl, 0, n * 8, s));
-    if (dc) CTG_CHECK(hipMemsetAsync(dc, 0, n * 8, s));
-    CTG_CHECK(launch_overlap_argmax(r, label_begin, label_end, dl, dc, s));
-    if (host) {
-        CTG_CHECK(hipMemcpyAsync(out_labels, dl, n * 8, hipMemcpyDeviceToHost, s));
-        if (dc) CTG_CHECK(hipMemcpyAsync(out_counts, dc, n * 8, hipMemcpyDeviceToHost, s));
-    }
+    DenseOut<uint64_t> ol, oc;
+    int rc = hip_status(ol.open(out_labels, n * 8, mem, true, s), "ctg_max_overlaps");
+    if (!rc) rc = hip_status(oc.open(out_counts, n * 8, mem, true, s), "ctg_max_overlaps");
+    if (rc) return rc;
+    CTG_CHECK(launch_overlap_argmax(r, label_begin, label_end, ol.d, oc.d, s));
+    CTG_CHECK(ol.copy_back(s));
+    CTG_CHECK(oc.copy_back(s));
     CTG_CHECK(hipStreamSynchronize(s));
     return CTG_OK;
 }
 
-// ---------------------------------------------------------------------------
-// segment morphology (kernels and back half: ctg_morph.hip)
-// ---------------------------------------------------------------------------
-// a morphology result without rows: the placeholders of empty_result plus the moments'
-static ResultPtr empty_morphology(int device) {
-    ResultPtr r = empty_result(device);
-    r->moments = (uint64_t*)dev_alloc(8);
-    return r;
-}
-
 int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, const int64_t* begin, const int64_t* end,
                    const int64_t* origin, int mem, void* stream, ctg_result** out) {
+    const char* who = "ctg_morphology";
     DevLock dev_lock;
     if (!labels || !shape || !out) {
         set_error("ctg_morphology: null argument");
@@ -1465,66 +1519,48 @@ int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, con
         set_error("ctg_morphology: label_bits must be 32 or 64");
         return CTG_ERR_ARG;
     }
-    int64_t b[3], e[3], o[3];
+    int64_t b[3], e[3], o[3], nb = 0;
+    int rc = box_of(who, shape, begin, end, b, e, &nb);
+    if (rc) return rc;
     for (int k = 0; k < 3; ++k) {
-        b[k] = begin ? begin[k] : 0;
-        e[k] = end ? end[k] : shape[k];
         o[k] = origin ? origin[k] : 0;
-        if (shape[k] < 0 || b[k] < 0 || e[k] > shape[k] || b[k] > e[k]) {
-            set_error("ctg_morphology: box outside the array");
-            return CTG_ERR_ARG;
-        }
         // a coordinate below 2^31 and fewer than 2^32 voxels: no sum reaches 2^63
         if (o[k] < 0 || o[k] >= (1ll << 31) || o[k] + e[k] >= (1ll << 31)) {
             set_error("ctg_morphology: origin + end must stay below 2^31 on every axis (origin >= 0)");
             return CTG_ERR_ARG;
         }
     }
-    const int64_t nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
-    if (nb >= 0xFFFFFFFFll) {   // (a record per voxel at most; the run table numbers records in 32 bits)
-        set_error("ctg_morphology: boxes of 2^32 voxels or more are not supported");
-        return CTG_ERR_UNSUPPORTED;
-    }
-    const int dev = current_device();
-    Workspace& w = ws(dev);
-    CTG_CHECK(ws_init(w));
-    hipStream_t s = (hipStream_t)stream;
-    ResultPtr r = empty_morphology(dev);
+    TableCall c;
+    if ((rc = c.begin(stream, empty_morphology)) != CTG_OK) return rc;
     if (nb == 0) {
-        *out = r.release();
+        *out = c.r.release();
         return CTG_OK;
     }
+    Workspace& w = *c.wp;
+    hipStream_t s = c.s;
+    ctg_result* r = c.r.get();
     const int64_t V = shape[0] * shape[1] * shape[2];
     const void* dl = nullptr;
-    int rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
-    if (rc) return rc;
+    if ((rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl)) != CTG_OK) return rc;
     unsigned over = 0;
-    if ((rc = overlap_status(morph_tables(w, dl, label_bits, shape, b, e, o, s, r.get(), &over), "ctg_morphology")) !=
-        CTG_OK)
-        return rc;
+    if ((rc = hip_status(morph_tables(w, dl, label_bits, shape, b, e, o, s, r, &over), who)) != CTG_OK) return rc;
     if (over) {
-        // labels >= 2^32 do not fit the table's 32-bit keys: the scan runs again
-        // on the monotone dense ids, and the sorted labels map back
+        // labels >= 2^32 do not fit the table's 32-bit keys.  1: the labels
+        // become monotone dense ids (2: no ignore label here)
         DenseSide d;
-        if ((rc = d.build(dl, shape, b, e, stream, "ctg_morphology")) != CTG_OK) return rc;
+        if ((rc = d.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
+        // 3: the scan runs again on the ids
         unsigned again = 0;
-        if ((rc = overlap_status(morph_tables(w, d.ids.p, 32, shape, b, e, o, s, r.get(), &again),
-                                 "ctg_morphology")) != CTG_OK)
-            return rc;
+        if ((rc = hip_status(morph_tables(w, d.ids.p, 32, shape, b, e, o, s, r, &again), who)) != CTG_OK) return rc;
+        // 4: which cannot overflow
         if (again) {
             set_error("ctg_morphology: dense ids past 2^32");
             return CTG_ERR_UNSUPPORTED;
         }
+        // 5: the sorted ids map back to labels
         CTG_CHECK(launch_gather_labels(d.U->nodes, r->nodes, r->n_nodes, s));
     }
-    if (w.profiling) {
-        if ((rc = read_phase_times(w, s)) != CTG_OK) return rc;
-    }
-    CTG_CHECK(hipStreamSynchronize(s));
-    w.last_records = r->n_records;
-    w.last_direct = r->n_direct;
-    *out = r.release();
-    return CTG_OK;
+    return c.end(true, out);
 }
 
 int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
@@ -1538,27 +1574,25 @@ int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, c
         set_error("ctg_merge_morphology: 2^32 rows or more in one call");
         return CTG_ERR_UNSUPPORTED;
     }
-    const int dev = current_device();
-    Workspace& w = ws(dev);
-    CTG_CHECK(ws_init(w));
-    hipStream_t s = (hipStream_t)stream;
-    ResultPtr r = empty_morphology(dev);
+    TableCall c;
+    int rc = c.begin(stream, empty_morphology);
+    if (rc) return rc;
     if (n == 0) {
-        *out = r.release();
+        *out = c.r.release();
         return CTG_OK;
     }
+    hipStream_t s = c.s;
     DevInput<double> dr;
-    int rc = dr.put(rows, (size_t)n * CTG_MORPH_COLS * 8, mem, s, "ctg_merge_morphology");
-    if (rc) return rc;
+    if ((rc = dr.put(rows, (size_t)n * CTG_MORPH_COLS * 8, mem, s, "ctg_merge_morphology")) != CTG_OK) return rc;
     int bad = 0;
-    if ((rc = overlap_status(morph_merge(w, dr, n, s, r.get(), &bad), "ctg_merge_morphology")) != CTG_OK) return rc;
+    if ((rc = hip_status(morph_merge(*c.wp, dr, n, s, c.r.get(), &bad), "ctg_merge_morphology")) != CTG_OK) return rc;
     if (bad) {
         set_error("ctg_merge_morphology: a row's id is not an integer in [0, 2^53), or its size, centre or box is "
                   "negative or not finite");
         return CTG_ERR_ARG;
     }
     CTG_CHECK(hipStreamSynchronize(s));
-    *out = r.release();
+    *out = c.r.release();
     return CTG_OK;
 }
 
@@ -1590,19 +1624,14 @@ int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t labe
         set_error("ctg_morphology_rows: label range too large");
         return CTG_ERR_ARG;
     }
-    const bool host = mem == CTG_MEM_HOST;
-    const size_t ob = out ? (size_t)n * CTG_MORPH_COLS * 8 : 0, rb = rows ? (size_t)N * CTG_MORPH_COLS * 8 : 0;
-    if (ob == 0 && rb == 0) return CTG_OK;
-    DevBuf<double> own_o, own_r;
-    double *d_o = ob ? out : nullptr, *d_r = rb ? rows : nullptr;
-    if (host && ((ob && !(d_o = own_o.alloc(ob))) || (rb && !(d_r = own_r.alloc(rb)))))
-        return overlap_status(hipErrorOutOfMemory, "ctg_morphology_rows");
-    if (ob) CTG_CHECK(hipMemsetAsync(d_o, 0, ob, s));
-    CTG_CHECK(launch_morph_rows(r, label_begin, label_end, d_o, d_r, s));
-    if (host) {
-        if (ob) CTG_CHECK(hipMemcpyAsync(out, d_o, ob, hipMemcpyDeviceToHost, s));
-        if (rb) CTG_CHECK(hipMemcpyAsync(rows, d_r, rb, hipMemcpyDeviceToHost, s));
-    }
+    DenseOut<double> od, orw;
+    int rc = hip_status(od.open(out, (size_t)n * CTG_MORPH_COLS * 8, mem, true, s), "ctg_morphology_rows");
+    if (!rc) rc = hip_status(orw.open(rows, (size_t)N * CTG_MORPH_COLS * 8, mem, false, s), "ctg_morphology_rows");
+    if (rc) return rc;
+    if (!od.d && !orw.d) return CTG_OK;
+    CTG_CHECK(launch_morph_rows(r, label_begin, label_end, od.d, orw.d, s));
+    CTG_CHECK(od.copy_back(s));
+    CTG_CHECK(orw.copy_back(s));
     CTG_CHECK(hipStreamSynchronize(s));
     return CTG_OK;
 }

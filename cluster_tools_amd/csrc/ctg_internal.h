@@ -554,7 +554,14 @@ hipError_t overlap_tables(Workspace& w, const void* A, int abits, const void* B,
 // n > 0 (key = a << 32 | b, count) records -> r: equal keys add their counts
 hipError_t overlap_reduce(Workspace& w, const uint64_t* key, const uint64_t* cnt, int64_t n, hipStream_t s,
                           ctg_result* r);
-hipError_t launch_overlap_heads(int64_t n, const uint64_t* key, uint64_t* flags, hipStream_t s);
+// The front half of a record reduce, shared with the morphology (ValueT: u32
+// or u64): n > 0 (key, value) pairs sorted by the keys' low end_bit bits into
+// (ks, vs), the runs numbered -- scan[i] counts the distinct keys (low word)
+// and distinct high key halves (high word) up to and including sorted position
+// i, *last = scan[n - 1], read back after a stream synchronise.
+template <typename ValueT>
+hipError_t sort_and_number(Workspace& w, const uint64_t* key, const ValueT* val, int64_t n, unsigned end_bit,
+                           hipStream_t s, uint64_t* ks, ValueT* vs, uint64_t* scan, uint64_t* last);
 hipError_t launch_overlap_pack(int64_t n, const uint64_t* pairs, uint64_t* key, hipStream_t s);
 hipError_t launch_overlap_map_back(int64_t E, uint64_t* pairs, const uint64_t* Ua, int64_t na, const uint64_t* Ub,
                                    int64_t nb, hipStream_t s);

@@ -4,10 +4,9 @@
 // and ndist.mergeAndSerializeMorphology (morphology/merge_morphology.py:130).
 //
 //   k_morph_scan   box of labels -> (key = label, 10-word moments) records, one
-//                  per (tile flush, label), through an LDS table per workgroup
+//                  per (tile flush, label): a tile-table scan (ctg_tile_table.h)
 //   k_morph_merge  float64 rows [id, size, com, min, max] -> the same records
-//   radix sort     (key, record slot) by key (rocPRIM radix_sort_pairs)
-//   k_overlap_heads + inclusive scan   number the distinct labels
+//   sort_and_number   (key, record slot) sorted by key, the distinct labels numbered
 //   k_morph_runs   per label: n and the three sums add in u64, the box folds
 //   k_morph_finish origin added in integers: sums += n * origin, box += origin
 //   k_morph_rows   moments -> float64 rows, compact and / or dense over a label range
@@ -38,29 +37,21 @@
 // touches the workspace's record or sort buffers, so a CTG_DEFER_STATS handle
 // stays valid across these calls.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
-#include <algorithm>
-
-#include "ctg_internal.h"
+#include "ctg_tile_table.h"
 
 namespace ctg {
 
-constexpr int MO_THREADS = 256;   // 4 waves: 4 planes per step, as k_overlap_scan
-constexpr int MO_TILE_Z = 16;
 #ifndef CTG_MORPH_CAP
 #define CTG_MORPH_CAP 512
 #endif
 constexpr int MO_CAP = CTG_MORPH_CAP;   // LDS table entries (A/B builds: make variant EXTRA=-DCTG_MORPH_CAP=...)
-constexpr int MO_PROBES = 32;     // linear probes before a head gives up on the table
 constexpr uint32_t MO_EMPTY = 0xFFFFFFFFu;
 constexpr int MO_SY = 19, MO_SZ = 35;   // bit positions of sum y / sum z in the packed sums
-static_assert((MO_CAP & (MO_CAP - 1)) == 0 && MO_CAP % MO_THREADS == 0, "table capacity");
-static_assert(WAVE * TILE_Y * MO_TILE_Z * (WAVE - 1) < (1 << MO_SY) &&
-                  WAVE * TILE_Y * MO_TILE_Z * (TILE_Y - 1) < (1 << (MO_SZ - MO_SY)) &&
-                  (uint64_t)WAVE * TILE_Y * MO_TILE_Z * (MO_TILE_Z - 1) < (1ull << (64 - MO_SZ)) && TILE_Y <= 8 &&
-                  MO_TILE_Z <= 24,
+static_assert(WAVE * TILE_Y * TT_TILE_Z * (WAVE - 1) < (1 << MO_SY) &&
+                  WAVE * TILE_Y * TT_TILE_Z * (TILE_Y - 1) < (1 << (MO_SZ - MO_SY)) &&
+                  (uint64_t)WAVE * TILE_Y * TT_TILE_Z * (TT_TILE_Z - 1) < (1ull << (64 - MO_SZ)) && TILE_Y <= 8 &&
+                  TT_TILE_Z <= 24,
               "a tile's sums fit their fields");
 
 // one record: MORPH_WORDS u64 at rec[slot * MORPH_WORDS]
@@ -82,18 +73,73 @@ __device__ __forceinline__ void morph_put(uint64_t* __restrict__ rkey, uint64_t*
     q[9] = x1;
 }
 
-// One workgroup per 64 x TILE_Y x 16 tile of the box, a wave per row, lane = x.
-// Equal consecutive labels collapse to their head lane (run length from the
-// ballot of heads); a head of the run [x0, x0 + run) of row (z, y) adds, in
-// tile-local coordinates, run to cnt, (run * x0 + run (run - 1) / 2, run * y,
-// run * z) to the packed sums, and ors the run's x bits and its y and z bits
-// into the occupancy words.  The table is written out when more than half full
-// after a z step and at tile end, one global reservation per flush, converted to
-// array coordinates (sum z = sum z_local + n * z0, ...); a head that finds no
-// slot within MO_PROBES writes its record directly.  Records past `cap` are
-// dropped: n_records still counts them and the host runs again with room.
+// The tile-table policy of the morphology (the entry's words: the header).  A
+// head of the run [x0, x0 + run) of row (z, y) adds, in tile-local coordinates,
+// run to cnt, (run * x0 + run (run - 1) / 2, run * y, run * z) to the packed
+// sums, and ors the run's x bits and its y and z bits into the occupancy words;
+// a flushed entry is converted to array coordinates (sum z = sum z_local +
+// n * z0, ...).  A label >= 2^32 raises bit 0 of label_overflow.
 template <typename LabelT>
-__global__ __launch_bounds__(MO_THREADS) void k_morph_scan(const LabelT* __restrict__ A, int64_t Y, int64_t X,
+struct MorphTable {
+    using Key = uint32_t;
+    static constexpr Key EMPTY = MO_EMPTY;
+    static constexpr int CAP = MO_CAP;
+    static constexpr bool SET = false, HOLES = false;
+    struct Add {
+        uint64_t sums, xbits;
+        uint32_t run, yzbits;
+    };
+    const LabelT* __restrict__ A;
+    uint32_t* keys;
+    uint32_t* tcnt;
+    uint64_t* tsum;
+    uint64_t* txo;
+    uint32_t* tyz;
+    uint64_t* __restrict__ rkey;
+    uint64_t* __restrict__ rec;
+    unsigned long long* count;
+    Counters* C;
+    __device__ uint64_t load(int64_t p, bool in) const { return in ? (uint64_t)A[p] : 0ull; }
+    __device__ bool valid(uint64_t, bool in) const { return in; }
+    __device__ Key key(uint64_t a) const { return (uint32_t)a; }
+    __device__ uint32_t overflow(uint64_t a) const { return (a >> 32) ? 1u : 0u; }
+    __device__ Add head(uint32_t run, int lane, int dy, int lz) const {
+        return Add{(uint64_t)(run * (uint32_t)lane + run * (run - 1u) / 2u) | (uint64_t)(run * (uint32_t)dy) << MO_SY |
+                       (uint64_t)(run * (uint32_t)lz) << MO_SZ,
+                   (run == WAVE ? ~0ull : (1ull << run) - 1ull) << lane, run, (1u << dy) | (1u << (8 + lz))};
+    }
+    __device__ void add(uint32_t h, const Add& a) const {
+        atomicAdd(&tcnt[h], a.run);
+        atomicAdd((unsigned long long*)&tsum[h], (unsigned long long)a.sums);
+        atomicOr((unsigned long long*)&txo[h], (unsigned long long)a.xbits);
+        atomicOr(&tyz[h], a.yzbits);
+    }
+    __device__ void put_direct(uint64_t slot, Key key, uint32_t run, int64_t z, int64_t y, int64_t x) const {
+        const uint64_t r = run;
+        morph_put(rkey, rec, slot, key, r, r * (uint64_t)z, r * (uint64_t)y, r * (uint64_t)x + r * (r - 1) / 2,
+                  (uint64_t)z, (uint64_t)y, (uint64_t)x, (uint64_t)z, (uint64_t)y, (uint64_t)x + r - 1);
+    }
+    __device__ void put_flush(uint64_t slot, int e, Key key, const TileBox& t) const {
+        const uint64_t n = tcnt[e], sm = tsum[e], xo = txo[e];
+        const uint32_t yo = tyz[e] & 0xFFu, zo = tyz[e] >> 8;
+        morph_put(rkey, rec, slot, key, n, (sm >> MO_SZ) + n * (uint64_t)t.z0,
+                  ((sm >> MO_SY) & ((1ull << (MO_SZ - MO_SY)) - 1ull)) + n * (uint64_t)t.y0,
+                  (sm & ((1ull << MO_SY) - 1ull)) + n * (uint64_t)t.x0, (uint64_t)(t.z0 + __ffs((int)zo) - 1),
+                  (uint64_t)(t.y0 + __ffs((int)yo) - 1), (uint64_t)(t.x0 + __ffsll((unsigned long long)xo) - 1),
+                  (uint64_t)(t.z0 + 31 - __clz((int)zo)), (uint64_t)(t.y0 + 31 - __clz((int)yo)),
+                  (uint64_t)(t.x0 + 63 - __clzll((long long)xo)));
+    }
+    __device__ void clear(int e) const {
+        keys[e] = EMPTY;
+        tcnt[e] = 0;
+        tsum[e] = 0;
+        txo[e] = 0;
+        tyz[e] = 0;
+    }
+};
+
+template <typename LabelT>
+__global__ __launch_bounds__(TT_THREADS) void k_morph_scan(const LabelT* __restrict__ A, int64_t Y, int64_t X,
                                                             int64_t bz, int64_t by, int64_t bx, int64_t ez,
                                                             int64_t ey, int64_t ex, uint64_t* __restrict__ rkey,
                                                             uint64_t* __restrict__ rec, int64_t cap, Counters* C) {
@@ -102,152 +148,17 @@ __global__ __launch_bounds__(MO_THREADS) void k_morph_scan(const LabelT* __restr
     __shared__ uint32_t tkey[MO_CAP];
     __shared__ uint32_t tcnt[MO_CAP];
     __shared__ uint32_t tyz[MO_CAP];
-    __shared__ uint32_t used;
-    __shared__ uint32_t wpos;
-    __shared__ unsigned long long base;
-    const int tid = threadIdx.x;
-    for (int e = tid; e < MO_CAP; e += MO_THREADS) {
-        tkey[e] = MO_EMPTY;
-        tcnt[e] = 0;
-        tsum[e] = 0;
-        txo[e] = 0;
-        tyz[e] = 0;
-    }
-    if (tid == 0) used = 0;
-    __syncthreads();
-    const int lane = tid & (WAVE - 1), wave = tid >> 6;
-    const int64_t x0 = bx + (int64_t)blockIdx.x * WAVE;
-    const int64_t x = x0 + lane;
-    const int64_t y0 = by + (int64_t)blockIdx.y * TILE_Y;
-    const int64_t z0 = bz + (int64_t)blockIdx.z * MO_TILE_Z;
-    const bool in = x < ex;
-    uint32_t over = 0;
-    for (int zs = 0; zs < MO_TILE_Z; zs += MO_THREADS / WAVE) {
-        const int lz = zs + wave;
-        const int64_t z = z0 + lz;
-        if (z < ez) {   // (wave-uniform, like the row bound below)
-            for (int dy = 0; dy < TILE_Y; ++dy) {
-                const int64_t y = y0 + dy;
-                if (y >= ey) break;
-                const uint64_t a = in ? (uint64_t)A[(z * Y + y) * X + x] : 0ull;
-                if (in && (a >> 32)) over = 1u;
-                const uint32_t key = (uint32_t)a;
-                const uint32_t prev = __shfl_up(key, 1, WAVE);
-                // (lanes below a lane inside the box are inside it too)
-                const bool head = in && (lane == 0 || prev != key);
-                const uint64_t bound = __ballot(head || !in);
-                bool direct = false;
-                uint32_t run = 0;
-                if (head) {
-                    const uint64_t above = lane == WAVE - 1 ? 0ull : bound >> (lane + 1);
-                    run = above ? (uint32_t)__ffsll((unsigned long long)above) : (uint32_t)(WAVE - lane);
-                    direct = true;
-                    if (key != MO_EMPTY) {   // (the one key that looks like a free slot goes direct)
-                        const uint64_t add = (uint64_t)(run * (uint32_t)lane + run * (run - 1u) / 2u) |
-                                             (uint64_t)(run * (uint32_t)dy) << MO_SY |
-                                             (uint64_t)(run * (uint32_t)lz) << MO_SZ;
-                        const uint64_t xbits = (run == WAVE ? ~0ull : (1ull << run) - 1ull) << lane;
-                        const uint32_t yzbits = (1u << dy) | (1u << (8 + lz));
-                        uint32_t h = hash_key(key) & (MO_CAP - 1);
-                        for (int q = 0; q < MO_PROBES; ++q) {
-                            uint32_t cur = tkey[h];
-                            if (cur == MO_EMPTY) {
-                                cur = atomicCAS(&tkey[h], MO_EMPTY, key);
-                                if (cur == MO_EMPTY) {
-                                    atomicAdd(&used, 1u);
-                                    cur = key;
-                                }
-                            }
-                            if (cur == key) {
-                                atomicAdd(&tcnt[h], run);
-                                atomicAdd((unsigned long long*)&tsum[h], (unsigned long long)add);
-                                atomicOr((unsigned long long*)&txo[h], (unsigned long long)xbits);
-                                atomicOr(&tyz[h], yzbits);
-                                direct = false;
-                                break;
-                            }
-                            h = (h + 1) & (MO_CAP - 1);
-                        }
-                    }
-                }
-                const uint64_t dm = __ballot(direct);
-                if (dm) {
-                    const uint32_t n = (uint32_t)__popcll(dm);
-                    const uint32_t rank =
-                        __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0));
-                    unsigned long long b0 = 0;
-                    if (lane == 0) {
-                        b0 = atomicAdd(&C->n_records, (unsigned long long)n);
-                        atomicAdd(&C->n_direct, (unsigned long long)n);
-                    }
-                    b0 = bcast0_u64(b0);
-                    if (direct && b0 + rank < (unsigned long long)cap) {
-                        CTG_IDX(b0 + rank, cap);
-                        const uint64_t r = run;
-                        morph_put(rkey, rec, b0 + rank, key, r, r * (uint64_t)z, r * (uint64_t)y,
-                                  r * (uint64_t)x + r * (r - 1) / 2, (uint64_t)z, (uint64_t)y, (uint64_t)x, (uint64_t)z,
-                                  (uint64_t)y, (uint64_t)x + r - 1);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (used > MO_CAP / 2 || zs + MO_THREADS / WAVE >= MO_TILE_Z) {   // (uniform: read after the barrier)
-            if (tid == 0) {
-                base = used ? atomicAdd(&C->n_records, (unsigned long long)used) : 0ull;
-                wpos = 0;
-            }
-            __syncthreads();
-            // compaction order is irrelevant (sorted afterwards)
-            for (int e = tid; e < MO_CAP; e += MO_THREADS) {
-                const uint32_t k = tkey[e];
-                const bool live = k != MO_EMPTY;
-                const uint64_t m = __ballot(live);
-                if (m) {
-                    const uint32_t rank =
-                        __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-                    uint32_t w0 = 0;
-                    if (lane == 0) w0 = atomicAdd(&wpos, (uint32_t)__popcll(m));
-                    w0 = __shfl(w0, 0, WAVE);
-                    if (live) {
-                        const unsigned long long slot = base + w0 + rank;
-                        if (slot < (unsigned long long)cap) {
-                            CTG_IDX(slot, cap);
-                            const uint64_t n = tcnt[e], sm = tsum[e], xo = txo[e];
-                            const uint32_t yo = tyz[e] & 0xFFu, zo = tyz[e] >> 8;
-                            morph_put(rkey, rec, slot, k, n, (sm >> MO_SZ) + n * (uint64_t)z0,
-                                      ((sm >> MO_SY) & ((1ull << (MO_SZ - MO_SY)) - 1ull)) + n * (uint64_t)y0,
-                                      (sm & ((1ull << MO_SY) - 1ull)) + n * (uint64_t)x0,
-                                      (uint64_t)(z0 + __ffs((int)zo) - 1), (uint64_t)(y0 + __ffs((int)yo) - 1),
-                                      (uint64_t)(x0 + __ffsll((unsigned long long)xo) - 1),
-                                      (uint64_t)(z0 + 31 - __clz((int)zo)), (uint64_t)(y0 + 31 - __clz((int)yo)),
-                                      (uint64_t)(x0 + 63 - __clzll((long long)xo)));
-                        }
-                        tkey[e] = MO_EMPTY;
-                        tcnt[e] = 0;
-                        tsum[e] = 0;
-                        txo[e] = 0;
-                        tyz[e] = 0;
-                    }
-                }
-            }
-            __syncthreads();
-            if (tid == 0) used = 0;
-            __syncthreads();
-        }
-    }
-    over = (uint32_t)__any((int)over);
-    if (lane == 0 && over) atomicOr(&C->label_overflow, 1ull);
+    const MorphTable<LabelT> pol{A, tkey, tcnt, tsum, txo, tyz, rkey, rec, &C->n_records, C};
+    tile_table_scan(pol, tile_of_grid(Y, X, bz, by, bx, ez, ey, ex), cap);
 }
 
 template <typename LabelT>
 static hipError_t launch_morph_scan_t(const void* A, const int64_t* shape, const int64_t* b, const int64_t* e,
                                       uint64_t* rkey, uint64_t* rec, int64_t cap, Counters* C, hipStream_t s) {
-    const int64_t gx = (e[2] - b[2] + WAVE - 1) / WAVE, gy = (e[1] - b[1] + TILE_Y - 1) / TILE_Y,
-                  gz = (e[0] - b[0] + MO_TILE_Z - 1) / MO_TILE_Z;
-    if (gx > 0x7FFFFFFFll || gy > 65535 || gz > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_morph_scan<LabelT>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3(MO_THREADS), 0, s,
-                       (const LabelT*)A, shape[1], shape[2], b[0], b[1], b[2], e[0], e[1], e[2], rkey, rec, cap, C);
+    dim3 grid;
+    CTG_TRY(tile_grid(b, e, &grid));
+    hipLaunchKernelGGL((k_morph_scan<LabelT>), grid, dim3(TT_THREADS), 0, s, (const LabelT*)A, shape[1], shape[2],
+                       b[0], b[1], b[2], e[0], e[1], e[2], rkey, rec, cap, C);
     return hipGetLastError();
 }
 
@@ -378,34 +289,21 @@ __global__ void k_morph_rows(int64_t N, const uint64_t* __restrict__ nodes, cons
         for (int c = 0; c < CTG_MORPH_COLS; ++c) out[(a - lb) * CTG_MORPH_COLS + c] = r[c];
 }
 
-static dim3 grid_for(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
 // n (key, record) pairs -> r's nodes and moments (array coordinates + origin):
 // sort the record slots by key, number the labels, fold.  n in (0, 2^32 - 1);
 // keys compare in their low end_bit bits.
 static hipError_t morph_reduce(Workspace& w, const uint64_t* key, const uint64_t* rec, int64_t n, unsigned end_bit,
                                const int64_t* origin, hipStream_t s, ctg_result* r) {
     Ev ev{w, s};
-    DevBuf<uint64_t> ks((size_t)n * 8), flags((size_t)n * 8), scan((size_t)n * 8);
+    DevBuf<uint64_t> ks((size_t)n * 8), scan((size_t)n * 8);
     DevBuf<uint32_t> idx((size_t)n * 4), is((size_t)n * 4);
-    if (!ks || !flags || !scan || !idx || !is) return hipErrorOutOfMemory;
+    if (!ks || !scan || !idx || !is) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(k_morph_iota, grid_for(n), dim3(256), 0, s, n, idx.p);
     CTG_TRY(hipGetLastError());
-    CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
-        return rocprim::radix_sort_pairs(t, tb, key, ks.p, idx.p, is.p, (size_t)n, 0u, end_bit, s);
-    }));
-    ev.mark(3);
-    CTG_TRY(launch_overlap_heads(n, ks, flags, s));
-    CTG_TRY(with_temp(w.temp, [&](void* t, size_t& tb) {
-        return rocprim::inclusive_scan(t, tb, flags.p, scan.p, (size_t)n, rocprim::plus<uint64_t>(), s);
-    }));
     uint64_t last = 0;
-    CTG_TRY(hipMemcpyAsync(&last, scan.p + (n - 1), 8, hipMemcpyDeviceToHost, s));
-    CTG_TRY(hipStreamSynchronize(s));
-    flags.reset();
+    CTG_TRY(sort_and_number(w, key, (const uint32_t*)idx.p, n, end_bit, s, ks.p, is.p, scan.p, &last));
     idx.reset();
     const int64_t N = (int64_t)(uint32_t)last;
-    ev.mark(4);
     DevBuf<uint64_t> nodes((size_t)N * 8), mom((size_t)N * MORPH_WORDS * 8);
     if (!nodes || !mom) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(k_morph_init, grid_for(N * MORPH_WORDS), dim3(256), 0, s, N, mom.p);
@@ -427,41 +325,26 @@ static hipError_t morph_reduce(Workspace& w, const uint64_t* key, const uint64_t
 
 hipError_t morph_tables(Workspace& w, const void* A, int bits, const int64_t* shape, const int64_t* b,
                         const int64_t* e, const int64_t* origin, hipStream_t s, ctg_result* r, unsigned* overflow) {
-    *overflow = 0;
     Ev ev{w, s};
-    const int64_t nb = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]);
-    // a record per voxel at most; coarse labellings need a small fraction of that
-    int64_t cap = std::min<int64_t>(nb, std::max<int64_t>(1 << 12, nb / 16));
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        DevBuf<uint64_t> rkey((size_t)cap * 8), rec((size_t)cap * MORPH_WORDS * 8);
-        if (!rkey || !rec) return hipErrorOutOfMemory;
-        CTG_TRY(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
-        ev.mark(0);
-        CTG_TRY(bits == 32 ? launch_morph_scan_t<uint32_t>(A, shape, b, e, rkey, rec, cap, w.counters, s)
-                           : launch_morph_scan_t<uint64_t>(A, shape, b, e, rkey, rec, cap, w.counters, s));
-        ev.mark(1);
-        ev.mark(2);
-        CTG_TRY(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
-        CTG_TRY(hipStreamSynchronize(s));
-        if (w.counters_host->label_overflow) {
-            *overflow = 1;
-            return hipSuccess;
-        }
-        const int64_t m = (int64_t)w.counters_host->n_records;
-        if (m > cap) {
-            // which heads miss the table depends on the order of arrival, so a
-            // second run may count a few more: the third gets a slot per voxel
-            cap = attempt == 0 ? std::min<int64_t>(nb, m + m / 8 + 1024) : nb;
-            continue;
-        }
-        if (m <= 0 || m >= 0xFFFFFFFFll) return hipErrorInvalidValue;   // (the API refuses empty and 2^32-voxel boxes)
-        r->n_records = m;
-        r->n_direct = (int64_t)w.counters_host->n_direct;
-        CTG_TRY(morph_reduce(w, rkey, rec, m, 32u, origin, s, r));
-        ev.mark(6);
-        return hipSuccess;
-    }
-    return hipErrorOutOfMemory;   // (unreachable: the third attempt holds every voxel)
+    DevBuf<uint64_t> rkey, rec;
+    int64_t m = 0;
+    CTG_TRY(scan_into_records(
+        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s,
+        [&](int64_t cap) {
+            rkey.reset();
+            rec.reset();
+            if (!rkey.alloc((size_t)cap * 8) || !rec.alloc((size_t)cap * MORPH_WORDS * 8)) return hipErrorOutOfMemory;
+            return bits == 32 ? launch_morph_scan_t<uint32_t>(A, shape, b, e, rkey, rec, cap, w.counters, s)
+                              : launch_morph_scan_t<uint64_t>(A, shape, b, e, rkey, rec, cap, w.counters, s);
+        },
+        &m, overflow));
+    if (*overflow) return hipSuccess;
+    if (m <= 0 || m >= 0xFFFFFFFFll) return hipErrorInvalidValue;   // (the API refuses empty and 2^32-voxel boxes)
+    r->n_records = m;
+    r->n_direct = (int64_t)w.counters_host->n_direct;
+    CTG_TRY(morph_reduce(w, rkey, rec, m, 32u, origin, s, r));
+    ev.mark(6);
+    return hipSuccess;
 }
 
 hipError_t morph_merge(Workspace& w, const double* rows, int64_t n, hipStream_t s, ctg_result* r, int* bad) {

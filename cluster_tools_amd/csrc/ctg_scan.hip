@@ -33,8 +33,8 @@
 // wave polls after each fold batch and plane (see k_face_scan).
 #include <type_traits>
 
-#include "ctg_internal.h"
 #include "ctg_stats.h"
+#include "ctg_tile_table.h"
 
 #ifndef CTG_ROWS
 #define CTG_ROWS 4
@@ -1500,77 +1500,40 @@ int scan_tile_rows_narrow() { return ROWS_NARROW * WAVES; }
 // ---------------------------------------------------------------------------
 // unique labels of a box (per-block ``nodes``): LDS hash set per tile
 // ---------------------------------------------------------------------------
-constexpr int UNIQ_THREADS = 256;  // 4 waves: the unique-label scan walks 4 planes per step
 constexpr int USET_CAP = 2048;
 
-__global__ __launch_bounds__(UNIQ_THREADS) void k_unique_tiles(const uint64_t* L, int64_t Y, int64_t X,
-                                                                int64_t bz, int64_t by, int64_t bx,
-                                                                int64_t ez, int64_t ey, int64_t ex,
-                                                                uint64_t* out, unsigned long long* count,
-                                                                int64_t cap) {
+// The tile-table policy of both kernels (ctg_tile_table.h): a set of u64 keys,
+// key = tag | (KeptT)label, written out as they are.  A label whose key equals
+// EMPTY_KEY is not reported.
+template <typename LabelT, typename KeptT>
+struct UniqueSet {
+    using Key = uint64_t;
+    static constexpr Key EMPTY = EMPTY_KEY;
+    static constexpr int CAP = USET_CAP;
+    static constexpr bool SET = true, HOLES = false;
+    const LabelT* __restrict__ L;
+    uint64_t tag;
+    uint64_t* keys;
+    uint64_t* __restrict__ out;
+    unsigned long long* count;
+    __device__ Key load(int64_t p, bool in) const { return in ? (tag | (KeptT)L[p]) : EMPTY_KEY; }
+    __device__ bool valid(Key, bool in) const { return in; }
+    __device__ Key key(Key k) const { return k; }
+    __device__ uint32_t overflow(Key) const { return 0u; }
+    __device__ int head(uint32_t, int, int, int) const { return 0; }
+    __device__ void add(uint32_t, int) const {}
+    __device__ void put_flush(uint64_t slot, int, Key key, const TileBox&) const { out[slot] = key; }
+    __device__ void clear(int e) const { keys[e] = EMPTY; }
+};
+
+__global__ __launch_bounds__(TT_THREADS) void k_unique_tiles(const uint64_t* L, int64_t Y, int64_t X,
+                                                              int64_t bz, int64_t by, int64_t bx,
+                                                              int64_t ez, int64_t ey, int64_t ex,
+                                                              uint64_t* out, unsigned long long* count,
+                                                              int64_t cap) {
     __shared__ uint64_t set[USET_CAP];
-    __shared__ uint32_t used;
-    __shared__ unsigned long long base;
-    __shared__ uint32_t wpos;
-    const int tid = threadIdx.x;
-    for (int e = tid; e < USET_CAP; e += UNIQ_THREADS) set[e] = EMPTY_KEY;
-    if (tid == 0) used = 0;
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    const int64_t x = bx + (int64_t)blockIdx.x * 64 + lane;
-    const int64_t y0 = by + (int64_t)blockIdx.y * TILE_Y;
-    const int64_t z0 = bz + (int64_t)blockIdx.z * 16;
-    for (int zs = 0; zs < 16; zs += 4) {
-        const int64_t z = z0 + zs + wave;
-        if (z < ez) {
-            for (int dy = 0; dy < TILE_Y; ++dy) {
-                const int64_t y = y0 + dy;
-                if (y >= ey) break;
-                uint64_t l = (x < ex) ? L[(z * Y + y) * X + x] : EMPTY_KEY;
-                uint32_t lo = (uint32_t)l, hi = (uint32_t)(l >> 32);
-                uint32_t plo = __shfl_up(lo, 1, 64), phi = __shfl_up(hi, 1, 64);
-                uint64_t prev = ((uint64_t)phi << 32) | plo;
-                const bool head = (x < ex) && (lane == 0 || prev != l);
-                if (head) {
-                    uint32_t h = hash_key(l) & (USET_CAP - 1);
-                    for (int p = 0; p < USET_CAP; ++p) {
-                        uint64_t cur = set[h];
-                        if (cur == l) break;
-                        if (cur == EMPTY_KEY) {
-                            uint64_t old = atomicCAS((unsigned long long*)&set[h], (unsigned long long)EMPTY_KEY,
-                                                     (unsigned long long)l);
-                            if (old == EMPTY_KEY) {
-                                atomicAdd(&used, 1u);
-                                break;
-                            }
-                            if (old == l) break;
-                        }
-                        h = (h + 1) & (USET_CAP - 1);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (used > USET_CAP / 2 || zs + 4 >= 16) {
-            if (tid == 0) {
-                base = atomicAdd(count, (unsigned long long)used);
-                wpos = 0;
-            }
-            __syncthreads();
-            // compaction order is irrelevant (sorted afterwards)
-            for (int e = tid; e < USET_CAP; e += UNIQ_THREADS) {
-                uint64_t k = set[e];
-                if (k != EMPTY_KEY) {
-                    uint32_t r = atomicAdd(&wpos, 1u);
-                    if (base + r < (unsigned long long)cap) out[base + r] = k;
-                    set[e] = EMPTY_KEY;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) used = 0;
-            __syncthreads();
-        }
-    }
+    const UniqueSet<uint64_t, uint64_t> pol{L, 0ull, set, out, count};
+    tile_table_scan(pol, tile_of_grid(Y, X, bz, by, bx, ez, ey, ex), cap);
 }
 
 // Per-block node lists of a batched call (ctg_rag_blocks): the unique labels
@@ -1578,18 +1541,12 @@ __global__ __launch_bounds__(UNIQ_THREADS) void k_unique_tiles(const uint64_t* L
 // per 64 x 8 x 16 tile, emitted as (block << 32) | label candidates; sorting
 // and de-duplicating them leaves each block's sorted nodes contiguous.
 template <typename LabelT>
-__global__ __launch_bounds__(UNIQ_THREADS) void k_unique_blocks(const LabelT* __restrict__ L,
-                                                                 const BlockGeom* __restrict__ blocks,
-                                                                 const uint32_t* __restrict__ tile_prefix,
-                                                                 int n_blocks, uint64_t* __restrict__ out,
-                                                                 unsigned long long* count, int64_t cap) {
+__global__ __launch_bounds__(TT_THREADS) void k_unique_blocks(const LabelT* __restrict__ L,
+                                                               const BlockGeom* __restrict__ blocks,
+                                                               const uint32_t* __restrict__ tile_prefix,
+                                                               int n_blocks, uint64_t* __restrict__ out,
+                                                               unsigned long long* count, int64_t cap) {
     __shared__ uint64_t set[USET_CAP];
-    __shared__ uint32_t used;
-    __shared__ unsigned long long base;
-    __shared__ uint32_t wpos;
-    const int tid = threadIdx.x;
-    for (int e = tid; e < USET_CAP; e += UNIQ_THREADS) set[e] = EMPTY_KEY;
-    if (tid == 0) used = 0;
     uint32_t t = blockIdx.x;
     int lo = 0, hi = n_blocks;
     while (hi - lo > 1) {
@@ -1602,63 +1559,11 @@ __global__ __launch_bounds__(UNIQ_THREADS) void k_unique_blocks(const LabelT* __
     const int bz = G.own_begin[0], by = G.own_begin[1], bx = G.own_begin[2];
     const int ez = G.own_end[0], ey = G.own_end[1], ex = G.own_end[2];
     const uint32_t ntx = (uint32_t)(ex - bx + 63) / 64, nty = (uint32_t)(ey - by + TILE_Y - 1) / TILE_Y;
-    const int64_t Y = G.shape[1], X = G.shape[2];
-    const LabelT* Lb = L + G.label_offset;
-    const uint64_t tag = (uint64_t)lo << 32;
-    __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    const int64_t x = bx + (int64_t)(t % ntx) * 64 + lane;
-    const int64_t y0 = by + (int64_t)((t / ntx) % nty) * TILE_Y;
-    const int64_t z0 = bz + (int64_t)(t / (ntx * nty)) * 16;
-    for (int zs = 0; zs < 16; zs += 4) {
-        const int64_t z = z0 + zs + wave;
-        if (z < ez) {
-            for (int dy = 0; dy < TILE_Y; ++dy) {
-                const int64_t y = y0 + dy;
-                if (y >= ey) break;
-                const uint64_t l = (x < ex) ? (tag | (uint32_t)Lb[(z * Y + y) * X + x]) : EMPTY_KEY;
-                uint32_t plo = __shfl_up((uint32_t)l, 1, 64), phi = __shfl_up((uint32_t)(l >> 32), 1, 64);
-                const uint64_t prev = ((uint64_t)phi << 32) | plo;
-                const bool head = (x < ex) && (lane == 0 || prev != l);
-                if (head) {
-                    uint32_t h = hash_key(l) & (USET_CAP - 1);
-                    for (int p = 0; p < USET_CAP; ++p) {
-                        const uint64_t cur = set[h];
-                        if (cur == l) break;
-                        if (cur == EMPTY_KEY) {
-                            const uint64_t old = atomicCAS((unsigned long long*)&set[h],
-                                                           (unsigned long long)EMPTY_KEY, (unsigned long long)l);
-                            if (old == EMPTY_KEY) {
-                                atomicAdd(&used, 1u);
-                                break;
-                            }
-                            if (old == l) break;
-                        }
-                        h = (h + 1) & (USET_CAP - 1);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (used > USET_CAP / 2 || zs + 4 >= 16) {
-            if (tid == 0) {
-                base = atomicAdd(count, (unsigned long long)used);
-                wpos = 0;
-            }
-            __syncthreads();
-            for (int e = tid; e < USET_CAP; e += UNIQ_THREADS) {
-                const uint64_t k = set[e];
-                if (k != EMPTY_KEY) {
-                    const uint32_t r = atomicAdd(&wpos, 1u);
-                    if (base + r < (unsigned long long)cap) out[base + r] = k;
-                    set[e] = EMPTY_KEY;
-                }
-            }
-            __syncthreads();
-            if (tid == 0) used = 0;
-            __syncthreads();
-        }
-    }
+    const TileBox box{G.shape[1], G.shape[2], bx + (int64_t)(t % ntx) * WAVE,
+                      by + (int64_t)((t / ntx) % nty) * TILE_Y, bz + (int64_t)(t / (ntx * nty)) * TT_TILE_Z,
+                      ez, ey, ex};
+    const UniqueSet<LabelT, uint32_t> pol{L + G.label_offset, (uint64_t)lo << 32, set, out, count};
+    tile_table_scan(pol, box, cap);
 }
 
 hipError_t launch_unique_blocks(const void* L, int label_bits, const BlockGeom* blocks, const uint32_t* tile_prefix,
@@ -1666,10 +1571,10 @@ hipError_t launch_unique_blocks(const void* L, int label_bits, const BlockGeom* 
                                 hipStream_t s) {
     if (n_tiles <= 0) return hipSuccess;
     if (label_bits == 32)
-        hipLaunchKernelGGL(k_unique_blocks<uint32_t>, dim3((unsigned)n_tiles), dim3(UNIQ_THREADS), 0, s,
+        hipLaunchKernelGGL(k_unique_blocks<uint32_t>, dim3((unsigned)n_tiles), dim3(TT_THREADS), 0, s,
                            (const uint32_t*)L, blocks, tile_prefix, n_blocks, out, count, cap);
     else
-        hipLaunchKernelGGL(k_unique_blocks<uint64_t>, dim3((unsigned)n_tiles), dim3(UNIQ_THREADS), 0, s,
+        hipLaunchKernelGGL(k_unique_blocks<uint64_t>, dim3((unsigned)n_tiles), dim3(TT_THREADS), 0, s,
                            (const uint64_t*)L, blocks, tile_prefix, n_blocks, out, count, cap);
     return hipGetLastError();
 }
@@ -1680,7 +1585,7 @@ hipError_t launch_unique_tiles(const uint64_t* L, const int64_t* shape, const in
                                uint64_t* out, unsigned long long* count, int64_t cap, hipStream_t s) {
     dim3 grid((unsigned)((e[2] - b[2] + 63) / 64), (unsigned)((e[1] - b[1] + TILE_Y - 1) / TILE_Y),
               (unsigned)((e[0] - b[0] + 15) / 16));
-    hipLaunchKernelGGL(k_unique_tiles, grid, dim3(UNIQ_THREADS), 0, s, L, shape[1], shape[2], b[0], b[1], b[2],
+    hipLaunchKernelGGL(k_unique_tiles, grid, dim3(TT_THREADS), 0, s, L, shape[1], shape[2], b[0], b[1], b[2],
                        e[0], e[1], e[2], out, count, cap);
     return hipGetLastError();
 }

@@ -482,6 +482,33 @@ def test_unique_and_map_helpers(gpu):
     np.testing.assert_array_equal(rag.unique_labels(lab, (2, 3, 4), (7, 9, 10)), np.unique(lab[2:7, 3:9, 4:10]))
 
 
+def _distinct_label_volume(dtype=np.uint64):
+    """(16, 16, 128), a label of its own at every voxel: a 64 x 8 x 16 tile of
+    the unique-label kernels meets 2048 distinct keys per 4-plane step against
+    its 2048-entry set, so every step fills the set and flushes mid-tile."""
+    return np.arange(1, 16 * 16 * 128 + 1, dtype=dtype).reshape(16, 16, 128)
+
+
+def test_unique_labels_flush_every_step(gpu):
+    lab = _distinct_label_volume()
+    np.testing.assert_array_equal(rag.unique_labels(lab), np.unique(lab))
+    np.testing.assert_array_equal(rag.unique_labels(lab, (1, 3, 5), (15, 13, 121)),
+                                  np.unique(lab[1:15, 3:13, 5:121]))
+
+
+@pytest.mark.parametrize('dtype', [np.uint32, np.uint64])
+def test_block_nodes_flush_every_step(gpu, dtype):
+    """The same volume as two blocks along z (the second with its lower halo
+    plane): the per-block nodes of the batched call."""
+    lab = _distinct_label_volume(dtype)
+    whole = ((0, 0, 0), (8, 16, 128))
+    upper = ((1, 0, 0), (9, 16, 128))
+    res = rag.rag_blocks([lab[0:8], lab[7:16]], [whole, upper], [whole, ((0, 0, 0), (9, 16, 128))])
+    assert len(res) == 2
+    np.testing.assert_array_equal(res[0]['nodes'], np.unique(lab[0:8]).astype(np.uint64))
+    np.testing.assert_array_equal(res[1]['nodes'], np.unique(lab[8:16]).astype(np.uint64))
+
+
 @pytest.mark.parametrize('defer', [False, True])
 def test_hip_backend_slabs_merge(gpu, defer):
     """The multi-GPU data path (local partials -> ctg_mgpu_split / pack ->
