@@ -1,0 +1,317 @@
+// C ABI of libctg.so (include/ctg.h): label overlaps and segment morphology
+// (kernels and back halves: ctg_overlap.hip, ctg_morph.hip).  What the entry
+// points share comes first; the call scaffold is ctg_api.h's.
+#include <hip/hip_runtime.h>
+
+#include "ctg_api.h"
+
+using namespace ctg;
+
+constexpr int64_t TABLE_MAX_VOXELS = 0xFFFFFFFFll;   // a record per voxel at most; the run table numbers records in 32 bits
+
+// an overlaps / a morphology result without rows: the placeholders of
+// empty_result plus the counts' / the moments'
+static ResultPtr empty_overlaps(int device) {
+    ResultPtr r = empty_result(device);
+    r->counts = (uint64_t*)dev_alloc(8);
+    return r;
+}
+static ResultPtr empty_morphology(int device) {
+    ResultPtr r = empty_result(device);
+    r->moments = (uint64_t*)dev_alloc(8);
+    return r;
+}
+
+// A label volume of ctg_label_overlaps / ctg_morphology whose labels reach
+// 2^32: the box's sorted unique labels U and the whole array as 32-bit ranks in
+// U (monotone; voxels outside the box get some rank and are never read).
+struct DenseSide {
+    ResultPtr U;
+    DevBuf<uint32_t> ids;
+    int build(const void* vol, const int64_t* shape, const int64_t* b, const int64_t* e, void* stream,
+              const char* who) {
+        int rc = nested(U, [&](ctg_result** u) {
+            return ctg_unique_labels((const uint64_t*)vol, shape, b, e, CTG_MEM_DEVICE, stream, u);
+        });
+        if (rc) return rc;
+        if (U->n_nodes > 0xFFFFFFFFll) {
+            set_error(std::string(who) + ": more than 2^32 distinct labels in one box");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        const int64_t V = shape[0] * shape[1] * shape[2];
+        if (!ids.alloc((size_t)V * 4)) {
+            set_error(std::string(who) + ": out of device memory for the dense relabelling");
+            return CTG_ERR_NOMEM;
+        }
+        CTG_CHECK(launch_remap_dense((const uint64_t*)vol, V, U->nodes, U->n_nodes, ids, (hipStream_t)stream));
+        return CTG_OK;
+    }
+};
+
+extern "C" {
+
+int ctg_label_overlaps(const void* labels, int label_bits, const void* values, int value_bits, const int64_t* shape,
+                       const int64_t* begin, const int64_t* end, int with_ignore, uint64_t ignore_label, int mem,
+                       void* stream, ctg_result** out) {
+    const char* who = "ctg_label_overlaps";
+    ApiCall c;
+    if (!labels || !values || !shape || !out) {
+        set_error("ctg_label_overlaps: null argument");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if ((label_bits != 32 && label_bits != 64) || (value_bits != 32 && value_bits != 64)) {
+        set_error("ctg_label_overlaps: label_bits and value_bits must be 32 or 64");
+        return CTG_ERR_ARG;
+    }
+    CallBox box;
+    int rc = box_of(who, shape, begin, end, TABLE_MAX_VOXELS, &box);
+    if (rc || (rc = c.begin(stream, empty_overlaps)) != CTG_OK) return rc;
+    if (box.voxels == 0) return c.end(false, out);
+    const int64_t *b = box.b, *e = box.e;
+    Workspace& w = c.w();
+    hipStream_t s = c.s;
+    ctg_result* r = c.r.get();
+    const int64_t V = shape[0] * shape[1] * shape[2];
+    const void *dl = nullptr, *dv = nullptr;
+    rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
+    if (!rc) rc = stage_in(w.stage[1], values, (size_t)V * (value_bits / 8), mem, s, &dv);
+    if (rc) return rc;
+    unsigned over = 0;
+    if ((rc = hip_status(overlap_tables(w, dl, label_bits, dv, value_bits, shape, b, e, with_ignore, ignore_label, s,
+                                        r, &over),
+                         who)) != CTG_OK)
+        return rc;
+    if (over) {
+        // labels >= 2^32 do not fit the 32 + 32 bit keys.  1: the side(s) that
+        // hold them become monotone dense ids
+        DenseSide da, db;
+        if ((over & 1u) && (rc = da.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
+        if ((over & 2u) && (rc = db.build(dv, shape, b, e, stream, who)) != CTG_OK) return rc;
+        // 2: so does the ignore label (absent from the box: nothing to skip)
+        if ((over & 2u) && with_ignore) {
+            DevBuf<uint32_t> rank(4);
+            uint32_t h = 0;
+            if (!rank) return hip_status(hipErrorOutOfMemory, who);
+            CTG_CHECK(launch_overlap_find(db.U->nodes, db.U->n_nodes, ignore_label, rank, s));
+            CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
+            CTG_CHECK(hipStreamSynchronize(s));
+            with_ignore = h != 0xFFFFFFFFu;
+            ignore_label = h;
+        }
+        // 3: the scan runs again on the ids
+        unsigned again = 0;
+        if ((rc = hip_status(overlap_tables(w, da.U ? (const void*)da.ids.p : dl, da.U ? 32 : label_bits,
+                                            db.U ? (const void*)db.ids.p : dv, db.U ? 32 : value_bits, shape, b, e,
+                                            with_ignore, ignore_label, s, r, &again),
+                             who)) != CTG_OK)
+            return rc;
+        // 4: which cannot overflow
+        if (again) {
+            set_error("ctg_label_overlaps: dense ids past 2^32");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        // 5: the sorted tables map back to labels
+        CTG_CHECK(launch_overlap_map_back(r->n_edges, r->edges, da.U ? da.U->nodes : nullptr,
+                                          da.U ? da.U->n_nodes : 0, db.U ? db.U->nodes : nullptr,
+                                          db.U ? db.U->n_nodes : 0, s));
+        if (da.U) CTG_CHECK(launch_gather_labels(da.U->nodes, r->nodes, r->n_nodes, s));
+    }
+    return c.end(r->n_records > 0, out, true);
+}
+
+int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n, int mem, void* stream,
+                       ctg_result** out) {
+    ApiCall c;
+    if (!out || n < 0 || (n > 0 && (!pairs || !counts))) {
+        set_error("ctg_merge_overlaps: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (n >= 0xFFFFFFFFll) {
+        set_error("ctg_merge_overlaps: 2^32 rows or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    int rc = c.begin(stream, empty_overlaps);
+    if (rc) return rc;
+    if (n == 0) return c.end(false, out);
+    Workspace& w = c.w();
+    hipStream_t s = c.s;
+    ResultPtr& r = c.r;
+    DevInput<uint64_t> dp, dc;
+    rc = dp.put(pairs, (size_t)n * 16, mem, s, "ctg_merge_overlaps");
+    if (!rc) rc = dc.put(counts, (size_t)n * 8, mem, s, "ctg_merge_overlaps");
+    if (rc) return rc;
+    CTG_CHECK(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
+    CTG_CHECK(launch_max_pairs(n, dp, &w.counters->max_v, s));
+    CTG_CHECK(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    DensePairs dense;
+    const uint64_t* src = dp;
+    if (w.counters_host->max_v >> 32) {
+        if ((rc = dense.build(dp, n, s)) != CTG_OK) return rc;
+        if (dense.U->n_nodes > 0xFFFFFFFFll) {
+            set_error("ctg_merge_overlaps: more than 2^32 distinct labels");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        src = dense.dense;
+    }
+    DevBuf<uint64_t> key((size_t)n * 8);
+    if (!key) return hip_status(hipErrorOutOfMemory, "ctg_merge_overlaps");
+    CTG_CHECK(launch_overlap_pack(n, src, key, s));
+    if ((rc = hip_status(overlap_reduce(w, key, dc, n, s, r.get()), "ctg_merge_overlaps")) != CTG_OK) return rc;
+    CTG_CHECK(dense.map_back(r.get(), s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    r->n_records = n;
+    return c.end(false, out);
+}
+
+int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_end, uint64_t* out_labels,
+                     uint64_t* out_counts, int mem, void* stream) {
+    DevLock dev_lock;
+    if (!r || label_end < label_begin || (label_end > label_begin && !out_labels)) {
+        set_error("ctg_max_overlaps: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (!r->counts || (r->n_nodes > 0 && !r->row_off)) {
+        set_error("ctg_max_overlaps: not an overlaps result (ctg_label_overlaps, ctg_merge_overlaps)");
+        return CTG_ERR_ARG;
+    }
+    const uint64_t n = label_end - label_begin;
+    if (n == 0) return CTG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    DenseOut<uint64_t> ol, oc;
+    int rc = hip_status(ol.open(out_labels, n * 8, mem, true, s), "ctg_max_overlaps");
+    if (!rc) rc = hip_status(oc.open(out_counts, n * 8, mem, true, s), "ctg_max_overlaps");
+    if (rc) return rc;
+    CTG_CHECK(launch_overlap_argmax(r, label_begin, label_end, ol.d, oc.d, s));
+    CTG_CHECK(ol.copy_back(s));
+    CTG_CHECK(oc.copy_back(s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
+
+int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, const int64_t* begin, const int64_t* end,
+                   const int64_t* origin, int mem, void* stream, ctg_result** out) {
+    const char* who = "ctg_morphology";
+    ApiCall c;
+    if (!labels || !shape || !out) {
+        set_error("ctg_morphology: null argument");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (label_bits != 32 && label_bits != 64) {
+        set_error("ctg_morphology: label_bits must be 32 or 64");
+        return CTG_ERR_ARG;
+    }
+    CallBox box;
+    int64_t o[3];
+    int rc = box_of(who, shape, begin, end, TABLE_MAX_VOXELS, &box);
+    if (rc) return rc;
+    const int64_t *b = box.b, *e = box.e;
+    for (int k = 0; k < 3; ++k) {
+        o[k] = origin ? origin[k] : 0;
+        // a coordinate below 2^31 and fewer than 2^32 voxels: no sum reaches 2^63
+        if (o[k] < 0 || o[k] >= (1ll << 31) || o[k] + e[k] >= (1ll << 31)) {
+            set_error("ctg_morphology: origin + end must stay below 2^31 on every axis (origin >= 0)");
+            return CTG_ERR_ARG;
+        }
+    }
+    if ((rc = c.begin(stream, empty_morphology)) != CTG_OK) return rc;
+    if (box.voxels == 0) return c.end(false, out);
+    Workspace& w = c.w();
+    hipStream_t s = c.s;
+    ctg_result* r = c.r.get();
+    const int64_t V = shape[0] * shape[1] * shape[2];
+    const void* dl = nullptr;
+    if ((rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl)) != CTG_OK) return rc;
+    unsigned over = 0;
+    if ((rc = hip_status(morph_tables(w, dl, label_bits, shape, b, e, o, s, r, &over), who)) != CTG_OK) return rc;
+    if (over) {
+        // labels >= 2^32 do not fit the table's 32-bit keys.  1: the labels
+        // become monotone dense ids (2: no ignore label here)
+        DenseSide d;
+        if ((rc = d.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
+        // 3: the scan runs again on the ids
+        unsigned again = 0;
+        if ((rc = hip_status(morph_tables(w, d.ids.p, 32, shape, b, e, o, s, r, &again), who)) != CTG_OK) return rc;
+        // 4: which cannot overflow
+        if (again) {
+            set_error("ctg_morphology: dense ids past 2^32");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        // 5: the sorted ids map back to labels
+        CTG_CHECK(launch_gather_labels(d.U->nodes, r->nodes, r->n_nodes, s));
+    }
+    return c.end(true, out, true);
+}
+
+int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
+    ApiCall c;
+    if (!out || n < 0 || (n > 0 && !rows)) {
+        set_error("ctg_merge_morphology: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (n >= 0xFFFFFFFFll) {
+        set_error("ctg_merge_morphology: 2^32 rows or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    int rc = c.begin(stream, empty_morphology);
+    if (rc) return rc;
+    if (n == 0) return c.end(false, out);
+    hipStream_t s = c.s;
+    DevInput<double> dr;
+    if ((rc = dr.put(rows, (size_t)n * CTG_MORPH_COLS * 8, mem, s, "ctg_merge_morphology")) != CTG_OK) return rc;
+    int bad = 0;
+    if ((rc = hip_status(morph_merge(c.w(), dr, n, s, c.r.get(), &bad), "ctg_merge_morphology")) != CTG_OK) return rc;
+    if (bad) {
+        set_error("ctg_merge_morphology: a row's id is not an integer in [0, 2^53), or its size, centre or box is "
+                  "negative or not finite");
+        return CTG_ERR_ARG;
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    return c.end(false, out);
+}
+
+int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end, double* out, double* rows,
+                        int mem, void* stream) {
+    DevLock dev_lock;
+    if (!r || label_end < label_begin) {
+        set_error("ctg_morphology_rows: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (!r->moments) {
+        set_error("ctg_morphology_rows: not a morphology result (ctg_morphology, ctg_merge_morphology)");
+        return CTG_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = r->n_nodes;
+    if (N > 0) {   // the id column is a float64: the largest label (the last: nodes ascend) must fit it
+        uint64_t top = 0;
+        CTG_CHECK(hipMemcpyAsync(&top, r->nodes + (N - 1), 8, hipMemcpyDeviceToHost, s));
+        CTG_CHECK(hipStreamSynchronize(s));
+        if (top >= (1ull << 53)) {
+            set_error("ctg_morphology_rows: a label of 2^53 or more does not fit the float64 id column "
+                      "(ctg_result_copy_moments holds any label)");
+            return CTG_ERR_UNSUPPORTED;
+        }
+    }
+    const uint64_t n = label_end - label_begin;
+    if (n > (1ull << 40)) {
+        set_error("ctg_morphology_rows: label range too large");
+        return CTG_ERR_ARG;
+    }
+    DenseOut<double> od, orw;
+    int rc = hip_status(od.open(out, (size_t)n * CTG_MORPH_COLS * 8, mem, true, s), "ctg_morphology_rows");
+    if (!rc) rc = hip_status(orw.open(rows, (size_t)N * CTG_MORPH_COLS * 8, mem, false, s), "ctg_morphology_rows");
+    if (rc) return rc;
+    if (!od.d && !orw.d) return CTG_OK;
+    CTG_CHECK(launch_morph_rows(r, label_begin, label_end, od.d, orw.d, s));
+    CTG_CHECK(od.copy_back(s));
+    CTG_CHECK(orw.copy_back(s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
+
+}  // extern "C"

@@ -158,18 +158,9 @@ __host__ __device__ inline uint32_t bloom_block(uint32_t owner, uint32_t block_m
 __host__ __device__ inline uint32_t bloom_word(uint32_t block, uint64_t h) { return block + ((uint32_t)(h >> 40) & 7u); }
 
 // ---------------------------------------------------------------------------
-// records: the face scan flushes one record per (tile, edge)
+// records: the face scan flushes one record per (tile, edge), into the NREG
+// regions of the record buffer (NREG, RegionPrefix: ctg_plan.h)
 // ---------------------------------------------------------------------------
-// The scan reserves record slots from NREG region counters (region r owns
-// slots [r*rcap, (r+1)*rcap)) instead of one global counter: same-address
-// device atomics serialize (~25 ns each), and one counter per flush across
-// every workgroup of the chip was a measurable queue.
-constexpr int NREG = 64;
-
-struct RegionPrefix {          // exclusive prefix of the region counts (host-computed)
-    uint32_t off[NREG + 1];
-};
-
 struct RecordBuf {
     uint64_t* key = nullptr;      // (u << 32) | v
     double2* sums = nullptr;      // wide records: (sum, sum of squares); compact: unused (in the body)
@@ -178,17 +169,7 @@ struct RecordBuf {
     int64_t rcap = 0;             // slots per region (cap / NREG)
 };
 
-// one array of a batched call (ctg_rag_blocks): the host's ctg_block_desc
-// in device memory plus the tile bookkeeping of the launch
-struct BlockGeom {
-    int64_t label_offset;    // element offset of the array in the labels arena
-    int64_t data_offset;     // element offset in the data arena (affinities: channel 0 of C x V)
-    int32_t shape[3];
-    int32_t own_begin[3], own_end[3];
-    int32_t graph_begin[3], graph_end[3];
-    int32_t ntx, nty, ntz;   // tiles along x, y, z
-};
-
+// (BlockGeom, one array of a batched call: ctg_plan.h)
 struct ScanParams {
     const void* labels;
     const void* data;          // boundary (Z,Y,X) or affinities (C,Z,Y,X); may be null

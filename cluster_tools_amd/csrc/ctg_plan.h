@@ -1,13 +1,17 @@
-// The host layer's decisions as pure functions: tile depths, the channel
-// classification, the choice between the record-sort paths and the key range
-// of the bucket sort.  Plain C++17 -- no HIP, no getenv: the environment
-// switches are read by the callers and passed in as values -- so a host
-// program can exercise them without a GPU (tools/plan_check.cpp,
+// The host layer's decisions as pure functions: call boxes, tile depths, the
+// batched-block plan, record-buffer and candidate-buffer sizes, the Bloom
+// filter's size, the narrow-row mode, the channel classification, the
+// adjacency rule of the reduce, the count-matrix sums of the multi-GPU
+// exchange, the choice between the record-sort paths and the key range of the
+// bucket sort.  Plain C++17 -- no HIP, no getenv: the environment switches are
+// read by the callers (scan_switches, sort_switches) and passed in as values --
+// so a host program can exercise them without a GPU (tools/plan_check.cpp,
 // tests/test_plan.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/ctg.h"
 
@@ -19,6 +23,34 @@ inline int bits_for(uint64_t v) {
     int b = 1;
     while (b < 64 && (v >> b)) ++b;
     return b;
+}
+inline int bits_u(int64_t v) { return v <= 0 ? 0 : bits_for((uint64_t)v); }
+
+// ---------------------------------------------------------------------------
+// the box of a call
+// ---------------------------------------------------------------------------
+struct CallBox {
+    enum Error { OK, OUTSIDE, TOO_LARGE } error;
+    int64_t b[3], e[3];
+    int64_t voxels;
+};
+
+// [b, e) of a call on an array of `shape`: begin / end default to the whole
+// array and the box must lie inside it (checked on every axis first); then, with
+// max_voxels > 0, it must hold fewer than max_voxels voxels
+inline CallBox call_box(const int64_t* shape, const int64_t* begin, const int64_t* end, int64_t max_voxels) {
+    CallBox c{};
+    for (int k = 0; k < 3; ++k) {
+        c.b[k] = begin ? begin[k] : 0;
+        c.e[k] = end ? end[k] : shape[k];
+        if (shape[k] < 0 || c.b[k] < 0 || c.e[k] > shape[k] || c.b[k] > c.e[k]) {
+            c.error = CallBox::OUTSIDE;
+            return c;
+        }
+    }
+    c.voxels = (c.e[0] - c.b[0]) * (c.e[1] - c.b[1]) * (c.e[2] - c.b[2]);
+    c.error = max_voxels > 0 && c.voxels >= max_voxels ? CallBox::TOO_LARGE : CallBox::OK;
+    return c;
 }
 
 // ---------------------------------------------------------------------------
@@ -58,6 +90,192 @@ inline TileDepths scan_tile_depths(const int64_t* shape, int64_t rows_wide, int6
     int tzn = std::min(tz, NARROW_TILE_Z);
     while (tzn < tz && cols_n * ((shape[0] + tzn - 1) / tzn) > 65536) tzn *= 2;
     return {tz, tzn};
+}
+
+// boundary maps of fragmented volumes scan with 1-row waves.  0: wide tiles;
+// 1: narrow; 2: the sampled x-face density decides on the device.  The probe
+// and the second launch cost ~0.1 ms, so volumes below 2^28 voxels (~645^3,
+// steps of ~2 ms) keep the wide tiles.  nr_switch: CTG_NARROW_ROWS, 0 / 1
+// forces a width (at any size), -1 unset
+inline int narrow_rows_mode(bool boundary_map, int64_t V, int nr_switch) {
+    if (!boundary_map || (V < (1ll << 28) && nr_switch < 0)) return 0;
+    return nr_switch < 0 ? 2 : (nr_switch ? 1 : 0);
+}
+
+// ---------------------------------------------------------------------------
+// batched blocks (ctg_rag_blocks)
+// ---------------------------------------------------------------------------
+// one array of a batched call: the host's ctg_block_desc in device memory plus
+// the tile bookkeeping of the launch
+struct BlockGeom {
+    int64_t label_offset;    // element offset of the array in the labels arena
+    int64_t data_offset;     // element offset in the data arena (affinities: channel 0 of C x V)
+    int32_t shape[3];
+    int32_t own_begin[3], own_end[3];
+    int32_t graph_begin[3], graph_end[3];
+    int32_t ntx, nty, ntz;   // tiles along x, y, z
+};
+
+struct BlockPlan {
+    // BOX_OUTSIDE / ARRAY_OUTSIDE: of block bad_block, the first such block (its
+    // box is checked before its place in the arenas); TOO_MANY_TILES: every
+    // block is fine but one of the two launches would pass 2^31 - 1 tiles
+    enum Error { OK, BOX_OUTSIDE, ARRAY_OUTSIDE, TOO_MANY_TILES } error = OK;
+    int bad_block = -1;
+    int64_t own_voxels = 0, voxels = 0;   // over all blocks: owned boxes, arrays
+    int tile_z = 0;                       // planes per workgroup: one tile deep for the usual <= 128-plane blocks
+    // keys carry the block in the bits of u from tag_shift up (32: no tag);
+    // label_hi_mask: the bits a label must not have
+    int tag_bits = 0, tag_shift = 32;
+    uint32_t label_hi_mask = 0;
+    std::vector<BlockGeom> geom;
+    std::vector<uint32_t> prefix;    // tiles of the scan launch before block b
+    std::vector<uint32_t> uprefix;   // tiles of the node launch (64 x unique_rows x 16 voxels of the owned box)
+};
+
+// has_data: a data arena is given (else data offsets are not looked at and are
+// 0 in the geometry); max_x: the widest array the scan takes; scan_rows /
+// unique_rows: y rows of a scan / node tile; tile_z_switch: CTG_TILE_Z, 0 unset
+inline BlockPlan plan_blocks(const ctg_block_desc* blocks, int n_blocks, bool has_data, int n_channels,
+                             int64_t labels_len, int64_t data_len, int64_t max_x, int scan_rows, int unique_rows,
+                             int tile_z_switch) {
+    BlockPlan p;
+    const int nch = has_data ? std::max(1, n_channels) : 0;
+    int64_t zmax = 1;
+    for (int b = 0; b < n_blocks; ++b) {
+        const ctg_block_desc& d = blocks[b];
+        int64_t V = 1, ov = 1;
+        p.bad_block = b;
+        for (int k = 0; k < 3; ++k) {
+            V *= d.shape[k];
+            if (d.shape[k] < 0 || d.shape[k] > (k == 2 ? max_x : 0x7FFFFFFF) || d.own_begin[k] < 0 ||
+                d.own_end[k] > d.shape[k] || d.graph_begin[k] < 0 || d.graph_end[k] > d.shape[k]) {
+                p.error = BlockPlan::BOX_OUTSIDE;
+                return p;
+            }
+        }
+        if (d.label_offset < 0 || d.label_offset + V > labels_len ||
+            (has_data && (d.data_offset < 0 || d.data_offset + V * nch > data_len))) {
+            p.error = BlockPlan::ARRAY_OUTSIDE;
+            return p;
+        }
+        for (int k = 0; k < 3; ++k) ov *= std::max<int64_t>(0, d.own_end[k] - d.own_begin[k]);
+        p.own_voxels += ov;
+        p.voxels += V;
+        zmax = std::max(zmax, d.shape[0]);
+    }
+    p.bad_block = -1;
+    p.tile_z = tile_z_switch > 0 ? tile_z_switch : (int)std::min<int64_t>(zmax, 128);
+    p.tag_bits = bits_u(n_blocks - 1);
+    p.tag_shift = 32 - p.tag_bits;
+    p.label_hi_mask = p.tag_bits ? ~((1u << p.tag_shift) - 1u) : 0u;
+    p.geom.resize(n_blocks);
+    p.prefix.assign(n_blocks + 1, 0);
+    p.uprefix.assign(n_blocks + 1, 0);
+    for (int b = 0; b < n_blocks; ++b) {
+        const ctg_block_desc& d = blocks[b];
+        BlockGeom& g = p.geom[b];
+        g.label_offset = d.label_offset;
+        g.data_offset = has_data ? d.data_offset : 0;
+        int64_t oe[3];
+        for (int k = 0; k < 3; ++k) {
+            g.shape[k] = (int32_t)d.shape[k];
+            g.own_begin[k] = (int32_t)d.own_begin[k];
+            g.own_end[k] = (int32_t)d.own_end[k];
+            g.graph_begin[k] = (int32_t)d.graph_begin[k];
+            g.graph_end[k] = (int32_t)d.graph_end[k];
+            oe[k] = std::max<int64_t>(0, d.own_end[k] - d.own_begin[k]);
+        }
+        g.ntx = (int32_t)((d.shape[2] + TILE_X - 1) / TILE_X);
+        g.nty = (int32_t)((d.shape[1] + scan_rows - 1) / scan_rows);
+        g.ntz = (int32_t)((d.shape[0] + p.tile_z - 1) / p.tile_z);
+        const int64_t nt = (int64_t)g.ntx * g.nty * g.ntz;
+        const int64_t ut = ((oe[2] + 63) / 64) * ((oe[1] + unique_rows - 1) / unique_rows) * ((oe[0] + 15) / 16);
+        if ((int64_t)p.prefix[b] + nt > 0x7FFFFFFFll || (int64_t)p.uprefix[b] + ut > 0x7FFFFFFFll) {
+            p.error = BlockPlan::TOO_MANY_TILES;
+            return p;
+        }
+        p.prefix[b + 1] = p.prefix[b] + (uint32_t)nt;
+        p.uprefix[b + 1] = p.uprefix[b] + (uint32_t)ut;
+    }
+    return p;
+}
+
+// ---------------------------------------------------------------------------
+// records: the face scan flushes one record per (tile, edge)
+// ---------------------------------------------------------------------------
+// The scan reserves record slots from NREG region counters (region r owns
+// slots [r*rcap, (r+1)*rcap)) instead of one global counter: same-address
+// device atomics serialize (~25 ns each), and one counter per flush across
+// every workgroup of the chip was a measurable queue.
+constexpr int NREG = 64;
+
+struct RegionPrefix {          // exclusive prefix of the region counts (host-computed)
+    uint32_t off[NREG + 1];
+};
+
+// record slots a scan of V voxels starts with (cap: the slots the workspace
+// holds already), a multiple of NREG
+inline int64_t record_slots_first(int64_t cap, int64_t V) {
+    const int64_t need = std::max<int64_t>(cap, std::max<int64_t>(1 << 16, V / 24));
+    return (need + NREG - 1) / NREG * NREG;
+}
+// ... and after an overflow, from the fullest region's count
+inline int64_t record_slots_regrow(uint64_t fullest) { return ((int64_t)(fullest * 5 / 4) + 1024) * NREG; }
+
+struct RegionFold {
+    RegionPrefix pre;
+    uint64_t total, fullest;
+};
+// the NREG region counts of a scan -> their exclusive prefix (32 bits: the
+// caller refuses totals of 2^32), their sum and their maximum
+inline RegionFold fold_regions(const unsigned long long* rcount) {
+    RegionFold f{};
+    for (int r = 0; r < NREG; ++r) {
+        f.pre.off[r] = (uint32_t)f.total;
+        f.total += rcount[r];
+        f.fullest = std::max<uint64_t>(f.fullest, rcount[r]);
+    }
+    f.pre.off[NREG] = (uint32_t)f.total;
+    return f;
+}
+
+// unique-label candidates (per tile and flush, so a label repeats): the buffer
+// a pass over n voxels starts with, and after a pass that counted m > capacity
+// candidates; bound: what the regrown buffer never needs to pass
+inline int64_t candidate_cap_first(int64_t n) {
+    return std::max<int64_t>(1, std::min<int64_t>(n, std::max<int64_t>(1 << 16, n / 8)));
+}
+inline int64_t candidate_cap_regrow(int64_t m, int64_t bound) { return std::min<int64_t>(bound, m + 1024); }
+
+// 64-byte blocks of the Bloom filter of n_edges RAG edges: 24 bits per stored
+// direction (48 per edge; 32: +3 % records, 12-channel scan +0.5 ms,
+// profiles/r4/tz), a power of two, 128 at least
+inline uint32_t bloom_blocks(int64_t n_edges) {
+    const int64_t bits = n_edges * 48;
+    uint32_t blocks = 128;
+    while ((int64_t)blocks * 512 < bits) blocks *= 2;
+    return blocks;
+}
+
+// ---------------------------------------------------------------------------
+// the multi-GPU exchange's count matrix: counts_all[(src * world + dst) * 2]
+// rows and [.. + 1] nodes of src's table that dst owns
+// ---------------------------------------------------------------------------
+struct ExchangeCounts {
+    int64_t rows, nodes;   // of this rank's table, over all destinations
+    int64_t words;         // u64 words this rank sends (pack) / receives (merge)
+};
+inline ExchangeCounts exchange_counts(const int64_t* counts_all, int world, int rank, int row_words, bool receive) {
+    ExchangeCounts c{};
+    for (int d = 0; d < world; ++d) {
+        const int64_t* mine = counts_all + ((int64_t)rank * world + d) * 2;
+        const int64_t* other = receive ? counts_all + ((int64_t)d * world + rank) * 2 : mine;
+        c.rows += mine[0];
+        c.nodes += mine[1];
+        if (d != rank) c.words += other[0] * row_words + other[1];
+    }
+    return c;
 }
 
 // ---------------------------------------------------------------------------
@@ -116,6 +334,19 @@ inline ChannelPlan plan_channels(const ChannelClass& cc, int n_channels, bool ad
     p.nn_mix = faces && cc.long_range && have_bloom;
     return p;
 }
+
+// What the reduce asks of a key before it is an edge.  0: nothing (boundary
+// maps, graphs, and affinities whose nearest-neighbour channels prove every
+// edge); 1: some record of the key carries the ADJ bit (also: drop the Bloom
+// filter's false positives); 2: the same, decided after a merge
+// (CTG_NO_ADJ_FILTER: a partial table)
+inline int need_adj_whole(int n_channels, bool skip_adj_marks, bool adj_filter, bool have_bloom) {
+    if (have_bloom) return 1;
+    return n_channels > 0 && !skip_adj_marks ? (adj_filter ? 1 : 2) : 0;
+}
+// batched blocks.  boundary / graph: every key is a face of the block's graph
+// box; affinities: keep the keys of the block's sub-graph (ADJ marks)
+inline int need_adj_blocks(int n_channels) { return n_channels > 0 ? 1 : 0; }
 
 // ---------------------------------------------------------------------------
 // record sort

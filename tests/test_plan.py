@@ -1,5 +1,6 @@
-"""The host layer's decisions (csrc/ctg_plan.h: tile depths, record-sort path,
-channel classes, bucket key range) are pure functions; tools/plan_check.cpp
+"""The host layer's decisions (csrc/ctg_plan.h: call boxes, tile depths, the
+batched-block plan, buffer sizes, channel classes, record-sort path, bucket
+key range, ...) are pure functions; tools/plan_check.cpp
 drives them on the CPU -- built with the host compiler and
 -fsanitize=address,undefined -- and its answers are compared with the tables
 below (no GPU, no library)."""
@@ -188,3 +189,206 @@ def test_packed_key_range(plan):
              (70000, 100000, 17, 23), (1, 1, 1, 1), (3, (1 << 20) - 1, 20, 23)]
     got = plan(['range %d %d %d %d' % c for c in cases])
     assert [tuple(map(int, g.split())) for g in got] == [_key_range(*c) for c in cases]
+
+
+# ---------------------------------------------------------------------------
+# the host decisions of the face-scan entry points.  The expected values are
+# worked by hand or by the arithmetic restated here in Python, never printed
+# from the code under test.
+# ---------------------------------------------------------------------------
+def _box(shape, begin=None, end=None, max_voxels=0):
+    b, e = begin or (0, 0, 0), end or (0, 0, 0)
+    return 'box %d %d %d %d %d %d %d %d %d %d %d %d' % (tuple(shape) + (int(begin is not None),) + tuple(b) +
+                                                        (int(end is not None),) + tuple(e) + (max_voxels,))
+
+
+def test_call_box(plan):
+    cap = (1 << 32) - 1
+    ok = [(_box((4, 5, 6)), (0, 0, 0, 4, 5, 6, 120)),
+          (_box((4, 5, 6), begin=(1, 2, 3)), (1, 2, 3, 4, 5, 6, 3 * 3 * 3)),
+          (_box((4, 5, 6), end=(2, 5, 1)), (0, 0, 0, 2, 5, 1, 10)),
+          (_box((4, 5, 6), begin=(1, 2, 3), end=(1, 5, 6)), (1, 2, 3, 1, 5, 6, 0)),       # an empty box is a box
+          (_box((0, 5, 6)), (0, 0, 0, 0, 5, 6, 0)),
+          (_box((3, 5, 286331153), max_voxels=0), (0, 0, 0, 3, 5, 286331153, cap)),       # no cap
+          (_box((3, 5, 286331152), max_voxels=cap), (0, 0, 0, 3, 5, 286331152, cap - 15))]
+    for q, exp in ok:
+        assert tuple(map(int, plan([q])[0].split())) == (0,) + exp, q
+    outside = [_box((4, -5, 6)), _box((4, 5, 6), begin=(0, -1, 0)), _box((4, 5, 6), end=(4, 5, 7)),
+               _box((4, 5, 6), begin=(3, 0, 0), end=(2, 5, 6)),
+               _box((1 << 11, 1 << 11, 1 << 10), end=(1 << 11, 1 << 11, (1 << 10) + 1), max_voxels=cap)]
+    assert [int(a.split()[0]) for a in plan(outside)] == [1] * len(outside)
+    too_large = [_box((3, 5, 286331153), max_voxels=cap), _box((1 << 11, 1 << 11, 1 << 10), max_voxels=cap)]
+    assert [int(a.split()[0]) for a in plan(too_large)] == [2, 2]
+
+
+MAX_X = 1 << 30     # (the scan's own limit is the caller's: any value above the shapes used here)
+UNIQUE_ROWS = 8
+
+
+def _blk(shape, label_offset=0, data_offset=0, own=None, graph=None):
+    own = own or ((0, 0, 0), shape)
+    graph = graph or ((0, 0, 0), shape)
+    return dict(shape=shape, label_offset=label_offset, data_offset=data_offset, own=own, graph=graph)
+
+
+def _blocks_query(blocks, has_data=0, n_channels=0, labels_len=None, data_len=0, max_x=MAX_X, tile_z=0):
+    if labels_len is None:
+        labels_len = max(b['label_offset'] + b['shape'][0] * b['shape'][1] * b['shape'][2] for b in blocks)
+    q = ['blocks %d %d %d %d %d %d %d %d %d' % (len(blocks), has_data, n_channels, labels_len, data_len, max_x,
+                                                ROWS_WIDE, UNIQUE_ROWS, tile_z)]
+    for b in blocks:
+        q.append('%d %d' % (b['label_offset'], b['data_offset']))
+        q += ['%d %d %d' % tuple(v) for v in (b['shape'], b['own'][0], b['own'][1], b['graph'][0], b['graph'][1])]
+    return ' '.join(q)
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def _blocks_expected(blocks, tile_z=0):
+    """The parent's inline arithmetic (ctg_rag_blocks), restated."""
+    n = len(blocks)
+    own, vox, zmax = 0, 0, 1
+    for blk in blocks:
+        o = 1
+        for k in range(3):
+            o *= max(0, blk['own'][1][k] - blk['own'][0][k])
+        own += o
+        vox += blk['shape'][0] * blk['shape'][1] * blk['shape'][2]
+        zmax = max(zmax, blk['shape'][0])
+    tz = tile_z if tile_z else min(zmax, 128)
+    tag_bits = 0 if n - 1 <= 0 else max(1, (n - 1).bit_length())
+    shift = 32 - tag_bits
+    mask = (0xFFFFFFFF & ~((1 << shift) - 1)) if tag_bits else 0
+    prefix, uprefix, tiles = [0], [0], []
+    for blk in blocks:
+        z, y, x = blk['shape']
+        t = (_ceil(x, 64), _ceil(y, ROWS_WIDE), _ceil(z, tz))
+        oe = [max(0, blk['own'][1][k] - blk['own'][0][k]) for k in range(3)]
+        prefix.append(prefix[-1] + t[0] * t[1] * t[2])
+        uprefix.append(uprefix[-1] + _ceil(oe[2], 64) * _ceil(oe[1], UNIQUE_ROWS) * _ceil(oe[0], 16))
+        tiles += list(t)
+    return [0, own, vox, tz, tag_bits, shift, mask] + prefix + uprefix + tiles
+
+
+def test_block_plan_tables(plan):
+    a = _blk((10, 40, 50), own=((1, 0, 0), (10, 40, 50)))
+    b = _blk((11, 33, 70), label_offset=20000, own=((1, 1, 1), (11, 33, 70)), graph=((0, 0, 0), (11, 33, 70)))
+    c = _blk((200, 65, 129), label_offset=45410)                       # shape[0] above 128: two tiles deep
+    empty = _blk((4, 9, 9), label_offset=45410 + 200 * 65 * 129, own=((2, 3, 3), (2, 9, 9)))   # an empty owned box
+    cases = [[a], [a, b], [a, b, c], [a, b, c, empty], [empty]]
+    got = plan([_blocks_query(bl) for bl in cases])
+    for bl, g in zip(cases, got):
+        assert [int(v) for v in g.split()] == _blocks_expected(bl), bl
+    # by hand: one block has no tag; 2 and 3 blocks take 1 and 2 tag bits
+    one, two, three = ([int(v) for v in g.split()] for g in got[:3])
+    assert one[1:7] == [9 * 40 * 50, 10 * 40 * 50, 10, 0, 32, 0]
+    assert one[7:] == [0, 2,  0, 1 * 5 * 1,  1, 2, 1]     # 50 -> 1 x tile, 40 -> 2 y tiles of 32; own 9 x 40 x 50
+    assert two[3:7] == [11, 1, 31, 0x80000000] and three[3:7] == [128, 2, 30, 0xC0000000]
+    assert three[7:11] == [0, 2, 2 + 2 * 2 * 1, 6 + 3 * 3 * 2]         # 200 planes in tiles of 128: 2 deep
+    four = [int(v) for v in got[3].split()]
+    assert four[12 + 4] == four[12 + 3]                                # the empty owned box adds no node tile
+    # CTG_TILE_Z
+    g = plan([_blocks_query([a, b, c], tile_z=7)])[0]
+    assert [int(v) for v in g.split()] == _blocks_expected([a, b, c], tile_z=7)
+    assert int(g.split()[3]) == 7
+
+
+def test_block_plan_errors(plan):
+    ok = _blk((2, 4, 8))
+    outside = [_blk((2, -4, 8)), _blk((2, 4, 8), own=((0, -1, 0), (2, 4, 8))), _blk((2, 4, 8), own=((0, 0, 0), (3, 4, 8))),
+               _blk((2, 4, 8), graph=((-1, 0, 0), (2, 4, 8))), _blk((2, 4, 8), graph=((0, 0, 0), (2, 5, 8))),
+               _blk((2, 4, MAX_X + 1), own=((0, 0, 0), (0, 0, 0)), graph=((0, 0, 0), (0, 0, 0)))]
+    got = plan([_blocks_query([ok, ok, bad], labels_len=64) for bad in outside])
+    assert got == ['1 2'] * len(outside)
+    arena = [dict(blocks=[ok, _blk((2, 4, 8), label_offset=-1)], labels_len=64),
+             dict(blocks=[ok, _blk((2, 4, 8), label_offset=1)], labels_len=64),
+             dict(blocks=[ok, _blk((2, 4, 8), data_offset=-1)], labels_len=64, has_data=1, data_len=64),
+             dict(blocks=[ok, ok], labels_len=64, has_data=1, data_len=63),
+             dict(blocks=[ok, ok], labels_len=64, has_data=1, n_channels=3, data_len=191)]
+    got = plan([_blocks_query(**kw) for kw in arena])
+    assert got == ['2 1', '2 1', '2 1', '2 0', '2 0']
+    # without a data arena the data offsets are not looked at; the box before the arena; blocks in order
+    fine = plan([_blocks_query([_blk((2, 4, 8), data_offset=-5)], labels_len=64)])[0]
+    assert fine.split()[0] == '0'
+    both = _blk((2, 4, 8), label_offset=-1, own=((0, 0, 0), (3, 4, 8)))
+    assert plan([_blocks_query([both], labels_len=64),
+                 _blocks_query([_blk((2, 4, 8), label_offset=1), both], labels_len=64)]) == ['1 0', '2 0']
+    # 2^31 - 1 tiles fit one launch, one more does not (x tiles of 64: 2^24 - 1 wide tiles a row)
+    wide = _blk((128, 32, 64 * ((1 << 24) - 1)), own=((0, 0, 0), (0, 0, 0)))
+    many = [wide] * 128                                                  # 2^31 - 128 tiles
+    row = _blk((127, 32, 64), own=((0, 0, 0), (0, 0, 0)))               # one tile each
+    lens = dict(labels_len=1 << 62, max_x=1 << 40)
+    got = plan([_blocks_query(many + [row] * 127, **lens), _blocks_query(many + [row] * 128, **lens)])
+    assert got[0].split()[0] == '0' and got[1].split()[0] == '3'
+
+
+def test_record_and_candidate_sizes(plan):
+    V0 = 24 << 16                                                        # V / 24 = 2^16: the floor
+    q = ['recfirst 0 0', 'recfirst 0 %d' % (V0 - 24), 'recfirst 0 %d' % V0, 'recfirst 0 %d' % (V0 + 24),
+         'recfirst 0 %d' % (V0 + 24 * 64), 'recfirst 100000 %d' % V0, 'recfirst 0 %d' % (512 ** 3),
+         'recgrow 0', 'recgrow 1000', 'recgrow 1001', 'recgrow 4000000',
+         'cand 0', 'cand 1', 'cand 65535', 'cand 65536', 'cand 524288', 'cand 524296', 'cand 8000000',
+         'candgrow 70000 9223372036854775807', 'candgrow 70000 70500', 'candgrow 70000 80000']
+    exp = [65536, 65536, 65536, 65600, 65600, 100032, 5592448,           # rounded up to a multiple of 64
+           1024 * 64, (1250 + 1024) * 64, (1251 + 1024) * 64, (5000000 + 1024) * 64,
+           1, 1, 65535, 65536, 65536, 65537, 1000000,
+           71024, 70500, 71024]
+    assert [int(v) for v in plan(q)] == exp
+    assert 5592448 == _ceil(512 ** 3 // 24, 64) * 64 and 100032 == _ceil(100000, 64) * 64
+
+
+def test_bloom_blocks(plan):
+    """48 bits an edge in 512-bit blocks, a power of two, 128 blocks at least:
+    128 * 512 / 48 = 1365.33 edges fill the floor."""
+    ns = [0, 1, 1365, 1366, 2730, 2731, 1000000]
+    exp = []
+    for n in ns:
+        blocks = 128
+        while blocks * 512 < n * 48:
+            blocks *= 2
+        exp.append(blocks)
+    assert exp[:6] == [128, 128, 128, 256, 256, 512] and exp[6] == 131072
+    assert [int(v) for v in plan(['bloom %d' % n for n in ns])] == exp
+
+
+def test_narrow_rows_and_need_adj(plan):
+    big = 1 << 28
+    q = ['narrow 1 %d -1' % (big - 1), 'narrow 1 %d -1' % big, 'narrow 0 %d -1' % big, 'narrow 0 %d 1' % big,
+         'narrow 1 1000 0', 'narrow 1 1000 1', 'narrow 1 %d 0' % big, 'narrow 1 %d 1' % big, 'narrow 1 1000 5']
+    assert [int(v) for v in plan(q)] == [0, 2, 0, 0, 0, 1, 0, 1, 1]
+    # need_adj of a whole array: n_channels, skip_adj_marks, adj_filter, have_bloom
+    q = ['adj 0 0 1 0', 'adj 3 1 1 0', 'adj 3 0 1 0', 'adj 3 0 0 0', 'adj 12 1 1 1', 'adj 12 0 1 1', 'adj 0 0 0 0',
+         'adjblocks 0', 'adjblocks 3']
+    assert [int(v) for v in plan(q)] == [0, 0, 1, 2, 1, 1, 0, 0, 1]
+
+
+def test_fold_regions(plan):
+    rc = [(7 * r * r + 3) % 1000 for r in range(64)]
+    rc[5] = 0
+    rc[40] = 123456
+    big = [1 << 26] * 64                                                 # total 2^32: the prefix wraps, the total does not
+    got = plan(['fold ' + ' '.join(map(str, c)) for c in (rc, [0] * 64, big)])
+    for c, g in zip((rc, [0] * 64, big), got):
+        v = [int(x) for x in g.split()]
+        off = [sum(c[:r]) & 0xFFFFFFFF for r in range(65)]
+        assert v == [sum(c), max(c)] + off
+    assert int(got[2].split()[0]) == 1 << 32 and int(got[2].split()[-1]) == 0
+
+
+def test_exchange_counts(plan):
+    world, row_words = 3, 28
+    counts = [[(10 * s + d + 1, 100 * s + 7 * d) for d in range(world)] for s in range(world)]    # [src][dst]: rows, nodes
+    flat = ' '.join('%d %d' % counts[s][d] for s in range(world) for d in range(world))
+    q, exp = [], []
+    for rank in range(world):
+        rows = sum(counts[rank][d][0] for d in range(world))
+        nodes = sum(counts[rank][d][1] for d in range(world))
+        send = sum(counts[rank][d][0] * row_words + counts[rank][d][1] for d in range(world) if d != rank)
+        recv = sum(counts[s][rank][0] * row_words + counts[s][rank][1] for s in range(world) if s != rank)
+        q += ['xchg %d %d %d 0 %s' % (world, rank, row_words, flat), 'xchg %d %d %d 1 %s' % (world, rank, row_words, flat)]
+        exp += [(rows, nodes, send), (rows, nodes, recv)]
+    assert [tuple(map(int, g.split())) for g in plan(q)] == exp
+    assert exp[0] == (1 + 2 + 3, 0 + 7 + 14, (2 + 3) * 28 + 7 + 14)      # rank 0 by hand
+    assert plan(['xchg 1 0 28 0 5 9', 'xchg 1 0 28 1 5 9']) == ['5 9 0', '5 9 0']     # one rank: nothing moves

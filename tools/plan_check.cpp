@@ -8,6 +8,23 @@
 //   chan ADJ_FILTER HAVE_BLOOM SKIP_ADJ NN N  z y x ...   (N offsets)
 //        -> lr_mask long_range nn_z nn_y nn_x skip_adj_marks nn3 nn_mix n_loop loop...
 //   range MIN_U MAX_V NB IB                   -> kmin kmax
+//   box SZ SY SX HAS_BEGIN bz by bx HAS_END ez ey ex MAX_VOXELS
+//                                            -> error bz by bx ez ey ex voxels   (error: 0 ok, 1 outside, 2 too large)
+//   blocks N HAS_DATA N_CHANNELS LABELS_LEN DATA_LEN MAX_X SCAN_ROWS UNIQUE_ROWS TILE_Z_SWITCH
+//          then per block: label_offset data_offset shape[3] own_begin[3] own_end[3] graph_begin[3] graph_end[3]
+//        -> error bad_block   (error: 1 box outside, 2 array outside), or
+//           error own_voxels voxels tile_z tag_bits tag_shift label_hi_mask  prefix[N+1]  uprefix[N+1]
+//           ntx nty ntz per block   (error: 0 ok, 3 too many tiles -- the tables up to that block)
+//   recfirst CAP V                           -> record slots of the first scan
+//   recgrow FULLEST                          -> record slots after an overflow
+//   cand N                                   -> first candidate capacity
+//   candgrow M BOUND                         -> regrown candidate capacity
+//   bloom N_EDGES                            -> 64-byte blocks
+//   narrow BOUNDARY_MAP V SWITCH             -> narrow-row mode
+//   adj N_CHANNELS SKIP_MARKS ADJ_FILTER HAVE_BLOOM -> need_adj of a whole-array call
+//   adjblocks N_CHANNELS                     -> need_adj of a batched call
+//   fold r[NREG]                             -> total fullest off[NREG + 1]
+//   xchg WORLD RANK ROW_WORDS RECEIVE counts[WORLD * WORLD * 2] -> rows nodes words
 //
 // g++ -std=c++17 -fsanitize=address,undefined tools/plan_check.cpp -o plan_check
 #include <cinttypes>
@@ -15,6 +32,7 @@
 #include <iostream>
 #include <sstream>
 #include <string>
+#include <vector>
 
 #include "../cluster_tools_amd/csrc/ctg_plan.h"
 
@@ -75,6 +93,83 @@ int main() {
             in >> min_u >> max_v >> nb >> ib;
             const KeyRange r = packed_key_range(min_u, max_v, nb, ib);
             printf("%" PRIu64 " %" PRIu64 "\n", r.kmin, r.kmax);
+        } else if (cmd == "box") {
+            int64_t shape[3], b[3] = {}, e[3] = {}, max_voxels;
+            int has_b, has_e;
+            in >> shape[0] >> shape[1] >> shape[2] >> has_b >> b[0] >> b[1] >> b[2] >> has_e >> e[0] >> e[1] >> e[2] >>
+                max_voxels;
+            const CallBox c = call_box(shape, has_b ? b : nullptr, has_e ? e : nullptr, max_voxels);
+            printf("%d %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 "\n", (int)c.error,
+                   c.b[0], c.b[1], c.b[2], c.e[0], c.e[1], c.e[2], c.voxels);
+        } else if (cmd == "blocks") {
+            int n, has_data, nch, rows, urows, tz;
+            int64_t labels_len, data_len, max_x;
+            in >> n >> has_data >> nch >> labels_len >> data_len >> max_x >> rows >> urows >> tz;
+            std::vector<ctg_block_desc> d(n);
+            for (ctg_block_desc& x : d) {
+                in >> x.label_offset >> x.data_offset;
+                for (int64_t* a : {x.shape, x.own_begin, x.own_end, x.graph_begin, x.graph_end}) in >> a[0] >> a[1] >> a[2];
+            }
+            const BlockPlan p = plan_blocks(d.data(), n, has_data, nch, labels_len, data_len, max_x, rows, urows, tz);
+            if (p.error == BlockPlan::BOX_OUTSIDE || p.error == BlockPlan::ARRAY_OUTSIDE) {
+                printf("%d %d\n", (int)p.error, p.bad_block);
+                continue;
+            }
+            printf("%d %" PRId64 " %" PRId64 " %d %d %d %u ", (int)p.error, p.own_voxels, p.voxels, p.tile_z, p.tag_bits,
+                   p.tag_shift, p.label_hi_mask);
+            for (uint32_t v : p.prefix) printf(" %u", v);
+            printf(" ");
+            for (uint32_t v : p.uprefix) printf(" %u", v);
+            printf(" ");
+            for (const BlockGeom& g : p.geom) printf(" %d %d %d", g.ntx, g.nty, g.ntz);
+            printf("\n");
+        } else if (cmd == "recfirst") {
+            int64_t cap, V;
+            in >> cap >> V;
+            printf("%" PRId64 "\n", record_slots_first(cap, V));
+        } else if (cmd == "recgrow") {
+            uint64_t mx;
+            in >> mx;
+            printf("%" PRId64 "\n", record_slots_regrow(mx));
+        } else if (cmd == "cand") {
+            int64_t n;
+            in >> n;
+            printf("%" PRId64 "\n", candidate_cap_first(n));
+        } else if (cmd == "candgrow") {
+            int64_t m, bound;
+            in >> m >> bound;
+            printf("%" PRId64 "\n", candidate_cap_regrow(m, bound));
+        } else if (cmd == "bloom") {
+            int64_t n;
+            in >> n;
+            printf("%u\n", bloom_blocks(n));
+        } else if (cmd == "narrow") {
+            int boundary, sw;
+            int64_t V;
+            in >> boundary >> V >> sw;
+            printf("%d\n", narrow_rows_mode(boundary, V, sw));
+        } else if (cmd == "adj") {
+            int nch, skip, filter, bloom;
+            in >> nch >> skip >> filter >> bloom;
+            printf("%d\n", need_adj_whole(nch, skip, filter, bloom));
+        } else if (cmd == "adjblocks") {
+            int nch;
+            in >> nch;
+            printf("%d\n", need_adj_blocks(nch));
+        } else if (cmd == "fold") {
+            unsigned long long rc[NREG];
+            for (unsigned long long& r : rc) in >> r;
+            const RegionFold f = fold_regions(rc);
+            printf("%" PRIu64 " %" PRIu64, f.total, f.fullest);
+            for (uint32_t o : f.pre.off) printf(" %u", o);
+            printf("\n");
+        } else if (cmd == "xchg") {
+            int world, rank, row_words, receive;
+            in >> world >> rank >> row_words >> receive;
+            std::vector<int64_t> c((size_t)world * world * 2);
+            for (int64_t& v : c) in >> v;
+            const ExchangeCounts x = exchange_counts(c.data(), world, rank, row_words, receive);
+            printf("%" PRId64 " %" PRId64 " %" PRId64 "\n", x.rows, x.nodes, x.words);
         } else {
             fprintf(stderr, "plan_check: unknown query '%s'\n", cmd.c_str());
             return 2;
