@@ -481,3 +481,43 @@ def merge_feature_stats(parts, n_edges, lo=0.0, hi=1.0, nbins=NBINS):
     vmax[count == 0] = 0.0
     return dict(count=count, sum=ssum, mean=mean, var=var, m2=m2, min=vmin,
                 max=vmax, hist=hist)
+
+
+def merge_feature_rows_exact(ids, rows, id_begin, id_end):
+    """The row merge of ``ctg_merge_feature_rows`` / ``ndist.mergeFeatureBlocks``
+    (reference-layout rows [mean, var, min, q10, q25, q50, q75, q90, max,
+    count], no histograms) in exact rational arithmetic: every float64 is an
+    exact Fraction, and each output is rounded to float64 once, at the end.
+
+    Rows whose count is not > 0 (zero, negative, not a number) are ignored,
+    whatever their other columns hold.  An id of [id_begin, id_end) without a
+    non-empty row gives a zero row; one non-empty row is returned unchanged;
+    otherwise N = sum c, mean = sum c mean_i / N, var = sum c (var_i +
+    (mean_i - mean)^2) / N, min / max over the rows, q_t = sum c q_t,i / N."""
+    from fractions import Fraction
+    ids = np.asarray(ids, dtype=np.uint64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, N_FEATURES)
+    begin, end = int(id_begin), int(id_end)
+    out = np.zeros((end - begin, N_FEATURES), dtype=np.float64)
+    groups = {}
+    for i, r in zip(ids.tolist(), rows):
+        if not begin <= i < end:
+            raise ValueError('an edge id lies outside [id_begin, id_end)')
+        if r[9] > 0:
+            groups.setdefault(i, []).append(r)
+    for i, rs in groups.items():
+        if len(rs) == 1:
+            out[i - begin] = rs[0]
+            continue
+        c = [Fraction(float(r[9])) for r in rs]
+        n = sum(c)
+        m = [Fraction(float(r[0])) for r in rs]
+        mean = sum(ci * mi for ci, mi in zip(c, m)) / n
+        var = sum(ci * (Fraction(float(r[1])) + (mi - mean) ** 2) for ci, mi, r in zip(c, m, rs)) / n
+        o = out[i - begin]
+        o[0], o[1], o[9] = float(mean), float(var), float(n)
+        o[2] = min(float(r[2]) for r in rs)
+        o[8] = max(float(r[8]) for r in rs)
+        for t in range(3, 8):
+            o[t] = float(sum(ci * Fraction(float(r[t])) for ci, r in zip(c, rs)) / n)
+    return out

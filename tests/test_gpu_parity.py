@@ -768,6 +768,8 @@ def test_group_sort_cases(gpu, monkeypatch, case):
         e_o, f_o = O.boundary_features(lab, bnd, ignore_label=case == 'ignore')
         np.testing.assert_array_equal(out['edges'], e_o)
         check_features(out['features'], f_o)
+        if case != 'ignore':   # every label has a face: the nodes are the volume's labels
+            np.testing.assert_array_equal(out['nodes'], O.unique_labels(lab))
 
 
 def test_group_sort_one_label_group(gpu, monkeypatch):

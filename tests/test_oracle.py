@@ -8,6 +8,8 @@
   restatements of the same semantics).
 * the reference tests' structural assertions (test_graph.py:27-115) hold for
   the oracle's per-block sub-graphs and merge.
+* merge_feature_rows_exact (the reference of the GPU row merge) pools the
+  rows of the parts of a sample set to that set's exact moments.
 """
 import json
 import os
@@ -196,3 +198,63 @@ def test_merge_of_partials_is_exact():
                               e_all.shape[0])
     f = O.finalize_features(m, 0.0, 1.0)
     np.testing.assert_allclose(f, f_all, rtol=1e-10, atol=1e-13)
+
+
+def _exact_moments(x):
+    """(count, mean, population variance) of the samples x as Fractions."""
+    from fractions import Fraction
+    f = [Fraction(float(v)) for v in x]
+    n = len(f)
+    mean = sum(f) / n
+    return n, mean, sum((v - mean) ** 2 for v in f) / n
+
+
+@pytest.mark.parametrize('k', [2, 3, 17])
+@pytest.mark.parametrize('family', ['unit', 'signed', 'offset'])
+def test_merge_feature_rows_exact_pools_sample_sets(k, family):
+    """merge_feature_rows_exact against the definition it restates: the rows of
+    k parts of one sample set merge to the count, mean, population variance,
+    min and max of the whole set, each computed from the samples in Fractions
+    and rounded once.  The float32 samples are multiples of 2^-12 and every
+    part holds a power of two of them (4096 in all), so a part's exact mean and
+    variance are float64 numbers (asserted) and the rows lose nothing."""
+    rng = np.random.default_rng(100 + k)
+    m = rng.integers(0, 4096, size=4096)
+    x = {'unit': m / 4096.0, 'signed': (m - 2048) / 4096.0, 'offset': 1000.0 + m / 4096.0}[family].astype(np.float32)
+    sizes = {2: [2048, 2048], 3: [2048, 1024, 1024], 17: [2048] + [128] * 16}[k]
+    assert sum(sizes) == x.size and len(sizes) == k
+    rows = np.zeros((k + 2, 10))
+    at = 0
+    for i, s in enumerate(sizes):
+        part = x[at:at + s]
+        at += s
+        n, mean, var = _exact_moments(part)
+        assert float(mean) == mean and float(var) == var
+        rows[i] = [float(mean), float(var), part.min(), 0, 0, 0, 0, 0, part.max(), n]
+    rows[k] = [np.nan, -1.0, -1e30, 5, 5, 5, 5, 5, 1e30, 0.0]          # empty rows are ignored,
+    rows[k + 1] = [7.0, 7.0, -7.0, 7, 7, 7, 7, 7, 7e9, np.nan]          # whatever they hold
+    ids = np.full(k + 2, 5, np.uint64)
+    got = O.merge_feature_rows_exact(ids, rows[rng.permutation(k + 2)], 4, 7)
+    n, mean, var = _exact_moments(x)
+    assert got.shape == (3, 10) and not got[[0, 2]].any()
+    assert got[1, 9] == n and got[1, 0] == float(mean) and got[1, 1] == float(var)
+    assert got[1, 2] == x.min() and got[1, 8] == x.max()
+
+
+def test_merge_feature_rows_exact_rule():
+    """The row rule on hand-computed rows: count-weighted quantiles, the
+    one-row copy, zero rows, the id range."""
+    rows = np.array([[1.0, 0.0, 1.0, 1.0, 2.0, 3.0, 4.0, 5.0, 1.0, 1.0],
+                     [4.0, 0.0, 4.0, 4.0, 5.0, 6.0, 7.0, 8.0, 4.0, 2.0],
+                     [0.1, 0.3, 0.05, 0.06, 0.07, 0.08, 0.09, 0.1, 0.7, 3.0],
+                     [9.0, 9.0, 9.0, 9.0, 9.0, 9.0, 9.0, 9.0, 9.0, 0.0]])
+    got = O.merge_feature_rows_exact([10, 10, 12, 11], rows, 10, 14)
+    # ids 10: samples {1, 4, 4}: mean 3, variance 2; quantiles (1 q_a + 2 q_b) / 3
+    np.testing.assert_array_equal(got[0], [3.0, 2.0, 1.0, 3.0, 4.0, 5.0, 6.0, 7.0, 4.0, 3.0])
+    np.testing.assert_array_equal(got[1], np.zeros(10))      # only an empty row
+    np.testing.assert_array_equal(got[2], rows[2])           # one row: unchanged
+    np.testing.assert_array_equal(got[3], np.zeros(10))      # absent
+    assert O.merge_feature_rows_exact([], np.zeros((0, 10)), 3, 5).tolist() == [[0.0] * 10] * 2
+    for bad in (9, 14):
+        with pytest.raises(ValueError, match='outside'):
+            O.merge_feature_rows_exact([bad], rows[:1], 10, 14)
