@@ -30,6 +30,9 @@ CTG_N_FEATURES = 10
 CTG_NBINS = 40
 CTG_WIDE_RECORD_WORDS = 48
 CTG_MORPH_COLS = 11
+CTG_REGION_COLS = 5
+CTG_REGION_SUMS = 0
+CTG_REGION_FEATURES = 1
 CTG_MGPU_SAMPLES = 1024
 CTG_MGPU_ROW_WORDS = 28
 CTG_MGPU_MAX_WORLD = 32
@@ -89,6 +92,12 @@ PROTOTYPES = {
     'ctg_merge_morphology': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
     'ctg_result_copy_moments': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
     'ctg_morphology_rows': (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, ctypes.c_int, c_vp]),
+    'ctg_region_features': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int,
+                                           ctypes.c_uint64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_merge_region_features': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_region_rows': (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, c_vp,
+                                       c_vp, ctypes.c_int, c_vp]),
+    'ctg_result_copy_region': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

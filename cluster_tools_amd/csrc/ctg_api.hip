@@ -287,16 +287,16 @@ int ctg_diag_bounds(uint64_t* out) {
 #ifdef CTG_DIAG
     if (!out) return CTG_ERR_ARG;
     CTG_CHECK(hipDeviceSynchronize());
-    hipError_t (*take[7])(unsigned long long*) = {bounds_take_api,    bounds_take_scan, bounds_take_sort,
+    hipError_t (*take[8])(unsigned long long*) = {bounds_take_api,    bounds_take_scan, bounds_take_sort,
                                                    bounds_take_reduce, bounds_take_mgpu, bounds_take_overlap,
-                                                   bounds_take_morph};
+                                                   bounds_take_morph,  bounds_take_region};
     out[0] = out[1] = out[2] = out[3] = 0;
     int found = 0;
-    for (int f = 0; f < 7; ++f) {
+    for (int f = 0; f < 8; ++f) {
         unsigned long long h[3] = {0, 0, 0};
         CTG_CHECK(take[f](h));
         if (h[0] && !found) {
-            out[0] = (uint64_t)f + 1;   // 1 api, 2 scan, 3 sort, 4 reduce, 5 mgpu, 6 overlap, 7 morph
+            out[0] = (uint64_t)f + 1;   // 1 api, 2 scan, 3 sort, 4 reduce, 5 mgpu, 6 overlap, 7 morph, 8 region
             out[1] = h[0];
             out[2] = h[1];
             out[3] = h[2];
@@ -584,6 +584,16 @@ int ctg_result_copy_moments(const ctg_result* r, uint64_t* dst, int mem) {
     }
     return copy_out(dst, r->moments, (size_t)r->n_nodes * MORPH_WORDS * 8, mem);
 }
+int ctg_result_copy_region(const ctg_result* r, uint64_t* counts, double* sums, float* minmax, int mem) {
+    if (!r || !r->reg_count) {
+        set_error("result has no region moments (not a region-features result)");
+        return CTG_ERR_ARG;
+    }
+    int rc = counts ? copy_out(counts, r->reg_count, (size_t)r->n_nodes * 8, mem) : CTG_OK;
+    if (!rc && sums) rc = copy_out(sums, r->reg_sum, (size_t)r->n_nodes * 8, mem);
+    if (!rc && minmax) rc = copy_out(minmax, r->reg_minmax, (size_t)r->n_nodes * 8, mem);
+    return rc;
+}
 const uint64_t* ctg_result_device_edges(const ctg_result* r) { return r ? r->edges : nullptr; }
 const double* ctg_result_device_features(const ctg_result* r) { return r ? r->features : nullptr; }
 int ctg_result_info(const ctg_result* r, int64_t* n_records, int64_t* n_direct) {
@@ -609,6 +619,9 @@ void ctg_free(ctg_result* r) {
     dev_free(r->counts);
     dev_free(r->row_off);
     dev_free(r->moments);
+    dev_free(r->reg_count);
+    dev_free(r->reg_sum);
+    dev_free(r->reg_minmax);
     if (r->device >= 0 && r->device != d) hipSetDevice(d);
     delete r;
 }

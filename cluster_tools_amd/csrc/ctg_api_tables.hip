@@ -1,5 +1,6 @@
-// C ABI of libctg.so (include/ctg.h): label overlaps and segment morphology
-// (kernels and back halves: ctg_overlap.hip, ctg_morph.hip).  What the entry
+// C ABI of libctg.so (include/ctg.h): label overlaps, segment morphology and
+// region features (kernels and back halves: ctg_overlap.hip, ctg_morph.hip,
+// ctg_region.hip).  What the entry
 // points share comes first; the call scaffold is ctg_api.h's.
 #include <hip/hip_runtime.h>
 
@@ -22,7 +23,15 @@ static ResultPtr empty_morphology(int device) {
     return r;
 }
 
-// A label volume of ctg_label_overlaps / ctg_morphology whose labels reach
+static ResultPtr empty_region(int device) {
+    ResultPtr r = empty_result(device);
+    r->reg_count = (uint64_t*)dev_alloc(8);
+    r->reg_sum = (double*)dev_alloc(8);
+    r->reg_minmax = (float*)dev_alloc(8);
+    return r;
+}
+
+// A label volume of ctg_label_overlaps / ctg_morphology / ctg_region_features whose labels reach
 // 2^32: the box's sorted unique labels U and the whole array as 32-bit ranks in
 // U (monotone; voxels outside the box get some rank and are never read).
 struct DenseSide {
@@ -308,6 +317,156 @@ int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t labe
     if (rc) return rc;
     if (!od.d && !orw.d) return CTG_OK;
     CTG_CHECK(launch_morph_rows(r, label_begin, label_end, od.d, orw.d, s));
+    CTG_CHECK(od.copy_back(s));
+    CTG_CHECK(orw.copy_back(s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
+
+int ctg_region_features(const void* labels, int label_bits, const void* data, int data_kind, const int64_t* shape,
+                        const int64_t* begin, const int64_t* end, int has_ignore, uint64_t ignore_label, int mem,
+                        void* stream, ctg_result** out) {
+    const char* who = "ctg_region_features";
+    ApiCall c;
+    if (out) *out = nullptr;
+    if (!labels || !data || !shape || !out) {
+        set_error("ctg_region_features: null argument");
+        return CTG_ERR_ARG;
+    }
+    if (label_bits != 32 && label_bits != 64) {
+        set_error("ctg_region_features: label_bits must be 32 or 64");
+        return CTG_ERR_ARG;
+    }
+    if (data_kind != CTG_DATA_F32 && data_kind != CTG_DATA_U8) {
+        set_error("ctg_region_features: data_kind must be CTG_DATA_F32 or CTG_DATA_U8");
+        return CTG_ERR_ARG;
+    }
+    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
+        set_error("ctg_region_features: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
+        return CTG_ERR_ARG;
+    }
+    CallBox box;
+    int rc = box_of(who, shape, begin, end, TABLE_MAX_VOXELS, &box);
+    if (rc || (rc = c.begin(stream, empty_region)) != CTG_OK) return rc;
+    if (box.voxels == 0) return c.end(false, out);
+    const int64_t *b = box.b, *e = box.e;
+    Workspace& w = c.w();
+    hipStream_t s = c.s;
+    ctg_result* r = c.r.get();
+    const int64_t V = shape[0] * shape[1] * shape[2];
+    const void *dl = nullptr, *dd = nullptr;
+    rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
+    if (!rc) rc = stage_in(w.stage[1], data, (size_t)V * (data_kind == CTG_DATA_U8 ? 1 : 4), mem, s, &dd);
+    if (rc) return rc;
+    unsigned over = 0;
+    if ((rc = hip_status(region_tables(w, dl, label_bits, dd, data_kind, shape, b, e, has_ignore, ignore_label, s, r,
+                                       &over),
+                         who)) != CTG_OK)
+        return rc;
+    if (over) {
+        // labels >= 2^32 do not fit the table's 32-bit keys.  1: the labels
+        // become monotone dense ids
+        DenseSide d;
+        if ((rc = d.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
+        // 2: so does the ignore label (absent from the box: nothing to skip)
+        if (has_ignore) {
+            DevBuf<uint32_t> rank(4);
+            uint32_t h = 0;
+            if (!rank) return hip_status(hipErrorOutOfMemory, who);
+            CTG_CHECK(launch_overlap_find(d.U->nodes, d.U->n_nodes, ignore_label, rank, s));
+            CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
+            CTG_CHECK(hipStreamSynchronize(s));
+            has_ignore = h != 0xFFFFFFFFu;
+            ignore_label = h;
+        }
+        // 3: the scan runs again on the ids
+        unsigned again = 0;
+        if ((rc = hip_status(region_tables(w, d.ids.p, 32, dd, data_kind, shape, b, e, has_ignore, ignore_label, s, r,
+                                           &again),
+                             who)) != CTG_OK)
+            return rc;
+        // 4: which cannot overflow
+        if (again) {
+            set_error("ctg_region_features: dense ids past 2^32");
+            return CTG_ERR_UNSUPPORTED;
+        }
+        // 5: the sorted ids map back to labels
+        CTG_CHECK(launch_gather_labels(d.U->nodes, r->nodes, r->n_nodes, s));
+    }
+    return c.end(r->n_records > 0, out, true);
+}
+
+int ctg_merge_region_features(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
+    ApiCall c;
+    if (out) *out = nullptr;
+    if (!out || n < 0 || (n > 0 && !rows)) {
+        set_error("ctg_merge_region_features: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (n >= 0xFFFFFFFFll) {
+        set_error("ctg_merge_region_features: 2^32 rows or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    int rc = c.begin(stream, empty_region);
+    if (rc) return rc;
+    if (n == 0) return c.end(false, out);
+    hipStream_t s = c.s;
+    DevInput<double> dr;
+    if ((rc = dr.put(rows, (size_t)n * CTG_REGION_COLS * 8, mem, s, "ctg_merge_region_features")) != CTG_OK) return rc;
+    int bad = 0;
+    if ((rc = hip_status(region_merge(c.w(), dr, n, s, c.r.get(), &bad), "ctg_merge_region_features")) != CTG_OK)
+        return rc;
+    if (bad) {
+        set_error("ctg_merge_region_features: a row's id is not an integer in [0, 2^53), or its count is negative or "
+                  "not finite");
+        return CTG_ERR_ARG;
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    return c.end(false, out);
+}
+
+int ctg_region_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end, int form, double norm, double* out,
+                    double* rows, int mem, void* stream) {
+    DevLock dev_lock;
+    if (!r || label_end < label_begin) {
+        set_error("ctg_region_rows: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (form != CTG_REGION_SUMS && form != CTG_REGION_FEATURES) {
+        set_error("ctg_region_rows: form must be CTG_REGION_SUMS or CTG_REGION_FEATURES");
+        return CTG_ERR_ARG;
+    }
+    if (!(norm > 0.0) || !(norm < 1.0 / 0.0)) {
+        set_error("ctg_region_rows: norm must be finite and positive");
+        return CTG_ERR_ARG;
+    }
+    if (!r->reg_count) {
+        set_error("ctg_region_rows: not a region-features result (ctg_region_features, ctg_merge_region_features)");
+        return CTG_ERR_ARG;
+    }
+    const uint64_t n = label_end - label_begin;
+    if (n > (1ull << 40)) {
+        set_error("ctg_region_rows: label range too large");
+        return CTG_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = r->n_nodes;
+    if (N > 0) {   // the id column is a float64: the largest label (the last: nodes ascend) must fit it
+        uint64_t top = 0;
+        CTG_CHECK(hipMemcpyAsync(&top, r->nodes + (N - 1), 8, hipMemcpyDeviceToHost, s));
+        CTG_CHECK(hipStreamSynchronize(s));
+        if (top >= (1ull << 53)) {
+            set_error("ctg_region_rows: a label of 2^53 or more does not fit the float64 id column "
+                      "(ctg_result_copy_region holds any label)");
+            return CTG_ERR_UNSUPPORTED;
+        }
+    }
+    DenseOut<double> od, orw;
+    int rc = hip_status(od.open(out, (size_t)n * CTG_REGION_COLS * 8, mem, true, s), "ctg_region_rows");
+    if (!rc) rc = hip_status(orw.open(rows, (size_t)N * CTG_REGION_COLS * 8, mem, false, s), "ctg_region_rows");
+    if (rc) return rc;
+    if (!od.d && !orw.d) return CTG_OK;
+    CTG_CHECK(launch_region_rows(r, label_begin, label_end, form, norm, od.d, orw.d, s));
     CTG_CHECK(od.copy_back(s));
     CTG_CHECK(orw.copy_back(s));
     CTG_CHECK(hipStreamSynchronize(s));

@@ -451,6 +451,7 @@ hipError_t bounds_take_mgpu(unsigned long long* h);
 hipError_t bounds_take_scan(unsigned long long* h);
 hipError_t bounds_take_overlap(unsigned long long* h);
 hipError_t bounds_take_morph(unsigned long long* h);
+hipError_t bounds_take_region(unsigned long long* h);
 #endif
 
 }  // namespace ctg
@@ -476,6 +477,11 @@ struct ctg_result {
     // segment morphology (ctg_morphology, ctg_merge_morphology): nodes holds the
     // distinct labels, ascending
     uint64_t* moments = nullptr;    // device (N, MORPH_WORDS): n, sum z y x, min z y x, max z y x (inclusive), or null
+    // region features (ctg_region_features, ctg_merge_region_features): nodes
+    // holds the distinct counted labels, ascending; all three or none
+    uint64_t* reg_count = nullptr;  // device (N,) voxels, or null
+    double* reg_sum = nullptr;      // device (N,) sum of the samples
+    float* reg_minmax = nullptr;    // device (N,2) smallest and largest sample
     int64_t n_records = 0;
     int64_t n_direct = 0;
     // affinity partial table (CTG_NO_ADJ_FILTER): a key is an edge only where
@@ -568,6 +574,29 @@ hipError_t morph_merge(Workspace& w, const double* rows, int64_t n, hipStream_t 
 // scattered into the zeroed dense table out over the labels [lb, le); either
 // may be null
 hipError_t launch_morph_rows(const ctg_result* r, uint64_t lb, uint64_t le, double* out, double* rows, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// region features (ctg_region.hip).  Call-sized pool buffers only, as the
+// label overlaps.
+// ---------------------------------------------------------------------------
+constexpr int REGION_WORDS = 3;   // u64 words of a record: n, the f64 sum's bits, f2ord(min) | f2ord(max) << 32
+// The count, sum, min and max of D (kind: CTG_DATA_F32 / CTG_DATA_U8) per label
+// of the box [b, e) of A (bits: 32 or 64) into r (nodes, reg_*; nothing where
+// every voxel is ignored); voxels whose label equals `ignore` are skipped
+// (has_ignore).  *overflow: a counted label >= 2^32 was met -- r is untouched
+// and the caller relabels densely.
+hipError_t region_tables(Workspace& w, const void* A, int bits, const void* D, int kind, const int64_t* shape,
+                         const int64_t* b, const int64_t* e, int has_ignore, uint64_t ignore, hipStream_t s,
+                         ctg_result* r, unsigned* overflow);
+// n > 0 rows of CTG_REGION_COLS float64 in the sum form (device), in any order
+// -> r: rows of one id combine.  *bad: some id was not an integer in [0, 2^53),
+// or a count was negative or not finite (r is untouched).
+hipError_t region_merge(Workspace& w, const double* rows, int64_t n, hipStream_t s, ctg_result* r, int* bad);
+// region moments -> float64 rows of `form`: compact into rows (N x
+// CTG_REGION_COLS) and / or scattered into the zeroed dense table out over the
+// labels [lb, le); either may be null
+hipError_t launch_region_rows(const ctg_result* r, uint64_t lb, uint64_t le, int form, double norm, double* out,
+                              double* rows, hipStream_t s);
 
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,

@@ -103,7 +103,8 @@ struct MorphTable {
     __device__ bool valid(uint64_t, bool in) const { return in; }
     __device__ Key key(uint64_t a) const { return (uint32_t)a; }
     __device__ uint32_t overflow(uint64_t a) const { return (a >> 32) ? 1u : 0u; }
-    __device__ Add head(uint32_t run, int lane, int dy, int lz) const {
+    __device__ NoFold fold(uint64_t, bool, uint64_t, int) const { return {}; }
+    __device__ Add head(uint32_t run, int lane, int dy, int lz, NoFold) const {
         return Add{(uint64_t)(run * (uint32_t)lane + run * (run - 1u) / 2u) | (uint64_t)(run * (uint32_t)dy) << MO_SY |
                        (uint64_t)(run * (uint32_t)lz) << MO_SZ,
                    (run == WAVE ? ~0ull : (1ull << run) - 1ull) << lane, run, (1u << dy) | (1u << (8 + lz))};
@@ -114,7 +115,7 @@ struct MorphTable {
         atomicOr((unsigned long long*)&txo[h], (unsigned long long)a.xbits);
         atomicOr(&tyz[h], a.yzbits);
     }
-    __device__ void put_direct(uint64_t slot, Key key, uint32_t run, int64_t z, int64_t y, int64_t x) const {
+    __device__ void put_direct(uint64_t slot, Key key, uint32_t run, int64_t z, int64_t y, int64_t x, NoFold) const {
         const uint64_t r = run;
         morph_put(rkey, rec, slot, key, r, r * (uint64_t)z, r * (uint64_t)y, r * (uint64_t)x + r * (r - 1) / 2,
                   (uint64_t)z, (uint64_t)y, (uint64_t)x, (uint64_t)z, (uint64_t)y, (uint64_t)x + r - 1);

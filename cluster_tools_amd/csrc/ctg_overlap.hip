@@ -54,9 +54,10 @@ struct OverlapTable {
     __device__ bool valid(const Voxel& v, bool in) const { return in && !(with_ignore && v.b == ignore); }
     __device__ Key key(const Voxel& v) const { return ((uint64_t)(uint32_t)v.a << 32) | (uint32_t)v.b; }
     __device__ uint32_t overflow(const Voxel& v) const { return ((v.a >> 32) ? 1u : 0u) | ((v.b >> 32) ? 2u : 0u); }
-    __device__ uint32_t head(uint32_t run, int, int, int) const { return run; }
+    __device__ NoFold fold(const Voxel&, bool, uint64_t, int) const { return {}; }
+    __device__ uint32_t head(uint32_t run, int, int, int, NoFold) const { return run; }
     __device__ void add(uint32_t h, uint32_t run) const { atomicAdd(&tcnt[h], run); }
-    __device__ void put_direct(uint64_t slot, Key key, uint32_t run, int64_t, int64_t, int64_t) const {
+    __device__ void put_direct(uint64_t slot, Key key, uint32_t run, int64_t, int64_t, int64_t, NoFold) const {
         rkey[slot] = key;
         rcnt[slot] = run;
     }

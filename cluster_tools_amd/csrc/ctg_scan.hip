@@ -1520,7 +1520,8 @@ struct UniqueSet {
     __device__ bool valid(Key, bool in) const { return in; }
     __device__ Key key(Key k) const { return k; }
     __device__ uint32_t overflow(Key) const { return 0u; }
-    __device__ int head(uint32_t, int, int, int) const { return 0; }
+    __device__ NoFold fold(Key, bool, uint64_t, int) const { return {}; }
+    __device__ int head(uint32_t, int, int, int, NoFold) const { return 0; }
     __device__ void add(uint32_t, int) const {}
     __device__ void put_flush(uint64_t slot, int, Key key, const TileBox&) const { out[slot] = key; }
     __device__ void clear(int e) const { keys[e] = EMPTY; }

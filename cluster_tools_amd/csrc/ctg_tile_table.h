@@ -1,8 +1,8 @@
 // Tile-table scans: one workgroup walks a 64 x TILE_Y x TT_TILE_Z tile of a box
 // of label voxels and gathers what it meets, per key, in an LDS hash table that
 // it writes out as records.  The protocol ("Tile-table scans") is
-// stated once, in tile_table_scan; k_overlap_scan, k_morph_scan, k_unique_tiles
-// and k_unique_blocks are policies over it.  The host half of such a scan --
+// stated once, in tile_table_scan; k_overlap_scan, k_morph_scan, k_unique_tiles,
+// k_unique_blocks and k_region_scan are policies over it.  The host half of such a scan --
 // the record buffer that grows until it holds every record -- is
 // scan_into_records.
 #pragma once
@@ -79,11 +79,16 @@ __device__ __forceinline__ uint32_t ballot_rank(uint64_t m) {
 //   load(p, in)                 what this lane reads at voxel p (in: inside the box along x), and of that:
 //   valid(v, in), key(v),       whether the voxel counts, its key, and a counted voxel's label-overflow
 //   overflow(v)                 bits -- all by value, so that they stay in registers as written
-//   head(run, lane, dy, lz)     what a head of `run` voxels at tile-local (lane, dy, lz) adds to its entry,
+//   fold(v, valid, bound, lane) what a lane gathers from the other lanes of its run (Fold; NoFold: nothing):
+//                               every lane of the wave calls it, before the heads part from the rest, so it
+//                               may shuffle; bound is the ballot of the heads and the skipped lanes
+//   head(run, lane, dy, lz, f)  what a head of `run` voxels at tile-local (lane, dy, lz) adds to its entry,
 //   add(h, a)                   and the adding to entry h
-//   put_direct(slot, key, run, z, y, x)   the record of a head that missed the table
+//   put_direct(slot, key, run, z, y, x, f)   the record of a head that missed the table
 //   put_flush(slot, e, key, t)  the record of entry e
 //   clear(e)                    entry e back to free
+struct NoFold {};   // the fold of a policy whose heads need nothing from their run's other lanes
+
 template <class P>
 __device__ __forceinline__ void tile_table_scan(const P& pol, const TileBox& t, int64_t cap) {
     using Key = typename P::Key;
@@ -117,6 +122,7 @@ __device__ __forceinline__ void tile_table_scan(const P& pol, const TileBox& t, 
                 const bool head = valid && (lane == 0 || !pvalid || prev != key);
                 // a run ends before the next head or skipped lane
                 const uint64_t bound = __ballot(head || !valid);
+                const auto f = pol.fold(v, valid, bound, lane);
                 bool direct = false;
                 uint32_t run = 0;
                 if (head) {
@@ -124,7 +130,7 @@ __device__ __forceinline__ void tile_table_scan(const P& pol, const TileBox& t, 
                     run = above ? (uint32_t)__ffsll((unsigned long long)above) : (uint32_t)(WAVE - lane);
                     direct = true;
                     if (key != P::EMPTY) {   // (the one key that looks like a free slot goes direct)
-                        const auto a = pol.head(run, lane, dy, lz);
+                        const auto a = pol.head(run, lane, dy, lz, f);
                         uint32_t h = hash_key(key) & (CAP - 1);
                         for (int q = 0; q < (P::SET ? CAP : TT_PROBES); ++q) {
                             Key cur = pol.keys[h];
@@ -157,7 +163,7 @@ __device__ __forceinline__ void tile_table_scan(const P& pol, const TileBox& t, 
                         b0 = bcast0_u64(b0);
                         if (direct && b0 + rank < (unsigned long long)cap) {
                             CTG_IDX(b0 + rank, cap);
-                            pol.put_direct(b0 + rank, key, run, z, y, x);
+                            pol.put_direct(b0 + rank, key, run, z, y, x, f);
                         }
                     }
                 }

@@ -21,6 +21,15 @@ WIDE_WORDS = L.CTG_WIDE_RECORD_WORDS
 NSLOTS = NBINS + 2   # histogram slots of a wide record: left outliers, the bins, right outliers
 MORPH_COLS = L.CTG_MORPH_COLS   # [id, size, com z y x, min z y x, max z y x]
 MORPH_WORDS = 10               # [n, sum z y x, min z y x, max z y x]
+REGION_COLS = L.CTG_REGION_COLS   # [id, count, sum, min, max] or [id, count, mean, minimum, maximum]
+REGION_FEATURE_NAMES = ('count', 'mean', 'minimum', 'maximum')   # the feature form's columns after the id
+
+
+def _region_form(form):
+    try:
+        return {'sums': L.CTG_REGION_SUMS, 'features': L.CTG_REGION_FEATURES}[form]
+    except KeyError:
+        raise ValueError("form must be 'sums' or 'features', got %r" % (form,)) from None
 
 
 def _is_torch(x):
@@ -113,7 +122,33 @@ class Result:
                 'ctg_morphology_rows')
         return out
 
+    def region_moments(self):
+        """(counts (N,) uint64, sums (N,) float64, minmax (N,2) float32) of a
+        region-features result."""
+        n = self.n_nodes
+        c, s, m = np.empty(n, np.uint64), np.empty(n, np.float64), np.empty((n, 2), np.float32)
+        L.check(L.load().ctg_result_copy_region(self.handle, _ptr(c), _ptr(s), _ptr(m), L.CTG_MEM_HOST),
+                'copy_region')
+        return c, s, m
+
+    def region_rows(self, form='sums', norm=1.0):
+        """(N,5) float64 rows of a region-features result, ids ascending:
+        [id, count, sum, min, max] (``form`` 'sums') or [id, count, mean,
+        minimum, maximum] over ``norm`` ('features')."""
+        out = np.empty((self.n_nodes, REGION_COLS), dtype=np.float64)
+        L.check(L.load().ctg_region_rows(self.handle, 0, 0, _region_form(form), float(norm), None, _ptr(out),
+                                         L.CTG_MEM_HOST, None), 'ctg_region_rows')
+        return out
+
     # --- device copies (torch)
+    def region_rows_torch(self, form='sums', norm=1.0):
+        """(N,5) float64 tensor of the rows of a region-features result."""
+        import torch
+        t = torch.empty((self.n_nodes, REGION_COLS), dtype=torch.float64, device='cuda:%d' % self.device)
+        L.check(L.load().ctg_region_rows(self.handle, 0, 0, _region_form(form), float(norm), None,
+                                         ctypes.c_void_p(t.data_ptr()), L.CTG_MEM_DEVICE, None), 'ctg_region_rows')
+        return t
+
     def moments_torch(self):
         """(N,10) int64 tensor of the uint64 moments of a morphology result."""
         import torch
@@ -793,6 +828,141 @@ def morphology_rows(handle_or_tables, label_begin, label_end):
     try:
         L.check(L.load().ctg_morphology_rows(r.handle, lb, le, _ptr(out), None, L.CTG_MEM_HOST, None),
                 'ctg_morphology_rows')
+    finally:
+        if own:
+            r.free()
+    return out
+
+
+def _data_volume(x, on_dev):
+    """A region-features data argument -> (array, CTG_DATA_*): float32 or uint8."""
+    if _is_torch(x) != on_dev:
+        raise ValueError('labels and data must both be numpy arrays or both CUDA tensors')
+    if on_dev:
+        import torch
+        if not (x.is_cuda and x.is_contiguous()) or x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError('data must be a contiguous float32 or uint8 CUDA tensor')
+        return x, L.CTG_DATA_U8 if x.dtype == torch.uint8 else L.CTG_DATA_F32
+    x = np.asarray(x)
+    if x.dtype not in (np.float32, np.uint8):
+        raise TypeError('data must be float32 or uint8, got %s' % x.dtype)
+    return np.ascontiguousarray(x), L.CTG_DATA_U8 if x.dtype == np.uint8 else L.CTG_DATA_F32
+
+
+def region_features_handle(labels, data, begin=None, end=None, ignore_label=None, stream=None):
+    """ctg_region_features -> the device-resident ``Result``: nodes() = the
+    distinct labels of the box [begin, end), ascending; region_moments() = their
+    voxel counts and the sums, minima and maxima of ``data`` over their voxels;
+    region_rows() = the float64 rows of either form.  Voxels whose *label*
+    equals ``ignore_label`` are not counted and that label gets no row (None:
+    every voxel counts, label 0 included).  Both volumes numpy arrays or both
+    CUDA tensors, (Z,Y,X); labels 32- or 64-bit integers, data float32 or uint8
+    (a channel of a 4-D input: pass ``data[channel]``)."""
+    labels, bits = _label_volume(labels, 'labels')
+    on_dev = _is_torch(labels)
+    data, kind = _data_volume(data, on_dev)
+    shape = tuple(labels.shape)
+    if len(shape) != 3:
+        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
+    if tuple(data.shape) != shape:
+        raise ValueError('data shape %s != labels shape %s' % (tuple(data.shape), shape))
+    for box in (begin, end):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end must have 3 entries')
+    if ignore_label is not None and not 0 <= int(ignore_label) < 1 << 64:
+        raise ValueError('ignore_label must be a uint64 value or None, got %r' % (ignore_label,))
+    lib = L.load()
+    dev = L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_region_features(_ptr(labels), bits, _ptr(data), kind, _shape_arr(shape),
+                                 _shape_arr(begin) if begin is not None else None,
+                                 _shape_arr(end) if end is not None else None,
+                                 int(ignore_label is not None), int(ignore_label or 0),
+                                 L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+    L.check(rc, 'ctg_region_features')
+    return Result(h, dev)
+
+
+def _region_tables(r, norm):
+    counts, sums, minmax = r.region_moments()
+    return dict(nodes=r.nodes(), counts=counts, sums=sums, minmax=minmax, rows=r.region_rows('sums'),
+                features=r.region_rows('features', norm))
+
+
+def region_features(labels, data, begin=None, end=None, ignore_label=None, norm=None):
+    """Host convenience of region_features_handle: dict(nodes (N,) uint64,
+    counts (N,) uint64, sums (N,) float64, minmax (N,2) float32, rows (N,5)
+    float64 in the sum form, features (N,5) float64 in the feature form over
+    ``norm`` -- None: 255 for uint8 data and 1 otherwise -- n_records,
+    n_direct).  A label of 2^53 or more does not fit the rows' id column: use
+    the handle's nodes() and region_moments() for such volumes."""
+    if norm is None:
+        dt = data.dtype
+        norm = 255.0 if str(dt).endswith('uint8') else 1.0
+    r = region_features_handle(labels, data, begin, end, ignore_label)
+    try:
+        out = _region_tables(r, norm)
+        out['n_records'], out['n_direct'] = r.info()
+    finally:
+        r.free()
+    return out
+
+
+def merge_region_features_handle(rows, stream=None):
+    """ctg_merge_region_features: (n,5) float64 rows [id, count, sum, min, max]
+    of partial tables, in any order -> the table in which the rows of one id
+    are combined (``Result``): counts and sums add, min and max fold."""
+    on_dev = _is_torch(rows)
+    if on_dev:
+        if not (rows.is_cuda and rows.is_contiguous()) or rows.element_size() != 8 or not rows.is_floating_point():
+            raise ValueError('rows must be a contiguous float64 CUDA tensor')
+        size = int(rows.numel())
+    else:
+        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
+        size = rows.size
+    if size % REGION_COLS or (size and rows.ndim == 2 and rows.shape[1] != REGION_COLS):
+        raise ValueError('region-feature rows have %d columns, got %s' % (REGION_COLS, tuple(rows.shape)))
+    lib = L.load()
+    dev = L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_merge_region_features(_ptr(rows), size // REGION_COLS,
+                                       L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+    L.check(rc, 'ctg_merge_region_features')
+    return Result(h, dev)
+
+
+def merge_region_features(rows, norm=1.0):
+    """Host convenience of merge_region_features_handle: the dict of region_features."""
+    r = merge_region_features_handle(rows)
+    try:
+        return _region_tables(r, norm)
+    finally:
+        r.free()
+
+
+def region_feature_rows(handle_or_tables, label_begin, label_end, form='features', norm=1.0):
+    """The dense (label_end - label_begin, 5) float64 table of the labels in
+    [label_begin, label_end) in ``form`` ('features': [id, count, mean, minimum,
+    maximum] over ``norm``; 'sums': [id, count, sum, min, max]): the row of
+    label a at a - label_begin, zeros for absent labels.  ``handle_or_tables``:
+    a ``Result`` of region_features_handle / merge_region_features_handle, or a
+    dict with 'rows' in the sum form (merged first)."""
+    lb, le = int(label_begin), int(label_end)
+    if lb < 0 or le < lb:
+        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
+    code = _region_form(form)
+    if not (float(norm) > 0.0 and float(norm) < float('inf')):
+        raise ValueError('norm must be finite and positive, got %r' % (norm,))
+    own = not isinstance(handle_or_tables, Result)
+    r = merge_region_features_handle(handle_or_tables['rows']) if own else handle_or_tables
+    out = np.zeros((le - lb, REGION_COLS), dtype=np.float64)
+    try:
+        L.check(L.load().ctg_region_rows(r.handle, lb, le, code, float(norm), _ptr(out), None, L.CTG_MEM_HOST, None),
+                'ctg_region_rows')
     finally:
         if own:
             r.free()

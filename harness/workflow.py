@@ -336,6 +336,90 @@ def morphology_workflow(input_path, input_key, output_path, output_key, block_sh
     return timer
 
 
+def _region_features_job(input_path, input_key, labels_path, labels_key, output_path, output_key, block_shape,
+                         channel, ignore_label, blocks):
+    """region_features.py:134-186 (_block_features) and the job's loop :213-228."""
+    from cluster_tools_amd import features
+    with ndist._open(input_path, 'r') as fi, ndist._open(labels_path, 'r') as fl:
+        ds_in, ds_labels = fi[input_key], fl[labels_key]                  # :217-218
+        blk = blocking([0, 0, 0], list(ds_labels.shape), list(block_shape))   # :221-222
+        for b in blocks:                                                  # :224
+            block = blk.getBlock(b)                                       # :139
+            bb = tuple(slice(x, y) for x, y in zip(block.begin, block.end))   # :140
+            labels = ds_labels[bb]                                        # :142
+            if ignore_label is not None and np.sum(labels != ignore_label) == 0:   # :146-149
+                continue
+            bb_in = bb if channel is None else (channel,) + bb            # :155
+            input_ = ds_in[bb_in]                                         # :156 (normalised after the merge, :151-157)
+            chunk_id = tuple(x // c for x, c in zip(block.begin, block_shape))     # :183-184
+            features.computeAndSerializeRegionFeatures(labels, input_, output_path, output_key, chunk_id,
+                                                       ignoreLabel=ignore_label)   # :159-185
+
+
+def _merge_region_features_job(tmp_path, tmp_key, output_path, output_key, node_chunk, feature_names,
+                               threads_per_job, blocks):
+    """merge_region_features.py:161-194."""
+    from cluster_tools_amd import features
+    with ndist._open(output_path, 'r') as f:
+        n_nodes = f[output_key].shape[0]                                  # :182-183
+    blk = blocking([0], [n_nodes], [node_chunk])                          # :185
+    node_begin = blk.getBlock(blocks[0]).begin[0]                         # :186
+    node_end = blk.getBlock(blocks[-1]).end[0]                            # :187
+    features.mergeAndSerializeRegionFeatures(tmp_path, tmp_key, output_path, output_key, node_begin, node_end,
+                                             featureNames=feature_names,
+                                             numberOfThreads=threads_per_job)   # :193-194
+
+
+def region_features_workflow(input_path, input_key, labels_path, labels_key, output_path, output_key, tmp_path,
+                             block_shape, number_of_labels, channel=None, ignore_label=0,
+                             feature_names=('count', 'mean'), node_chunk=10000, max_jobs=1, threads_per_job=4,
+                             timer=None, mode='threads'):
+    """RegionFeaturesWorkflow (features/features_workflow.py:77-105):
+    RegionFeatures into the varlen float64 dataset ``block_feats`` of
+    ``tmp_path`` with chunks = ``block_shape`` (region_features.py:71-83), then
+    MergeRegionFeatures over consecutive label ranges of ``node_chunk``
+    (merge_region_features.py:41-64; 10000 in the reference) into the
+    (number_of_labels, n_features) float32 dataset ``output_key``, columns in
+    ``feature_names`` order (:52-53; ['count', 'mean'] is region_features.py:211)."""
+    timer = timer or Timer()
+    tmp_key = 'block_feats'                                               # region_features.py:73
+    with ndist._open(input_path, 'r') as f:
+        shape = list(f[input_key].shape)                                  # :59
+    if len(shape) == 4 and channel is None:
+        raise RuntimeError('Got 4d input, but channel was not specified')   # :60-61
+    if len(shape) == 4 and channel >= shape[0]:
+        raise RuntimeError('Channel %i is to large for n-channels %i' % (channel, shape[0]))   # :62-64
+    if len(shape) == 3 and channel is not None:
+        raise RuntimeError('Channel was specified, but input is only 3d')   # :65-66
+    if len(shape) == 4:
+        shape = shape[1:]                                                 # :68-69
+    block_list = blocks_in_volume(shape, block_shape)                     # :87
+    with timer.stage('region_features'):
+        with ndist._open(tmp_path) as f:                                # :81-83 (float64 chunks: features.py)
+            f.require_dataset(tmp_key, shape=shape, compression='gzip', chunks=tuple(block_shape), dtype='float64')
+        job = functools.partial(_region_features_job, input_path, input_key, labels_path, labels_key, tmp_path,
+                                tmp_key, list(block_shape), channel, ignore_label)
+        _run_jobs(job, _jobs(block_list, max_jobs), mode)
+    with timer.stage('merge_region_features'):
+        chunk_size = min(int(node_chunk), int(number_of_labels))          # merge_region_features.py:41
+        with ndist._open(output_path) as f:                             # :51-53
+            f.require_dataset(output_key, dtype='float32', shape=(int(number_of_labels), len(feature_names)),
+                              chunks=(chunk_size, 1), compression='gzip')
+        node_block_list = blocks_in_volume([int(number_of_labels)], [chunk_size])   # :60
+        n_jobs = max(1, min(len(node_block_list), max_jobs))              # :62
+        # consecutive_blocks=True (:64): every job gets one run of label chunks
+        per_job = [len(node_block_list) // n_jobs + (1 if j < len(node_block_list) % n_jobs else 0)
+                   for j in range(n_jobs)]
+        runs, c0 = [], 0
+        for n in per_job:
+            runs.append(node_block_list[c0:c0 + n])
+            c0 += n
+        job = functools.partial(_merge_region_features_job, tmp_path, tmp_key, output_path, output_key, chunk_size,
+                                list(feature_names), threads_per_job)
+        _run_jobs(job, [r for r in runs if r], mode)
+    return timer
+
+
 def _normalize(x):
     """vu.normalize (utils/volume_utils.py:98-105): float32, min to 0, max to 1."""
     x = np.asarray(x, dtype=np.float32).copy()

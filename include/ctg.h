@@ -33,6 +33,10 @@
  *                                        morphology/block_morphology.py:134
  *   ctg_merge_morphology, ctg_morphology_rows <- ndist.mergeAndSerializeMorphology
  *                                        morphology/merge_morphology.py:130
+ *   ctg_region_features               <- _block_features, from np.unique to the feature arrays
+ *                                        features/region_features.py:159-171
+ *   ctg_merge_region_features, ctg_region_rows <- _extract_and_merge_region_features
+ *                                        features/merge_region_features.py:109-158
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -334,6 +338,75 @@ int ctg_result_copy_moments(const ctg_result* r, uint64_t* dst, int mem);
 int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end,
                         double* out, double* rows, int mem, void* stream);
 
+/*
+ * Region features (RegionFeaturesWorkflow): per label of the box [begin, end)
+ * (NULL = 0 / shape) of a label volume the voxel count and the sum, the minimum
+ * and the maximum of the samples of `data` at its voxels.  Replaces the array
+ * work of _block_features (features/region_features.py:159-171: np.unique, the
+ * dict relabelling and vigra.analysis.extractRegionFeatures); the chunk is
+ * written by cluster_tools_amd/features.py.
+ *   labels   uint64 (label_bits = 64) or uint32 (32), C-order (Z,Y,X) of `shape`;
+ *            any label value, 2^32 and above included; label 0 is a label like
+ *            any other unless it is the ignore label
+ *   data     CTG_DATA_F32 or CTG_DATA_U8, of `shape` (a channel of a 4-D input is
+ *            that channel's plane, region_features.py:155); samples enter as they
+ *            are, u8 as their integer value -- the normalisation of
+ *            region_features.py:151-157 is ctg_region_rows' `norm`
+ *   has_ignore  voxels whose *label* equals ignore_label are not counted and
+ *            that label gets no row (vigra's ignoreLabel, region_features.py:170-171)
+ * Result: nodes = the distinct counted labels, ascending; ctg_result_copy_region
+ * = their counts (uint64), sums (float64) and (min, max) (float32).  A sum is
+ * made of float64 adds of the samples, each exact, in no fixed order: where
+ * every partial sum is representable (u8 data; f32 data on a grid such as
+ * k / 256) the bits are the same in every run and across a merge, otherwise two
+ * orders of n terms differ by at most 2 (n - 1) 2^-53 sum|x|.  Non-finite
+ * samples: sums follow IEEE; the min and max of a label that holds a NaN are
+ * unspecified.  An empty box, or one whose every voxel is ignored, gives an
+ * empty result; a box outside the array is CTG_ERR_ARG; a box of 2^32 voxels or
+ * more is CTG_ERR_UNSUPPORTED.  ctg_result_info: the records the scan wrote,
+ * and how many of them bypassed the workgroup tables.  Like the overlaps calls
+ * these keep their records in buffers of their own: a CTG_DEFER_STATS handle of
+ * the same device stays valid across them.  Every argument error is found
+ * before any GPU work and leaves *out NULL.
+ */
+#define CTG_REGION_COLS 5
+#define CTG_REGION_SUMS 0       /* rows [id, count, sum, min, max]: the chunk form ctg_merge_region_features reads */
+#define CTG_REGION_FEATURES 1   /* rows [id, count, mean, minimum, maximum], normalised */
+int ctg_region_features(const void* labels, int label_bits, const void* data, int data_kind,
+                        const int64_t* shape, const int64_t* begin, const int64_t* end,
+                        int has_ignore, uint64_t ignore_label, int mem, void* stream, ctg_result** out);
+
+/* Combine partial region tables -- n rows of the 5-column float64 sum form, in
+ * any order -- into one result of the form above: per id the counts add
+ * (uint64), the sums add (float64), min and max fold.  Sums stay sums until the
+ * one division of ctg_region_rows, where merge_feats
+ * (features/merge_region_features.py:94-106) re-weights means block by block in
+ * float32; for exactly summable data the merged table equals one
+ * ctg_region_features call over the whole volume bit for bit.  Rows of count 0
+ * add nothing.  An id that is not an integer in [0, 2^53), or a negative or
+ * non-finite count, is CTG_ERR_ARG.  The array work of
+ * _extract_and_merge_region_features (features/merge_region_features.py:109-156). */
+int ctg_merge_region_features(const double* rows, int64_t n, int mem, void* stream, ctg_result** out);
+
+/* The float64 rows of a region-features result, in `form`: CTG_REGION_SUMS
+ * [id, count, sum, min, max], or CTG_REGION_FEATURES [id, count, mean, minimum,
+ * maximum] with mean = (sum / (double)count) / norm, minimum = min / norm,
+ * maximum = max / norm -- norm 255.0 for uint8 input and 1.0 otherwise
+ * (vu.normalize, features/region_features.py:151-157); norm must be finite and
+ * positive.  `rows` (may be NULL) receives the (N,5) rows of the labels in
+ * ascending order; `out` (may be NULL) is a dense (label_end - label_begin, 5)
+ * table that receives the row of every label in [label_begin, label_end) at
+ * label - label_begin and zeros for absent labels (what
+ * features/merge_region_features.py:157 makes of their 0 / 0).  A table with a
+ * label of 2^53 or more is CTG_ERR_UNSUPPORTED: the id column cannot hold it. */
+int ctg_region_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end, int form, double norm,
+                    double* out, double* rows, int mem, void* stream);
+
+/* the (N,) uint64 counts, (N,) float64 sums and (N,2) float32 (min, max) of a
+ * region-features result, which hold any label; each destination may be NULL
+ * (the feats['count'] ... arrays of features/region_features.py:170) */
+int ctg_result_copy_region(const ctg_result* r, uint64_t* counts, double* sums, float* minmax, int mem);
+
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
                      const uint64_t* query, int64_t n_query, int64_t* out_ids,
@@ -424,8 +497,8 @@ int ctg_trim(void);
 
 /* profiling: per-phase device milliseconds of the last ctg_rag_features call
  * (HIP events on the call's stream): [0] face scan, [1] key pack, [2] sort,
- * [3] segment, [4] reduce+finalize, [5] nodes, [6] total; of a ctg_label_overlaps
- * or ctg_morphology call: [0] scan, [2] sort, [3] run heads + prefix sums,
+ * [3] segment, [4] reduce+finalize, [5] nodes, [6] total; of a ctg_label_overlaps,
+ * ctg_morphology or ctg_region_features call: [0] scan, [2] sort, [3] run heads + prefix sums,
  * [4] run sums / folds, [6] total */
 int ctg_set_profiling(int on);
 int ctg_last_timings(double* ms, int n);
@@ -435,7 +508,8 @@ int ctg_last_timings(double* ms, int n);
  * run tables, permutations, node bitmaps, exchange rows) that reached past
  * the current call's count since the last query.  Returns 0 (none) or 1 with
  * out[0] = source file (1 ctg_api, 2 ctg_scan, 3 ctg_sort, 4 ctg_reduce,
- * 5 ctg_mgpu, 6 ctg_overlap, 7 ctg_morph), out[1] = line, out[2] = index, out[3] = bound; clears them.
+ * 5 ctg_mgpu, 6 ctg_overlap, 7 ctg_morph,
+ * 8 ctg_region), out[1] = line, out[2] = index, out[3] = bound; clears them.
  * Product builds: CTG_ERR_UNSUPPORTED. */
 int ctg_diag_bounds(uint64_t* out);
 
