@@ -25,6 +25,9 @@ CTG_NO_ADJ_FILTER = 2
 CTG_NO_NODES = 4
 CTG_DEFER_STATS = 8
 CTG_ERR_STALE = -5
+CTG_ERR_MISSING = -6
+CTG_ASSIGN_DENSE = 0
+CTG_ASSIGN_SPARSE = 1
 CTG_MAX_CHANNELS = 24
 CTG_N_FEATURES = 10
 CTG_NBINS = 40
@@ -98,6 +101,12 @@ PROTOTYPES = {
     'ctg_region_rows': (ctypes.c_int, [c_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_double, c_vp,
                                        c_vp, ctypes.c_int, c_vp]),
     'ctg_result_copy_region': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int]),
+    'ctg_assignment_dense': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_assignment_sparse': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int64, ctypes.c_int, c_vp, ctypes.POINTER(c_vp)]),
+    'ctg_assignment_info': (ctypes.c_int, [c_vp, c_i64p, c_u64p, ctypes.POINTER(ctypes.c_int)]),
+    'ctg_assignment_free': (None, [c_vp]),
+    'ctg_apply_assignment': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int64,
+                                            ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, c_vp]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

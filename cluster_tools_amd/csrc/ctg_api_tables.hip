@@ -1,10 +1,13 @@
-// C ABI of libctg.so (include/ctg.h): label overlaps, segment morphology and
-// region features (kernels and back halves: ctg_overlap.hip, ctg_morph.hip,
-// ctg_region.hip).  What the entry
+// C ABI of libctg.so (include/ctg.h): label overlaps, segment morphology,
+// region features and assignments (kernels and back halves: ctg_overlap.hip,
+// ctg_morph.hip, ctg_region.hip, ctg_take.hip).  What the entry
 // points share comes first; the call scaffold is ctg_api.h's.
 #include <hip/hip_runtime.h>
 
+#include <numeric>
+
 #include "ctg_api.h"
+#include "ctg_take.h"
 
 using namespace ctg;
 
@@ -30,6 +33,12 @@ static ResultPtr empty_region(int device) {
     r->reg_minmax = (float*)dev_alloc(8);
     return r;
 }
+
+// an assignment under construction: freed unless release()d to the caller
+struct AssignmentFree {
+    void operator()(ctg_assignment* a) const { ctg_assignment_free(a); }
+};
+using AssignmentPtr = std::unique_ptr<ctg_assignment, AssignmentFree>;
 
 // A label volume of ctg_label_overlaps / ctg_morphology / ctg_region_features whose labels reach
 // 2^32: the box's sorted unique labels U and the whole array as 32-bit ranks in
@@ -470,6 +479,222 @@ int ctg_region_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_en
     CTG_CHECK(od.copy_back(s));
     CTG_CHECK(orw.copy_back(s));
     CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
+
+int ctg_assignment_dense(const uint64_t* table, int64_t n, int mem, void* stream, ctg_assignment** out) {
+    ApiCall c;
+    if (out) *out = nullptr;
+    if (!out || n < 0 || (n > 0 && !table)) {
+        set_error("ctg_assignment_dense: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
+        set_error("ctg_assignment_dense: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
+        return CTG_ERR_ARG;
+    }
+    int rc = c.begin(stream);
+    if (rc) return rc;
+    hipStream_t s = c.s;
+    AssignmentPtr a(new ctg_assignment());
+    a->device = c.dev;
+    a->kind = CTG_ASSIGN_DENSE;
+    a->n = n;
+    a->size = (uint64_t)n;
+    DevBuf<unsigned long long> stat(16);
+    if (!stat || !(a->table = (uint64_t*)dev_alloc(std::max<size_t>((size_t)n * 8, 8))))
+        return hip_status(hipErrorOutOfMemory, "ctg_assignment_dense");
+    CTG_CHECK(hipMemsetAsync(stat.p, 0, 16, s));
+    if (n)
+        CTG_CHECK(hipMemcpyAsync(a->table, table, (size_t)n * 8,
+                                 mem == CTG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    CTG_CHECK(launch_take_max(a->table, n, stat, s));
+    unsigned long long h[2] = {0, 0};
+    CTG_CHECK(hipMemcpyAsync(h, stat.p, 16, hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    a->max_value = h[1];
+    *out = a.release();
+    return CTG_OK;
+}
+
+int ctg_assignment_sparse(const uint64_t* keys, const uint64_t* values, int64_t n, int mem, void* stream,
+                          ctg_assignment** out) {
+    const char* who = "ctg_assignment_sparse";
+    ApiCall c;
+    if (out) *out = nullptr;
+    if (!out || n < 0 || (n > 0 && (!keys || !values))) {
+        set_error("ctg_assignment_sparse: bad arguments");
+        return CTG_ERR_ARG;
+    }
+    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
+        set_error("ctg_assignment_sparse: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
+        return CTG_ERR_ARG;
+    }
+    if (n > (1ll << 40)) {
+        set_error("ctg_assignment_sparse: more than 2^40 pairs");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    int rc = c.begin(stream);
+    if (rc) return rc;
+    hipStream_t s = c.s;
+    AssignmentPtr a(new ctg_assignment());
+    a->device = c.dev;
+    a->kind = CTG_ASSIGN_SPARSE;
+    a->n = n;
+    a->size = take_capacity(n);
+    const size_t slot_bytes = (size_t)a->size * 16;
+    DevBuf<unsigned long long> stat(16);
+    if (!stat || !(a->table = (uint64_t*)dev_alloc((size_t)take_table_words(a->size) * 8)))
+        return hip_status(hipErrorOutOfMemory, who);
+    DevInput<uint64_t> dk, dv;
+    rc = dk.put(keys, (size_t)n * 8, mem, s, who);
+    if (!rc) rc = dv.put(values, (size_t)n * 8, mem, s, who);
+    if (rc) return rc;
+    CTG_CHECK(hipMemsetAsync(stat.p, 0, 16, s));
+    CTG_CHECK(hipMemsetAsync(a->table, 0xFF, slot_bytes, s));               // every slot free
+    CTG_CHECK(hipMemsetAsync((char*)a->table + slot_bytes, 0, 16, s));      // the side words
+    CTG_CHECK(launch_take_build(dk, dv, n, a->table, a->size, stat, s));
+    unsigned long long h[2] = {0, 0};
+    CTG_CHECK(hipMemcpyAsync(h, stat.p, 16, hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    if (h[0]) {
+        set_error("ctg_assignment_sparse: " + std::to_string(h[0]) + " duplicate key(s)");
+        return CTG_ERR_ARG;
+    }
+    a->max_value = h[1];
+    *out = a.release();
+    return CTG_OK;
+}
+
+int ctg_assignment_info(const ctg_assignment* a, int64_t* n, uint64_t* max_value, int* kind) {
+    if (!a) {
+        set_error("ctg_assignment_info: null handle");
+        return CTG_ERR_ARG;
+    }
+    if (n) *n = a->n;
+    if (max_value) *max_value = a->max_value;
+    if (kind) *kind = a->kind;
+    return CTG_OK;
+}
+
+void ctg_assignment_free(ctg_assignment* a) {
+    if (!a) return;
+    const int d = current_device();
+    if (a->device >= 0 && a->device != d) hipSetDevice(a->device);
+    dev_free(a->table);
+    if (a->device >= 0 && a->device != d) hipSetDevice(d);
+    delete a;
+}
+
+int ctg_apply_assignment(const ctg_assignment* a, const void* labels, int label_bits, int64_t n,
+                         const int64_t* seg_begin, const uint64_t* seg_offset, int64_t n_seg, int allow_missing,
+                         uint64_t* out, uint64_t* seg_nonzero, uint64_t* missing, int mem, void* stream) {
+    const char* who = "ctg_apply_assignment";
+    ApiCall c;
+    if (!a || !seg_nonzero || !missing || (n > 0 && !labels) || (seg_begin && !seg_offset && n_seg > 0)) {
+        set_error("ctg_apply_assignment: null argument");
+        return CTG_ERR_ARG;
+    }
+    if (label_bits != 32 && label_bits != 64) {
+        set_error("ctg_apply_assignment: label_bits must be 32 or 64");
+        return CTG_ERR_ARG;
+    }
+    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
+        set_error("ctg_apply_assignment: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
+        return CTG_ERR_ARG;
+    }
+    if (n < 0 || (seg_begin && n_seg < 0)) {
+        set_error("ctg_apply_assignment: negative n or n_seg");
+        return CTG_ERR_ARG;
+    }
+    if (seg_begin && n_seg > 0x7FFFFFFFll) {
+        set_error("ctg_apply_assignment: 2^31 segments or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    const TakeChunks chunks = take_chunk_prefix(seg_begin, n_seg, n, TAKE_CHUNK);
+    if (chunks.error == TakeChunks::BAD_SEGMENTS) {
+        set_error("ctg_apply_assignment: seg_begin must ascend from 0 to n");
+        return CTG_ERR_ARG;
+    }
+    if (chunks.error == TakeChunks::TOO_MANY_CHUNKS) {
+        set_error("ctg_apply_assignment: 2^43 voxels or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    if (allow_missing && a->kind != CTG_ASSIGN_SPARSE) {
+        set_error("ctg_apply_assignment: allow_missing needs a sparse assignment");
+        return CTG_ERR_ARG;
+    }
+    if (out && (const void*)out == labels && label_bits != 64) {
+        set_error("ctg_apply_assignment: in place needs 64-bit labels");
+        return CTG_ERR_ARG;
+    }
+    if (((uintptr_t)labels & (uintptr_t)(label_bits / 8 - 1)) || ((uintptr_t)out & 7u)) {
+        set_error("ctg_apply_assignment: labels and out must be aligned to their element size");
+        return CTG_ERR_ARG;
+    }
+    const int64_t ns = seg_begin ? n_seg : 1;
+    int rc = c.begin(stream);
+    if (rc) return rc;
+    hipStream_t s = c.s;
+    missing[0] = missing[1] = 0;
+    for (int64_t k = 0; k < ns; ++k) seg_nonzero[k] = 0;
+    if (n == 0) return CTG_OK;
+    // one device block: seg_begin (ns + 1), seg_off (ns), the counts (missing 2 + nonzero ns x slots), prefix (ns + 1, u32)
+    const int slots = take_count_slots(ns);
+    const size_t words = (size_t)(ns + 1) + (size_t)ns + 2 + (size_t)ns * slots;
+    std::vector<uint64_t> h(words + ((size_t)ns + 2) / 2, 0);
+    const int64_t whole[2] = {0, n};
+    std::copy_n(seg_begin ? seg_begin : whole, ns + 1, (int64_t*)h.data());
+    if (seg_begin) std::copy_n(seg_offset, ns, h.data() + ns + 1);
+    h[2 * ns + 2] = ~0ull;   // the smallest missing label starts at all ones
+    std::copy(chunks.prefix.begin(), chunks.prefix.end(), (uint32_t*)(h.data() + words));
+    DevBuf<uint64_t> seg(h.size() * 8);
+    if (!seg) return hip_status(hipErrorOutOfMemory, who);
+    CTG_CHECK(hipMemcpyAsync(seg.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
+    const bool host = mem == CTG_MEM_HOST;
+    const size_t lbytes = (size_t)n * (label_bits / 8);
+    DevInput<char> dl;
+    if ((rc = dl.put((const char*)labels, lbytes, mem, s, who)) != CTG_OK) return rc;
+    DevBuf<uint64_t> dout;
+    uint64_t* o = out;
+    if (host && out) {
+        // (a host call in place: the copy of the labels is overwritten instead)
+        o = (const void*)out == labels ? (uint64_t*)dl.own.p : dout.alloc((size_t)n * 8);
+        if (!o) return hip_status(hipErrorOutOfMemory, who);
+    }
+    TakeArgs A{};
+    A.labels = dl.p;
+    A.out = o;
+    A.seg_begin = (const int64_t*)seg.p;
+    A.seg_off = seg.p + ns + 1;
+    A.missing = (unsigned long long*)(seg.p + 2 * ns + 1);
+    A.seg_nonzero = A.missing + 2;
+    A.prefix = (const uint32_t*)(seg.p + words);
+    A.n_seg = (int)ns;
+    A.nz_slots = slots;
+    A.table = a->table;
+    A.size = a->size;
+    A.par = (int)(((uintptr_t)dl.p / (uintptr_t)(label_bits / 8)) & 1u);
+    A.wide_store = o && (int)(((uintptr_t)o >> 3) & 1u) == A.par;
+    Ev ev{c.w(), s};   // a profiled call: the kernel is phase 0, the other phases are empty
+    ev.mark(0);
+    CTG_CHECK(launch_take(A, label_bits, a->kind == CTG_ASSIGN_DENSE, chunks.prefix[ns], s));
+    for (int i = 1; i <= 6; ++i) ev.mark(i);
+    std::vector<uint64_t> back((size_t)ns * slots + 2);
+    CTG_CHECK(hipMemcpyAsync(back.data(), seg.p + 2 * ns + 1, back.size() * 8, hipMemcpyDeviceToHost, s));
+    if (host && out) CTG_CHECK(hipMemcpyAsync(out, o, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    if (c.w().profiling && (rc = read_phase_times(c.w(), s)) != CTG_OK) return rc;
+    missing[0] = back[0];
+    missing[1] = back[0] ? back[1] : 0;
+    for (int64_t k = 0; k < ns; ++k)
+        seg_nonzero[k] = std::accumulate(back.begin() + 2 + k * slots, back.begin() + 2 + (k + 1) * slots, (uint64_t)0);
+    if (missing[0] && !allow_missing) {
+        set_error(std::string(who) + ": " + std::to_string(missing[0]) + " voxel(s) without an entry, the smallest label " +
+                  std::to_string(missing[1]) +
+                  (a->kind == CTG_ASSIGN_DENSE ? " (the table has " + std::to_string(a->n) + " entries)" : ""));
+        return CTG_ERR_MISSING;
+    }
     return CTG_OK;
 }
 

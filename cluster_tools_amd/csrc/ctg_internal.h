@@ -495,6 +495,17 @@ struct ctg_result {
     std::vector<void*> owned;
 };
 
+// assignment handle (opaque in the C ABI): a dense table or the hash table of
+// ctg_take.h, in device memory the handle owns
+struct ctg_assignment {
+    int device = -1;
+    int kind = CTG_ASSIGN_DENSE;
+    int64_t n = 0;               // dense: entries; sparse: pairs
+    uint64_t max_value = 0;      // the largest value (0: no entry)
+    uint64_t* table = nullptr;   // device
+    uint64_t size = 0;           // dense: n; sparse: slots
+};
+
 namespace ctg {
 
 // a result under construction: freed (ctg_free) unless release()d to the caller
@@ -597,6 +608,33 @@ hipError_t region_merge(Workspace& w, const double* rows, int64_t n, hipStream_t
 // labels [lb, le); either may be null
 hipError_t launch_region_rows(const ctg_result* r, uint64_t lb, uint64_t le, int form, double norm, double* out,
                               double* rows, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// applying an assignment (ctg_take.hip).  Call-sized pool buffers only, as the
+// label overlaps.
+// ---------------------------------------------------------------------------
+struct TakeArgs {               // one launch of k_take
+    const void* labels;         // n labels of the launch's width
+    uint64_t* out;              // n values, or null: check only
+    const int64_t* seg_begin;   // device: n_seg + 1 entries, ascending from 0 to n
+    const uint64_t* seg_off;    // device: the label offset of each segment
+    const uint32_t* prefix;     // device: workgroups before each segment (ctg_plan.h: take_chunk_prefix)
+    int n_seg;
+    const uint64_t* table;      // dense: the table; sparse: the hash table of ctg_take.h
+    uint64_t size;              // dense: its entries; sparse: its slots
+    unsigned long long* seg_nonzero;   // device, zeroed: nonzero input voxels, nz_slots partial counts per segment
+    int nz_slots;               // a power of two (ctg_plan.h: take_count_slots); workgroup w adds to slot w mod nz_slots
+    unsigned long long* missing;       // device: [0] missing voxels (zeroed), [1] the smallest missing label (all ones)
+    int par;                    // parity of the labels' address in elements: pairs start where index + par is even
+    int wide_store;             // such pairs are 16-byte aligned in out, too
+};
+// n (key, value) pairs into the zeroed-to-free table of cap slots; stat[0]
+// counts the duplicates, stat[1] folds the largest value (both zeroed before)
+hipError_t launch_take_build(const uint64_t* keys, const uint64_t* vals, int64_t n, uint64_t* table, uint64_t cap,
+                             unsigned long long* stat, hipStream_t s);
+hipError_t launch_take_max(const uint64_t* table, int64_t n, unsigned long long* stat, hipStream_t s);
+// chunks: prefix[n_seg], the launch's workgroups
+hipError_t launch_take(const TakeArgs& A, int label_bits, bool dense, uint32_t chunks, hipStream_t s);
 
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,

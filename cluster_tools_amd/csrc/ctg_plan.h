@@ -259,6 +259,66 @@ inline uint32_t bloom_blocks(int64_t n_edges) {
 }
 
 // ---------------------------------------------------------------------------
+// applying an assignment (ctg_take.hip)
+// ---------------------------------------------------------------------------
+// voxels a workgroup of the apply kernel takes: 256 lanes x 2 voxels x 8 steps
+constexpr int64_t TAKE_CHUNK = 4096;
+
+// slots of the hash table of n (key, value) pairs: a power of two of at least
+// 2 n, so linear probing always meets a free slot, and at least 64
+inline uint64_t take_capacity(int64_t n) {
+    uint64_t cap = 64;
+    while (cap < 2 * (uint64_t)std::max<int64_t>(n, 0)) cap *= 2;
+    return cap;
+}
+
+// Partial counters per segment for the nonzero voxels: a wave adds its count
+// once, and adds to one address queue up behind each other (about 12 ns each:
+// 2^20 waves of a 1024^3 volume took 12.8 ms on one counter, DESIGN.md 5
+// "Write"), so the workgroups of a segment spread over this many counters,
+// which the host sums.  One where the segments are many -- and then short.
+inline int take_count_slots(int64_t n_seg) { return n_seg <= 4096 ? 64 : 1; }
+
+struct TakeChunks {
+    // BAD_SEGMENTS: seg_begin does not ascend from 0 to n; TOO_MANY_CHUNKS: the
+    // launch would pass 2^31 - 1 workgroups
+    enum Error { OK, BAD_SEGMENTS, TOO_MANY_CHUNKS } error = OK;
+    std::vector<uint32_t> prefix;   // chunks of the launch before segment k; n_seg + 1 entries
+};
+
+// The workgroups of one apply launch over the segments [seg_begin[k],
+// seg_begin[k + 1]) of a flat array of n voxels: segment k gets
+// ceil(length / chunk) of them, none where it is empty.  seg_begin null: one
+// segment [0, n) (n_seg is not looked at).
+inline TakeChunks take_chunk_prefix(const int64_t* seg_begin, int64_t n_seg, int64_t n, int64_t chunk) {
+    TakeChunks t;
+    const int64_t whole[2] = {0, n};
+    if (!seg_begin) {
+        seg_begin = whole;
+        n_seg = 1;
+    }
+    if (n_seg < 0 || n < 0 || (n_seg == 0 && n != 0) || (n_seg > 0 && (seg_begin[0] != 0 || seg_begin[n_seg] != n))) {
+        t.error = TakeChunks::BAD_SEGMENTS;
+        return t;
+    }
+    t.prefix.assign((size_t)n_seg + 1, 0);
+    for (int64_t k = 0; k < n_seg; ++k) {
+        const int64_t len = seg_begin[k + 1] - seg_begin[k];
+        if (len < 0) {
+            t.error = TakeChunks::BAD_SEGMENTS;
+            return t;
+        }
+        const int64_t c = (len + chunk - 1) / chunk;
+        if ((int64_t)t.prefix[k] + c > 0x7FFFFFFFll) {
+            t.error = TakeChunks::TOO_MANY_CHUNKS;
+            return t;
+        }
+        t.prefix[k + 1] = t.prefix[k] + (uint32_t)c;
+    }
+    return t;
+}
+
+// ---------------------------------------------------------------------------
 // the multi-GPU exchange's count matrix: counts_all[(src * world + dst) * 2]
 // rows and [.. + 1] nodes of src's table that dst owns
 // ---------------------------------------------------------------------------

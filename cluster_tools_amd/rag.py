@@ -969,6 +969,164 @@ def region_feature_rows(handle_or_tables, label_begin, label_end, form='features
     return out
 
 
+class Assignment:
+    """Owning wrapper around a ``ctg_assignment*`` handle: a node assignment in
+    device memory (assignment_dense, assignment_sparse), uploaded once and
+    applied to any number of label arrays (apply_assignment)."""
+
+    def __init__(self, handle, device):
+        self.handle = handle
+        self.device = device
+        n, mx, kind = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_int()
+        L.check(L.load().ctg_assignment_info(handle, ctypes.byref(n), ctypes.byref(mx), ctypes.byref(kind)),
+                'ctg_assignment_info')
+        self.n = int(n.value)                   # entries of a dense table / pairs of a sparse one
+        self.max_value = int(mx.value)          # the largest value (0: empty)
+        self.kind = 'sparse' if kind.value == L.CTG_ASSIGN_SPARSE else 'dense'
+
+    def __del__(self):
+        self.free()
+
+    def free(self):
+        if getattr(self, 'handle', None) and L is not None:
+            L.load().ctg_assignment_free(self.handle)
+            self.handle = None
+
+
+def _u64_vector(x, name):
+    """A 1-D table argument -> (array, on_device): a contiguous 64-bit integer
+    CUDA tensor as it is, anything else as a contiguous uint64 numpy array."""
+    if _is_torch(x):
+        if not (x.is_cuda and x.is_contiguous()) or x.element_size() != 8 or x.is_floating_point() or x.dim() != 1:
+            raise ValueError('%s must be a contiguous 1-D CUDA tensor of 64-bit integers' % name)
+        return x, True
+    x = np.asarray(x)
+    if x.dtype.kind not in 'ui' and x.size:
+        raise TypeError('%s must hold integers, got %s' % (name, x.dtype))
+    if x.ndim != 1:
+        raise ValueError('%s must be 1-D, got shape %s' % (name, x.shape))
+    if x.dtype.kind == 'i' and x.size and int(x.min()) < 0:
+        raise ValueError('%s holds negative values' % name)
+    return np.ascontiguousarray(x, dtype=np.uint64), False
+
+
+def assignment_dense(table, stream=None):
+    """ctg_assignment_dense: A(l) = table[l] (what nifty.tools.take indexes);
+    labels of len(table) and above are out of range."""
+    table, on_dev = _u64_vector(table, 'table')
+    lib = L.load()
+    dev = L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_assignment_dense(_ptr(table), int(table.shape[0]), L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
+                                  stream, ctypes.byref(h))
+    L.check(rc, 'ctg_assignment_dense')
+    return Assignment(h, dev)
+
+
+def assignment_sparse(keys, values, stream=None):
+    """ctg_assignment_sparse: A(keys[i]) = values[i] (the dict that
+    nifty.tools.takeDict reads), keys in any order.  A key given twice is an
+    error; 0 is a key like any other."""
+    keys, on_dev = _u64_vector(keys, 'keys')
+    values, v_dev = _u64_vector(values, 'values')
+    if on_dev != v_dev:
+        raise ValueError('keys and values must both be numpy arrays or both CUDA tensors')
+    if keys.shape[0] != values.shape[0]:
+        raise ValueError('%d keys for %d values' % (keys.shape[0], values.shape[0]))
+    lib = L.load()
+    dev = L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    h = ctypes.c_void_p()
+    rc = lib.ctg_assignment_sparse(_ptr(keys), _ptr(values), int(keys.shape[0]),
+                                   L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+    L.check(rc, 'ctg_assignment_sparse')
+    return Assignment(h, dev)
+
+
+def apply_assignment(a, labels, offset=0, segments=None, allow_missing=False, out=None, check_only=False, stream=None):
+    """ctg_apply_assignment: out[i] = A(labels[i] + off) with zeros unshifted,
+    over the flattened (C-order) ``labels`` -- a numpy array or a CUDA tensor of
+    32- or 64-bit integers, of any shape.
+
+    ``offset``: the label offset of the whole array; or ``segments`` =
+    (seg_begin, seg_offset): segment k is the flat range [seg_begin[k],
+    seg_begin[k + 1]) with its own offset (the blocks of a job in one call).
+    ``out``: None (a new uint64 array / int64 tensor of the labels' shape), an
+    array of the same kind and size, or ``labels`` itself (in place, 64-bit
+    labels).  ``check_only``: nothing is written, the counts alone.
+    A label without an entry raises KeyError (sparse) or IndexError (dense)
+    naming the smallest one, unless ``allow_missing`` (sparse only): such voxels
+    then keep their shifted label.
+
+    Returns (out, info): out is None with ``check_only``; info = dict(nonzero =
+    the nonzero input voxels per segment (uint64 array; one entry without
+    segments), n_missing, first_missing (None if none))."""
+    if not isinstance(a, Assignment) or not a.handle:
+        raise TypeError('a must be a live Assignment')
+    labels, bits = _label_volume(labels, 'labels')
+    on_dev = _is_torch(labels)
+    n = int(labels.numel()) if on_dev else int(labels.size)
+    if segments is not None:
+        if offset:
+            raise ValueError('give offset or segments, not both')
+        seg_begin = np.ascontiguousarray(np.asarray(segments[0], dtype=np.int64).reshape(-1))
+        seg_off = np.ascontiguousarray(np.asarray(segments[1], dtype=np.uint64).reshape(-1))
+        if seg_begin.shape[0] != seg_off.shape[0] + 1:
+            raise ValueError('segments: %d begins for %d offsets (need one more)' % (seg_begin.shape[0], seg_off.shape[0]))
+        n_seg = int(seg_off.shape[0])
+    else:
+        if not 0 <= int(offset) < 1 << 64:
+            raise ValueError('offset must be a uint64 value, got %r' % (offset,))
+        seg_begin = np.array([0, n], dtype=np.int64)
+        seg_off = np.array([int(offset)], dtype=np.uint64)
+        n_seg = 1
+    if allow_missing and a.kind != 'sparse':
+        raise ValueError('allow_missing needs a sparse assignment')
+    if check_only:
+        if out is not None:
+            raise ValueError('check_only writes nothing: out must be None')
+    elif out is None:
+        if on_dev:
+            import torch
+            out = torch.empty(tuple(labels.shape), dtype=torch.int64, device=labels.device)
+        else:
+            out = np.empty(labels.shape, dtype=np.uint64)
+    else:
+        if _is_torch(out) != on_dev:
+            raise ValueError('out must be of the same kind as labels (numpy array or CUDA tensor)')
+        if on_dev:
+            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
+            size = int(out.numel())
+        else:
+            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
+            size = int(out.size) if ok else -1
+        if not ok or size != n:
+            raise ValueError('out must be a contiguous 64-bit integer array of the size of labels')
+        if bits != 64 and _ptr(out).value == _ptr(labels).value and n:
+            raise ValueError('in place needs 64-bit labels')
+    lib = L.load()
+    L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    nonzero = np.zeros(max(n_seg, 1), dtype=np.uint64)
+    missing = np.zeros(2, dtype=np.uint64)
+    rc = lib.ctg_apply_assignment(a.handle, _ptr(labels), bits, n, _ptr(seg_begin), _ptr(seg_off), n_seg,
+                                  int(bool(allow_missing)), _ptr(out), _ptr(nonzero), _ptr(missing),
+                                  L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream)
+    if rc == L.CTG_ERR_MISSING:
+        msg = '%d: the smallest of the labels without an entry (%d voxel(s))' % (int(missing[1]), int(missing[0]))
+        if a.kind == 'sparse':
+            raise KeyError(msg)
+        raise IndexError(msg + '; the table has %d entries' % a.n)
+    L.check(rc, 'ctg_apply_assignment')
+    info = dict(nonzero=nonzero[:n_seg], n_missing=int(missing[0]),
+                first_missing=int(missing[1]) if missing[0] else None)
+    return out, info
+
+
 def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_offset=0, noise_amp=0.1,
                  with_boundary=True, device=None):
     """Generate the synthetic volume directly in HBM (torch tensors)."""

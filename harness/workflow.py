@@ -21,6 +21,11 @@ and ``NodeLabelWorkflow`` (node_labels/node_label_workflow.py), full-volume labe
     BlockNodeLabels    node_labels/block_node_labels.py:48-102, job :133-165
     MergeNodeLabels    node_labels/merge_node_labels.py:42-88, job :121-156
 
+and the last task of every segmentation workflow, ``WriteWorkflow`` / ``RelabelWorkflow``:
+
+    Write              write/write.py:68-127, job :292-387
+    FindUniques, MergeUniques, FindLabeling   relabel/find_uniques.py, merge_uniques.py, find_labeling.py
+
 Job execution (``mode``):
   * ``'processes'`` -- the reference's process model: ``LocalTask._submit``
     starts every job as its own process (``call([script, config])`` in a
@@ -570,4 +575,129 @@ def edge_features_workflow(input_path, input_key, labels_path, labels_key, graph
         if n_edges:
             _run_jobs(functools.partial(_merge_features_job, graph_path, output_path, output_key, block_list,
                                         threads_per_job), runs, mode)
+    return timer
+
+
+# ------------------------------------------------------------------ write / relabel
+def _write_job(input_path, input_key, output_path, output_key, block_shape, assignment_path, assignment_key,
+               offset_path, allow_empty_assignments, threads_per_job, job_id, blocks):
+    """write/write.py:292-387 (write) with _write / _write_with_offsets :204-246.
+    output_path None: in place (:303-309)."""
+    from cluster_tools_amd import write
+    a = write.load_assignments(assignment_path, assignment_key, threads_per_job)       # :319-323
+    import contextlib
+    import json
+    try:
+        offsets, empty_blocks = None, ()
+        if offset_path is not None:                                                   # :209-213
+            with open(offset_path) as f:
+                offset_config = json.load(f)
+            offsets, empty_blocks = offset_config['offsets'], set(offset_config['empty_blocks'])
+        in_place = output_path is None
+        one_file = in_place or input_path == output_path                               # :349-352: opened once
+        with contextlib.ExitStack() as files:
+            f_in = files.enter_context(ndist._open(input_path, 'a' if one_file else 'r'))
+            ds_in = f_in[input_key]
+            if ds_in.attrs.get('isLabelMultiset', False):
+                raise RuntimeError('label multiset input is not supported')
+            f_out = f_in if one_file else files.enter_context(ndist._open(output_path))
+            ds_out = ds_in if in_place else f_out[output_key]
+            blk = blocking([0, 0, 0], list(ds_in.shape), list(block_shape))            # :336
+            for b in blocks:
+                if b in empty_blocks:                                                 # :219
+                    continue
+                block = blk.getBlock(b)
+                bb = tuple(slice(x, y) for x, y in zip(block.begin, block.end))
+                write.write_block(ds_in, ds_out, bb, a, None if offsets is None else offsets[b],
+                                  allow_empty_assignments)
+            if job_id == 0:                                                           # :344-345, :383-384
+                write.write_max_id(ds_out, a)
+    finally:
+        a.free()
+
+
+def _write_job_k(args, job):
+    job_id, blocks = job
+    return _write_job(*args, job_id, blocks)
+
+
+def write_workflow(input_path, input_key, output_path, output_key, assignment_path, assignment_key, block_shape,
+                   offset_path=None, allow_empty_assignments=False, chunks=None, max_jobs=1, threads_per_job=1,
+                   timer=None, mode='threads'):
+    """WriteBase.run_impl (write/write.py:68-127): the uint64 output dataset
+    with chunks of half a block (:80-81) unless it exists (:85-86), then the
+    jobs.  Input and output the same dataset: in place (:93)."""
+    timer = timer or Timer()
+    with ndist._open(input_path, 'r') as f:
+        shape = list(f[input_key].shape)                                              # :74-76
+    if chunks is None:
+        chunks = tuple(min(bs // 2, sh) for bs, sh in zip(block_shape, shape))        # :80-81
+    with ndist._open(output_path) as f:                                               # :84-90
+        if output_key in f:
+            chunks = tuple(f[output_key].chunks)
+        if not all(bs % ch == 0 for bs, ch in zip(block_shape, chunks)):
+            raise ValueError('%s, %s' % (str(block_shape), str(chunks)))
+        f.require_dataset(output_key, shape=tuple(shape), chunks=tuple(chunks), compression='gzip', dtype='uint64')
+    in_place = input_path == output_path and input_key == output_key                  # :93
+    if assignment_key is None and not assignment_path.endswith('.pkl'):               # :95-97
+        raise ValueError('Assignments need to be pickled map if no key is given')
+    args = (input_path, input_key, None if in_place else output_path, None if in_place else output_key,
+            list(block_shape), assignment_path, assignment_key, offset_path, allow_empty_assignments, threads_per_job)
+    block_list = blocks_in_volume(shape, block_shape)                                 # :110-111
+    with timer.stage('write'):
+        _run_jobs(functools.partial(_write_job_k, args), list(enumerate(_jobs(block_list, max_jobs))), mode)
+    return timer
+
+
+def _find_uniques_job(input_path, input_key, block_shape, blocks):
+    """relabel/find_uniques.py:98-170: the job's unique ids (returned instead of
+    saved as find_uniques_job_<id>.npy)."""
+    from cluster_tools_amd import rag
+    parts = []
+    with ndist._open(input_path, 'r') as f:
+        ds = f[input_key]
+        blk = blocking([0, 0, 0], list(ds.shape), list(block_shape))
+        for b in blocks:
+            block = blk.getBlock(b)
+            parts.append(rag.unique_labels(ds[tuple(slice(x, y) for x, y in zip(block.begin, block.end))]))
+    if not parts:
+        return np.zeros(0, dtype=np.uint64)
+    r = rag.unique_values_handle(np.concatenate(parts))                               # :165
+    try:
+        return r.nodes()
+    finally:
+        r.free()
+
+
+def relabel_workflow(input_path, input_key, assignment_path, assignment_key, block_shape, output_path=None,
+                     output_key=None, max_jobs=1, threads_per_job=1, timer=None, mode='threads'):
+    """RelabelWorkflow (relabel/relabel_workflow.py): FindUniques per block,
+    MergeUniques (merge_uniques.py:104-106), FindLabeling -- the (n, 2) table
+    old id -> 1 .. N with 0 kept (find_labeling.py:106-116), saved as
+    ``assignment_key`` -- then Write, in place unless an output is named."""
+    from cluster_tools_amd import rag
+    timer = timer or Timer()
+    with ndist._open(input_path, 'r') as f:
+        shape = list(f[input_key].shape)
+    block_list = blocks_in_volume(shape, block_shape)
+    with timer.stage('find_uniques'):
+        job = functools.partial(_find_uniques_job, input_path, input_key, list(block_shape))
+        parts = _run_jobs(job, _jobs(block_list, max_jobs), mode)
+    with timer.stage('find_labeling'):
+        r = rag.unique_values_handle(np.concatenate(parts))                           # find_labeling.py:103-106
+        try:
+            uniques = r.nodes()
+        finally:
+            r.free()
+        start = 0 if len(uniques) and uniques[0] == 0 else 1                          # :108-113
+        new_ids = np.arange(start, start + len(uniques), dtype=np.uint64)
+        assignments = np.stack([uniques, new_ids], axis=1)                            # :115-116
+        with ndist._open(assignment_path) as f:                                       # :119-125
+            chunk_size = max(1, min(int(1e6), len(assignments)))
+            ds = f.require_dataset(assignment_key, shape=assignments.shape, dtype='uint64', compression='gzip',
+                                   chunks=(chunk_size, 2))
+            ds[:] = assignments
+    write_workflow(input_path, input_key, output_path or input_path, output_key or input_key, assignment_path,
+                   assignment_key, block_shape, max_jobs=max_jobs, threads_per_job=threads_per_job, timer=timer,
+                   mode=mode)
     return timer

@@ -37,6 +37,10 @@
  *                                        features/region_features.py:159-171
  *   ctg_merge_region_features, ctg_region_rows <- _extract_and_merge_region_features
  *                                        features/merge_region_features.py:109-158
+ *   ctg_assignment_dense, ctg_apply_assignment  <- nifty.tools.take, write/write.py:164-166
+ *   ctg_assignment_sparse, ctg_apply_assignment <- np.unique, the dict and nifty.tools.takeDict,
+ *                                        write/write.py:170-181
+ *   ctg_assignment_info               <- _write_maxlabel, write/write.py:281-289
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -407,6 +411,61 @@ int ctg_region_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_en
  * (the feats['count'] ... arrays of features/region_features.py:170) */
 int ctg_result_copy_region(const ctg_result* r, uint64_t* counts, double* sums, float* minmax, int mem);
 
+/*
+ * Write (WriteWorkflow, and every task that ends in nifty.tools.take /
+ * takeDict): a node assignment A, uploaded once, and its application to label
+ * arrays, out[i] = A(labels[i] + (labels[i] != 0 ? offset : 0)).
+ *
+ * ctg_assignment_dense   <- the table that nifty.tools.take indexes, write/write.py:164-166:
+ *                           A(l) = table[l]; l >= n is out of range (the assert of write.py:164).
+ *                           The handle holds a copy of the table.
+ * ctg_assignment_sparse  <- the dict of write/write.py:170-181 (np.unique, the dict
+ *                           comprehension, nifty.tools.takeDict): A(keys[i]) = values[i], keys in
+ *                           any order.  A key given twice is CTG_ERR_ARG, the message holds the
+ *                           count.  0 is a key like any other: without it, zero voxels are missing.
+ * ctg_assignment_info    <- _write_maxlabel, write/write.py:281-289: n entries / pairs, the
+ *                           largest value (0 for an empty assignment) and the kind; each
+ *                           destination may be NULL
+ * ctg_assignment_free    a NULL handle is fine
+ */
+#define CTG_ASSIGN_DENSE 0
+#define CTG_ASSIGN_SPARSE 1
+#define CTG_ERR_MISSING -6   /* ctg_apply_assignment: a label without an entry (the outputs are written all the same) */
+typedef struct ctg_assignment ctg_assignment;
+int ctg_assignment_dense(const uint64_t* table, int64_t n, int mem, void* stream, ctg_assignment** out);
+int ctg_assignment_sparse(const uint64_t* keys, const uint64_t* values, int64_t n, int mem, void* stream,
+                          ctg_assignment** out);
+int ctg_assignment_info(const ctg_assignment* a, int64_t* n, uint64_t* max_value, int* kind);
+void ctg_assignment_free(ctg_assignment* a);
+
+/* Apply an assignment to a flat array of n labels (write/write.py:194-200 with
+ * the lookups of :166 / :181; one call serves the blocks of a job).
+ *   labels      n labels, uint64 (label_bits = 64) or uint32 (32), aligned to their size
+ *   seg_begin   NULL: one segment [0, n) without offset (n_seg is not looked at).  Else
+ *               n_seg + 1 host entries that ascend from 0 to n: segment k is
+ *               [seg_begin[k], seg_begin[k + 1]) and nonzero labels in it are shifted by
+ *               seg_offset[k] (host, n_seg entries) before the lookup; an empty segment is fine
+ *   out         n uint64 values (`mem` as labels), or NULL: check only -- the same
+ *               counts, nothing written.  out == labels (64-bit labels) works in place.
+ *   seg_nonzero host, one word per segment: its nonzero input voxels (write.py:230
+ *               skips blocks where it is 0)
+ *   missing     host, 2 words: [0] the voxels whose shifted label is out of range
+ *               (dense) or absent (sparse), [1] the smallest such label (0 if none).  A
+ *               shift that wraps past 2^64 always counts, with the unshifted label as
+ *               its candidate for [1].
+ * A missing voxel's output is its shifted label.  With allow_missing (sparse
+ * only: allow_empty_assignments, write.py:173-174) that is the result and the
+ * call succeeds, missing[] still reporting them; otherwise any missing voxel makes the
+ * call CTG_ERR_MISSING, the message naming the count and the smallest label,
+ * with every output written.  Argument errors (CTG_ERR_ARG) are found before
+ * any GPU work: null pointers, label_bits, n < 0, a seg_begin that does not
+ * ascend from 0 to n, allow_missing with a dense assignment, in place with
+ * 32-bit labels, misaligned arrays.  The call uses call-sized buffers only: a
+ * CTG_DEFER_STATS handle of the same device stays valid across it. */
+int ctg_apply_assignment(const ctg_assignment* a, const void* labels, int label_bits, int64_t n,
+                         const int64_t* seg_begin, const uint64_t* seg_offset, int64_t n_seg, int allow_missing,
+                         uint64_t* out, uint64_t* seg_nonzero, uint64_t* missing, int mem, void* stream);
+
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
                      const uint64_t* query, int64_t n_query, int64_t* out_ids,
@@ -499,7 +558,7 @@ int ctg_trim(void);
  * (HIP events on the call's stream): [0] face scan, [1] key pack, [2] sort,
  * [3] segment, [4] reduce+finalize, [5] nodes, [6] total; of a ctg_label_overlaps,
  * ctg_morphology or ctg_region_features call: [0] scan, [2] sort, [3] run heads + prefix sums,
- * [4] run sums / folds, [6] total */
+ * [4] run sums / folds, [6] total; of a ctg_apply_assignment call: [0] = [6] the kernel */
 int ctg_set_profiling(int on);
 int ctg_last_timings(double* ms, int n);
 
