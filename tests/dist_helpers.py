@@ -6,6 +6,8 @@ cluster_tools_amd/dist.py runs unchanged on CPU tensors.
 """
 from __future__ import annotations
 
+import bisect
+
 import numpy as np
 import torch
 
@@ -126,7 +128,7 @@ def splitters(meta_all, world):
         if cnt[r] == 0:
             continue
         v = m[r, :S]
-        cw = np.zeros(S, dtype=object)
+        cw = np.zeros(S, dtype=object)      # Python integers: no overflow at any count
         for q in range(world):
             if cnt[q] == 0:
                 continue
@@ -134,12 +136,30 @@ def splitters(meta_all, world):
             c = (np.searchsorted(row, v, side='right') if q < r else
                  np.searchsorted(row, v, side='left') if q > r else np.arange(1, S + 1))
             cw = cw + int(cnt[q]) * c.astype(object)
+        # the weight intervals ((cw - cnt_r) * W, cw * W] of this rank's samples
+        # ascend with j, so the one that holds t is found by bisection
+        hi = [int(a) * world for a in cw]
         for k in range(1, world):
             t = total * S * k
-            hit = [(int(a) - int(cnt[r])) * world < t <= int(a) * world for a in cw]
-            for j in np.nonzero(hit)[0]:
+            j = bisect.bisect_left(hi, t)
+            if j < S and hi[j] - int(cnt[r]) * world < t:
                 spl[k - 1] = np.uint64(v[j]) ^ SIGN
     return spl
+
+
+def slab_nodes(labels, own_begin):
+    """The node list of the library's local call on a slab (ctg_rag_features):
+    the endpoints of every key of the scan -- the faces whose upper voxel lies
+    in the owned box, before any ignore_label filter -- so a label of a halo
+    plane counts only where it is the lower voxel of such a face; a slab
+    without a single face has one node, the label of the owned box's first
+    voxel (the single-label fix of ctg_api_scan.hip), whatever its halo holds."""
+    lab = np.asarray(labels)
+    ends = np.unique(O.rag_edges(lab, own_begin=own_begin).reshape(-1)).astype(np.uint64)
+    if ends.size:
+        return ends
+    own = lab[tuple(slice(int(b), None) for b in own_begin)]
+    return own.reshape(-1)[:1].astype(np.uint64)
 
 
 def split_counts(part, spl, world):
@@ -155,12 +175,14 @@ class OracleBackend:
     oracle's statistics (ctg_mgpu_sample / split / pack / merge)."""
 
     def local(self, labels, data, offsets, own_begin, own_end, ignore_label, hist_range):
+        """The slab's partial table; its node list follows the library's rule
+        (slab_nodes: halo-plane labels count only through an owned face)."""
         lab = np.asarray(labels)
         edges, feats, stats = O.boundary_features(lab, np.asarray(data), own_begin=own_begin,
                                                   ignore_label=ignore_label, lo=hist_range[0], hi=hist_range[1],
                                                   return_stats=True)
         sums, rec = encode_stats(stats)
-        nodes = np.unique(edges.reshape(-1)).astype(np.uint64)
+        nodes = slab_nodes(lab, own_begin)
         return Part(edges.astype(np.uint64).reshape(-1, 2), np.ascontiguousarray(feats), sums, rec, nodes, False)
 
     def sample(self, part):
@@ -173,7 +195,11 @@ class OracleBackend:
         return torch.from_numpy(meta)
 
     def split(self, part, meta_all, world):
-        return torch.from_numpy(split_counts(part, splitters(meta_all.numpy(), world), world))
+        m = meta_all.numpy()
+        key = (world, m.tobytes())     # every rank splits by the same gathered samples: derive them once
+        if getattr(self, '_spl_key', None) != key:
+            self._spl_key, self._spl = key, splitters(m, world)
+        return torch.from_numpy(split_counts(part, self._spl, world))
 
     def pack(self, part, counts_all, world, rank, words):
         c = np.asarray(counts_all).reshape(world, world, 2)[rank]

@@ -375,3 +375,72 @@ def test_exchange_host_phases(tmp_path):
             ph = json.load(f)
         assert set(ph) == {'local', 'sample', 'splitters+counts', 'exchange', 'merge', 'free'}
         assert all(v >= 0.0 for v in ph.values())
+
+
+# ------------------------------------------------ adversarial label layouts
+# (tests/exchange_cases.py; the kernels run them in test_gpu_exchange_cases.py)
+def _exchange_case_params():
+    from tests import exchange_cases as X
+    return [(n, w) for n in X.BOUNDARY_CASES for w in X.WORLDS]
+
+
+@pytest.mark.parametrize('name,world', _exchange_case_params())
+def test_exchange_cases_restatement_matches_whole_volume(name, world):
+    """The numpy restatement of the four exchange steps on every named label
+    layout of tests/exchange_cases.py, at world sizes up to 32: the case holds
+    what it claims to force (check_case), and the shards concatenate to the
+    whole-volume oracle -- edges and the unique labels of the volume bit for
+    bit, features within this file's 1e-9 / 1e-12 (observed: 3e-16)."""
+    from tests import exchange_cases as X
+    from tests.dist_helpers import OracleBackend
+    from tests.exchange_sim import simulate
+    c = X.case(name)
+    assert world in c.worlds
+    X.check_case(name, world)
+    e_ref, f_ref = _case_reference(name)
+    shards = simulate(OracleBackend(), c.labels, X.case_data(name), world)
+    np.testing.assert_array_equal(np.concatenate([s.edges() for s in shards]), e_ref)
+    np.testing.assert_allclose(np.concatenate([s.features() for s in shards]), f_ref, rtol=1e-9, atol=1e-12)
+    np.testing.assert_array_equal(np.concatenate([s.nodes() for s in shards]), O.unique_labels(c.labels))
+
+
+_CASE_REF = {}
+
+
+def _case_reference(name):
+    from tests import exchange_cases as X
+    if name not in _CASE_REF:
+        _CASE_REF[name] = O.boundary_features(X.case(name).labels, X.case_data(name))
+    return _CASE_REF[name]
+
+
+def test_exchange_case_lr_adjacency_precondition():
+    """The hand-built long-range volume holds its three pairs where it says:
+    (A, B) and (A2, B2) touch in one rank's planes and are paired by the -2
+    offset only in another's, (C, D) never touch and are paired in two ranks'
+    planes -- and the whole-volume oracle counts the far rank's sample of
+    (A, B), and has no (C, D) row."""
+    from tests import exchange_cases as X
+    c = X.case('lr_adjacency')
+    X.check_case('lr_adjacency', X.LR_WORLD)
+    e, f = O.affinity_features(c.labels, X.case_data('lr_adjacency'), c.offsets)
+    rows = {tuple(int(t) for t in k): i for i, k in enumerate(e)}
+    for a, b in (('A', 'B'), ('A2', 'B2')):
+        assert f[rows[(X.LR[a], X.LR[b])], 9] == 2      # the face's sample and the -2 pairing's
+    assert (X.LR['C'], X.LR['D']) not in rows
+
+
+def test_slab_nodes_rule():
+    """The node list of a slab's local call as restated for the numpy backend:
+    edge endpoints (a halo label counts where a face reaches it), and the
+    owned box's first label where the slab has no face at all."""
+    from tests.dist_helpers import slab_nodes
+    lab = np.full((4, 2, 2), 7, np.uint64)
+    np.testing.assert_array_equal(slab_nodes(lab, (1, 0, 0)), [7])
+    lab[0] = 5                                          # the halo plane differs: faces (5, 7)
+    np.testing.assert_array_equal(slab_nodes(lab, (1, 0, 0)), [5, 7])
+    lab[0, 0, 0] = 9                                    # a label inside the halo plane only: no owned face between 9 and 5
+    np.testing.assert_array_equal(slab_nodes(lab, (1, 0, 0)), [5, 7, 9])
+    lab[:] = 7
+    lab[0, 0, 0] = 9                                    # own box [2, 4) uniform; no owned face reaches plane 0
+    np.testing.assert_array_equal(slab_nodes(lab, (2, 0, 0)), [7])
