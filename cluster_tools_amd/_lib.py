@@ -28,6 +28,9 @@ CTG_ERR_STALE = -5
 CTG_ERR_MISSING = -6
 CTG_ASSIGN_DENSE = 0
 CTG_ASSIGN_SPARSE = 1
+CTG_CC_GREATER = 0
+CTG_CC_LESS = 1
+CTG_CC_EQUAL = 2
 CTG_MAX_CHANNELS = 24
 CTG_N_FEATURES = 10
 CTG_NBINS = 40
@@ -107,6 +110,10 @@ PROTOTYPES = {
     'ctg_assignment_free': (None, [c_vp]),
     'ctg_apply_assignment': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, ctypes.c_int64,
                                             ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, c_vp]),
+    'ctg_threshold_components': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_float,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
+                                                c_u64p]),
+    'ctg_merge_assignments': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_uint64, c_vp, ctypes.c_int, c_vp, c_u64p]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

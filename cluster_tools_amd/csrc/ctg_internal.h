@@ -636,6 +636,49 @@ hipError_t launch_take_max(const uint64_t* table, int64_t n, unsigned long long*
 // chunks: prefix[n_seg], the launch's workgroups
 hipError_t launch_take(const TakeArgs& A, int label_bits, bool dense, uint32_t chunks, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// thresholded components (ctg_cc.hip).  Call-sized pool buffers only, as the
+// label overlaps.
+// ---------------------------------------------------------------------------
+// The words of a call's small device block: the box's value range as f2ord
+// words and its NaN flag, the error word (bit 0: a find or union passed its
+// step cap; bit 1: a pair member that is 0 or not below n_labels), the number
+// of sets
+enum CcWord : int { CC_W_MIN = 0, CC_W_MAX = 1, CC_W_NAN = 2, CC_W_ERR = 3, CC_W_TOTAL = 4, CC_WORDS = 8 };
+constexpr uint32_t CC_ERR_CAP = 1u, CC_ERR_PAIR = 2u;
+struct CcArgs {                 // the box of a labelling call
+    const void* data;           // the array's samples (float32 or uint8)
+    const uint8_t* mask;        // the array's mask, or null
+    int64_t s_z, s_y;           // the array's strides in elements
+    int64_t base;               // element offset of the box's first voxel
+    uint32_t n[3];              // the box (z, y, x)
+    uint32_t nt[3];             // its tiles (ctg_plan.h: cc_grid)
+    float threshold;
+    int mode;                   // CTG_CC_*
+    uint32_t* words;            // device: CcWord
+    uint32_t* parent;           // device: one entry per voxel of the box, box-linear
+};
+// the smallest and largest sample of the box and whether it holds a NaN
+hipError_t launch_cc_range(const CcArgs& A, int data_kind, hipStream_t s);
+// per tile: threshold, label in LDS, each foreground voxel's tile root into parent (background: UF_NONE)
+hipError_t launch_cc_tile(const CcArgs& A, const CcGrid& G, int data_kind, int normalize, int conn, hipStream_t s);
+// the unions across tile borders
+hipError_t launch_cc_seams(const CcArgs& A, const CcGrid& G, int conn, hipStream_t s);
+// n parent entries = their own index
+hipError_t launch_uf_init(uint32_t* parent, int64_t n, hipStream_t s);
+// one union per (a, b) pair; a member that is 0 or >= n_labels raises CC_ERR_PAIR instead
+hipError_t launch_uf_pairs(const uint64_t* pairs, int64_t n, uint32_t* parent, uint32_t n_labels, uint32_t* words,
+                           hipStream_t s);
+// every node's root into parent; each root's rank within its CC_SEG-node segment into rank, the roots of
+// each segment into seg
+hipError_t launch_uf_flatten(uint32_t* parent, int64_t n, uint32_t* rank, uint32_t* seg, uint32_t* words,
+                             hipStream_t s);
+// seg -> its exclusive prefix, the sum into words[CC_W_TOTAL]
+hipError_t launch_uf_scan(uint32_t* seg, int64_t n_seg, uint32_t* words, hipStream_t s);
+// out[i] = rank of i's root among all roots + plus; 0 where parent[i] is UF_NONE
+hipError_t launch_uf_write(const uint32_t* parent, const uint32_t* rank, const uint32_t* seg, int64_t n,
+                           uint64_t plus, uint64_t* out, hipStream_t s);
+
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,
                       int world, uint64_t* spl, int64_t* counts, hipStream_t s);

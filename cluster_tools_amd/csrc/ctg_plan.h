@@ -319,6 +319,93 @@ inline TakeChunks take_chunk_prefix(const int64_t* seg_begin, int64_t n_seg, int
 }
 
 // ---------------------------------------------------------------------------
+// thresholded components (ctg_cc.hip)
+// ---------------------------------------------------------------------------
+// a labelling tile: TILE_X x CC_TILE_Y x CC_TILE_Z voxels, a wave per row
+constexpr int CC_TILE_Y = 8, CC_TILE_Z = 16;
+constexpr int CC_ROWS = CC_TILE_Y * CC_TILE_Z;
+// nodes a wave of the numbering pass takes, 64 a step.  2048: the one-workgroup scan of the
+// segments' root counts took 0.31 ms of a 512^3 call with 512
+constexpr int64_t CC_SEG = 2048;
+// node indices are u32 and 0xFFFFFFFF marks the background: boxes and label
+// counts stay below 2^32
+constexpr int64_t CC_MAX_NODES = 1ll << 32;
+inline bool cc_nodes_fit(uint64_t n) { return n < (uint64_t)CC_MAX_NODES; }
+inline int64_t cc_segments(int64_t nodes) { return (nodes + CC_SEG - 1) / CC_SEG; }
+
+// The earlier rows (dz, dy) of a tile that a row is united with, and whether
+// the neighbour row is dilated by one in x.  Connectivity c joins voxels with
+// 0 < |dz| + |dy| + |dx| <= c: 1: the two straight rows, undilated; 2: those
+// dilated, the two diagonal rows undilated; 3: all four dilated.
+struct CcRows {
+    int n;
+    int dz[4], dy[4], dil[4];
+};
+constexpr CcRows cc_neighbor_rows(int c) {
+    return c <= 1 ? CcRows{2, {0, -1, 0, 0}, {-1, 0, 0, 0}, {0, 0, 0, 0}}
+         : c == 2 ? CcRows{4, {0, -1, -1, -1}, {-1, 0, -1, 1}, {1, 1, 0, 0}}
+                  : CcRows{4, {0, -1, -1, -1}, {-1, 0, -1, 1}, {1, 1, 1, 1}};
+}
+
+struct CcGrid {
+    int64_t nt[3];     // tiles along z, y, x
+    int64_t tiles;
+    // voxels on the low x, y, z face of a tile that has a tile below it on that
+    // axis: one seam thread each (a voxel on two faces is counted on both and
+    // taken by the first)
+    int64_t seam[3];
+    int64_t seam_threads;
+    int64_t segs;      // waves of the numbering pass
+};
+// n: the box (z, y, x)
+inline CcGrid cc_grid(const int64_t* n) {
+    CcGrid g{};
+    g.nt[0] = (n[0] + CC_TILE_Z - 1) / CC_TILE_Z;
+    g.nt[1] = (n[1] + CC_TILE_Y - 1) / CC_TILE_Y;
+    g.nt[2] = (n[2] + TILE_X - 1) / TILE_X;
+    g.tiles = g.nt[0] * g.nt[1] * g.nt[2];
+    const bool some = g.tiles > 0;
+    g.seam[0] = some ? (g.nt[2] - 1) * n[0] * n[1] : 0;
+    g.seam[1] = some ? (g.nt[1] - 1) * n[0] * n[2] : 0;
+    g.seam[2] = some ? (g.nt[0] - 1) * n[1] * n[2] : 0;
+    g.seam_threads = g.seam[0] + g.seam[1] + g.seam[2];
+    g.segs = cc_segments(n[0] * n[1] * n[2]);
+    return g;
+}
+
+// Seam thread i of a box with n1 x n2 voxels per plane: first the x faces
+// (every 64th column), then the y faces, then the z faces.  take: false for a
+// voxel that an earlier face holds already.
+struct CcSeamVoxel {
+    bool take;
+    int64_t z, y, x;
+};
+constexpr CcSeamVoxel cc_seam_voxel(const CcGrid& g, int64_t n1, int64_t n2, int64_t i) {
+    if (i < g.seam[0]) {
+        const int64_t k = i % (g.nt[2] - 1), r = i / (g.nt[2] - 1);
+        return {true, r / n1, r % n1, (k + 1) * TILE_X};
+    }
+    i -= g.seam[0];
+    if (i < g.seam[1]) {
+        const int64_t x = i % n2, r = i / n2;
+        return {!(x && x % TILE_X == 0), r / (g.nt[1] - 1), (r % (g.nt[1] - 1) + 1) * CC_TILE_Y, x};
+    }
+    i -= g.seam[1];
+    const int64_t x = i % n2, r = i / n2, y = r % n1;
+    return {!((x && x % TILE_X == 0) || (y && y % CC_TILE_Y == 0)), (r / n1 + 1) * CC_TILE_Z, y, x};
+}
+// Whether the voxel at (z, y, x) takes its neighbour at offset (dz, dy, dx): a
+// neighbour of connectivity c that lies across a low face of the voxel's tile.
+// Of every neighbour pair that spans two tiles, one voxel sits on the low face
+// between them, so these are all the unions the tiles left out.
+constexpr bool cc_seam_partner(int c, int64_t z, int64_t y, int64_t x, int dz, int dy, int dx) {
+    const int norm = (dz != 0) + (dy != 0) + (dx != 0);
+    if (norm == 0 || norm > c) return false;
+    return (dx == -1 && x && x % TILE_X == 0) || (dy == -1 && y && y % CC_TILE_Y == 0) ||
+           (dz == -1 && z && z % CC_TILE_Z == 0);
+}
+
+// ---------------------------------------------------------------------------
 // the multi-GPU exchange's count matrix: counts_all[(src * world + dst) * 2]
 // rows and [.. + 1] nodes of src's table that dst owns
 // ---------------------------------------------------------------------------

@@ -1127,6 +1127,128 @@ def apply_assignment(a, labels, offset=0, segments=None, allow_missing=False, ou
     return out, info
 
 
+CC_MODES = {'greater': L.CTG_CC_GREATER, 'less': L.CTG_CC_LESS, 'equal': L.CTG_CC_EQUAL}
+
+
+def threshold_components(data, threshold, mode='greater', mask=None, normalize=True, connectivity=3, begin=None,
+                         end=None, out=None, stream=None):
+    """ctg_threshold_components: the connected components of the thresholded
+    box [begin, end) of ``data`` -> (labels, n).
+
+    ``data``: a (Z,Y,X) numpy array or contiguous CUDA tensor, float32 or uint8.
+    A voxel is foreground where ``v > threshold`` / ``v < threshold`` /
+    ``v == threshold`` (``mode`` 'greater', 'less', 'equal', in float32) and,
+    with a ``mask`` (same shape and kind as data, bool or uint8), the mask is
+    nonzero.  ``v`` is the sample, or with ``normalize`` the value of
+    vu.normalize over the box (utils/volume_utils.py:98-105); a NaN in a
+    normalised box gives the empty result, as numpy's minimum does.
+    ``connectivity`` 1, 2, 3: 6, 18 or 26 neighbours (skimage's label on a
+    boolean array: 3).  ``labels``: box-shaped uint64 (an int64 tensor for
+    tensors; ``out`` to write into an existing one), 0 for the background, the
+    components numbered 1 .. n in raster order of their first voxels, which is
+    scipy.ndimage.label's numbering."""
+    if mode not in CC_MODES:
+        raise ValueError("mode must be 'greater', 'less' or 'equal', got %r" % (mode,))
+    if connectivity not in (1, 2, 3):
+        raise ValueError('connectivity must be 1, 2 or 3, got %r' % (connectivity,))
+    on_dev = _is_torch(data)
+    data, kind = _data_volume(data, on_dev)
+    shape = tuple(data.shape)
+    if len(shape) != 3:
+        raise ValueError('data must be 3-D, got shape %s' % (shape,))
+    if mask is not None:
+        if _is_torch(mask) != on_dev:
+            raise ValueError('data and mask must both be numpy arrays or both CUDA tensors')
+        if tuple(mask.shape) != shape:
+            raise ValueError('mask shape %s != data shape %s' % (tuple(mask.shape), shape))
+        if on_dev:
+            import torch
+            if mask.dtype == torch.bool:
+                mask = mask.to(torch.uint8)
+            if not (mask.is_cuda and mask.is_contiguous()) or mask.dtype != torch.uint8:
+                raise ValueError('mask must be a contiguous bool or uint8 CUDA tensor')
+        else:
+            mask = np.asarray(mask)
+            if mask.dtype not in (np.bool_, np.uint8):
+                raise TypeError('mask must be bool or uint8, got %s' % mask.dtype)
+            mask = np.ascontiguousarray(mask).view(np.uint8)
+    for box in (begin, end):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end must have 3 entries')
+    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
+    e = list(shape) if end is None else [int(v) for v in end]
+    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
+        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
+    oshape = tuple(hi - lo for lo, hi in zip(b, e))
+    if out is None:
+        if on_dev:
+            import torch
+            out = torch.empty(oshape, dtype=torch.int64, device=data.device)
+        else:
+            out = np.empty(oshape, dtype=np.uint64)
+    else:
+        if _is_torch(out) != on_dev:
+            raise ValueError('out must be of the same kind as data (numpy array or CUDA tensor)')
+        if on_dev:
+            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
+        else:
+            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
+        if not ok or tuple(out.shape) != oshape:
+            raise ValueError('out must be a contiguous 64-bit integer array of the shape of the box %s' % (oshape,))
+    lib = L.load()
+    L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    n = ctypes.c_uint64(0)
+    rc = lib.ctg_threshold_components(_ptr(data), kind, _ptr(mask), _shape_arr(shape), _shape_arr(b), _shape_arr(e),
+                                      float(threshold), CC_MODES[mode], int(bool(normalize)), int(connectivity),
+                                      _ptr(out), L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream,
+                                      ctypes.byref(n))
+    L.check(rc, 'ctg_threshold_components')
+    return out, int(n.value)
+
+
+def merge_assignments(pairs, n_labels, stream=None):
+    """ctg_merge_assignments: the union-find over the ids 0 .. n_labels - 1 with
+    the (n, 2) ``pairs`` united -> (table, max_id): table[0] = 0, every other
+    id maps to 1 + the rank of its set's smallest member (merge_assignments.py:
+    125-132, the consecutive table).  ``pairs``: a numpy array (the table comes
+    back as a uint64 array) or a contiguous 64-bit integer CUDA tensor (an int64
+    tensor).  A pair member that is 0 or not below ``n_labels`` raises."""
+    on_dev = _is_torch(pairs)
+    if on_dev:
+        if not (pairs.is_cuda and pairs.is_contiguous()) or pairs.element_size() != 8 or pairs.is_floating_point():
+            raise ValueError('pairs must be a contiguous CUDA tensor of 64-bit integers')
+    else:
+        pairs = np.asarray(pairs)
+        if pairs.size and pairs.dtype.kind not in 'ui':
+            raise TypeError('pairs must hold integers, got %s' % pairs.dtype)
+    if len(pairs.shape) != 2 or pairs.shape[1] != 2:
+        raise ValueError('pairs must have shape (n, 2), got %s' % (tuple(pairs.shape),))
+    if not 0 <= int(n_labels) < 1 << 64:
+        raise ValueError('n_labels must be a uint64 value, got %r' % (n_labels,))
+    n_labels = int(n_labels)
+    if n_labels >= 1 << 32:
+        raise ValueError('n_labels must stay below 2^32, got %d' % n_labels)
+    if on_dev:
+        import torch
+        table = torch.empty(n_labels, dtype=torch.int64, device=pairs.device)
+    else:
+        if pairs.dtype.kind == 'i' and pairs.size and int(pairs.min()) < 0:
+            raise ValueError('pairs holds negative values')
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint64)
+        table = np.empty(n_labels, dtype=np.uint64)
+    lib = L.load()
+    L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    max_id = ctypes.c_uint64(0)
+    rc = lib.ctg_merge_assignments(_ptr(pairs), int(pairs.shape[0]), n_labels, _ptr(table),
+                                   L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(max_id))
+    L.check(rc, 'ctg_merge_assignments')
+    return table, int(max_id.value)
+
+
 def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_offset=0, noise_amp=0.1,
                  with_boundary=True, device=None):
     """Generate the synthetic volume directly in HBM (torch tensors)."""

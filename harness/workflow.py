@@ -701,3 +701,106 @@ def relabel_workflow(input_path, input_key, assignment_path, assignment_key, blo
                    assignment_key, block_shape, max_jobs=max_jobs, threads_per_job=threads_per_job, timer=timer,
                    mode=mode)
     return timer
+
+
+# ------------------------------------------------------------------ thresholded components
+def _block_components_job(input_path, input_key, output_path, output_key, block_shape, threshold, threshold_mode,
+                          mask_path, mask_key, channel, connectivity, blocks):
+    """thresholded_components/block_components.py:236-291: the job's
+    {block id: offset contribution} (returned instead of saved as
+    cc_offsets_<job>.json)."""
+    import contextlib
+    from cluster_tools_amd import thresholded_components as tc
+    with contextlib.ExitStack() as files:
+        one_file = input_path == output_path
+        f_in = files.enter_context(ndist._open(input_path, 'a' if one_file else 'r'))
+        f_out = f_in if one_file else files.enter_context(ndist._open(output_path))
+        ds_in, ds_out = f_in[input_key], f_out[output_key]
+        shape = list(ds_in.shape)[1:] if channel is not None else list(ds_in.shape)       # :267-270
+        mask = None
+        if mask_path:                                                                   # :274-275 (full-shape masks)
+            mask = files.enter_context(ndist._open(mask_path, 'r'))[mask_key]
+            if list(mask.shape) != shape:
+                raise ValueError('the mask must have the shape of the volume: %s, %s' % (list(mask.shape), shape))
+        blk = blocking([0, 0, 0], shape, list(block_shape))                             # :272
+        out = {}
+        for b in blocks:
+            block = blk.getBlock(b)
+            bb = tuple(slice(x, y) for x, y in zip(block.begin, block.end))
+            out[b] = tc.block_components(ds_in, ds_out, bb, threshold, threshold_mode, mask=mask, channel=channel,
+                                         connectivity=connectivity)
+        return out
+
+
+def _block_faces_job(path, key, block_shape, offset_path, blocks):
+    """thresholded_components/block_faces.py:140-177: the job's unique pairs
+    (returned instead of saved as cc_assignments_<job>.npy), or None."""
+    import json
+    from cluster_tools_amd import rag
+    from cluster_tools_amd import thresholded_components as tc
+    with open(offset_path) as f:                                                        # :154-158
+        offsets_dict = json.load(f)
+    offsets, empty_blocks, n_labels = offsets_dict['offsets'], set(offsets_dict['empty_blocks']), offsets_dict['n_labels']
+    with ndist._open(path, 'r') as f:
+        ds = f[key]
+        blk = blocking([0, 0, 0], list(ds.shape), list(block_shape))
+        parts = [tc.block_faces(ds, blk, b, offsets, empty_blocks) for b in blocks]
+    parts = [p for p in parts if p is not None]                                         # :169-173
+    if not parts:
+        return None
+    pairs = rag.unique_pairs(np.concatenate(parts, axis=0))[0]
+    assert int(pairs.max()) < n_labels, '%i, %i' % (int(pairs.max()), n_labels)
+    return pairs
+
+
+def thresholded_components_workflow(input_path, input_key, output_path, output_key, assignment_key, threshold,
+                                    threshold_mode='greater', mask_path=None, mask_key=None, channel=None,
+                                    block_shape=(64, 64, 64), connectivity=3, max_jobs=1, mode='threads',
+                                    tmp_folder=None, timer=None):
+    """ThresholdedComponentsWorkflow (thresholded_components/
+    thresholded_components_workflow.py:29-89): BlockComponents into the uint64
+    output dataset with chunks of half a block (block_components.py:77-106),
+    MergeOffsets into ``cc_offsets.json`` of ``tmp_folder`` (default: next to
+    the output), BlockFaces, MergeAssignments into the dataset
+    ``assignment_key`` of the output file (merge_assignments.py:136-139), then
+    Write in place with the offsets file."""
+    import json
+    import os
+    from cluster_tools_amd import thresholded_components as tc
+    timer = timer or Timer()
+    with ndist._open(input_path, 'r') as f:
+        shape = list(f[input_key].shape)
+    if channel is None:
+        assert len(shape) == 3, str(len(shape))                                         # block_components.py:84-86
+    else:
+        assert len(shape) == 4, str(len(shape))                                         # :88-96
+        shape = shape[1:]
+    chunks = tuple(min(bs // 2, sh) for bs, sh in zip(block_shape, shape))               # :80, :100
+    with ndist._open(output_path) as f:                                                 # :104-106
+        f.require_dataset(output_key, shape=tuple(shape), dtype='uint64', compression='gzip', chunks=chunks)
+    tmp_folder = tmp_folder or os.path.dirname(os.path.abspath(output_path))
+    offset_path = os.path.join(tmp_folder, 'cc_offsets.json')                            # workflow :52
+    block_list = blocks_in_volume(shape, block_shape)
+    with timer.stage('block_components'):
+        job = functools.partial(_block_components_job, input_path, input_key, output_path, output_key,
+                                list(block_shape), threshold, threshold_mode, mask_path, mask_key, channel,
+                                connectivity)
+        per_block = {}
+        for part in _run_jobs(job, _jobs(block_list, max_jobs), mode):
+            per_block.update(part)
+    with timer.stage('merge_offsets'):
+        merged = tc.merge_offsets(per_block)
+        with open(offset_path, 'w') as f:                                               # merge_offsets.py:127-130
+            json.dump(merged, f)
+    with timer.stage('block_faces'):
+        job = functools.partial(_block_faces_job, output_path, output_key, list(block_shape), offset_path)
+        pair_arrays = _run_jobs(job, _jobs(block_list, max_jobs), mode)
+    with timer.stage('merge_assignments'):
+        table = tc.merge_assignments(pair_arrays, merged['n_labels'])
+        with ndist._open(output_path) as f:                                             # merge_assignments.py:136-139
+            ds = f.require_dataset(assignment_key, shape=table.shape, dtype='uint64', compression='gzip',
+                                   chunks=(min(65334, len(table)),))
+            ds[:] = table
+    write_workflow(output_path, output_key, output_path, output_key, output_path, assignment_key, block_shape,
+                   offset_path=offset_path, max_jobs=max_jobs, timer=timer, mode=mode)
+    return timer

@@ -41,6 +41,10 @@
  *   ctg_assignment_sparse, ctg_apply_assignment <- np.unique, the dict and nifty.tools.takeDict,
  *                                        write/write.py:170-181
  *   ctg_assignment_info               <- _write_maxlabel, write/write.py:281-289
+ *   ctg_threshold_components          <- vu.normalize, the comparison and skimage.morphology.label,
+ *                                        thresholded_components/block_components.py:161-182
+ *   ctg_merge_assignments             <- nufd.boost_ufd and relabelConsecutive,
+ *                                        thresholded_components/merge_assignments.py:125-132
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -465,6 +469,60 @@ void ctg_assignment_free(ctg_assignment* a);
 int ctg_apply_assignment(const ctg_assignment* a, const void* labels, int label_bits, int64_t n,
                          const int64_t* seg_begin, const uint64_t* seg_offset, int64_t n_seg, int allow_missing,
                          uint64_t* out, uint64_t* seg_nonzero, uint64_t* missing, int mem, void* stream);
+
+/*
+ * Thresholded components (ThresholdedComponentsWorkflow): the connected
+ * components of a thresholded box, and the union-find merge of the block-offset
+ * ids that the block faces join.
+ *
+ * ctg_threshold_components <- vu.normalize, the comparison, np.sum,
+ *                           skimage.morphology.label and max of _cc_block /
+ *                           _cc_block_with_mask,
+ *                           thresholded_components/block_components.py:161-182, :211-233
+ *   data        the (Z,Y,X) array, float32 (CTG_DATA_F32) or uint8 (CTG_DATA_U8);
+ *               shape / begin / end as ctg_label_overlaps (NULL: the whole array)
+ *   mask        NULL, or a uint8 array of the same shape: a voxel whose mask is 0 is
+ *               background (block_components.py:225)
+ *   normalize   0: the sample widened to float32 is compared.  Else the value of
+ *               vu.normalize (utils/volume_utils.py:98-105) over the box: v = x - min, and
+ *               v /= max(x - min) where that is > 0 -- float32 arithmetic, the divide
+ *               correctly rounded.  A NaN in the box makes numpy's minimum NaN: the result
+ *               is empty.  Without normalize a NaN voxel is background in every mode.
+ *   mode        v > threshold, v < threshold or v == threshold, in float32
+ *   connectivity 1, 2 or 3: voxels with 0 < |dz| + |dy| + |dx| <= connectivity are
+ *               neighbours (6, 18, 26 of them; skimage's label on a boolean array: 3)
+ *   out         box-shaped uint64: 0 for the background, components numbered
+ *               1 .. *n_components in raster (C) order of each component's first voxel --
+ *               scipy.ndimage.label's numbering
+ * A box outside the array, a bad data_kind, mode or connectivity is CTG_ERR_ARG;
+ * a box of 2^32 voxels or more is CTG_ERR_UNSUPPORTED.
+ *
+ * ctg_merge_assignments  <- nufd.boost_ufd(labels), ufd.merge, ufd.find and
+ *                           relabelConsecutive(keep_zeros=True, start_label=1),
+ *                           thresholded_components/merge_assignments.py:125-132
+ *   pairs       (n, 2) uint64 ids to unite, in any order, repeats allowed
+ *   table       n_labels uint64: table[0] = 0, every other id maps to 1 + the rank of
+ *               its set's smallest member among those of all sets of 1 .. n_labels - 1
+ *               (the consecutive table the reference computes and then does not save,
+ *               merge_assignments.py:131)
+ *   max_id      the largest entry of table
+ * A pair member that is 0 or not below n_labels is CTG_ERR_ARG and the table is
+ * not written; n_labels of 2^32 or more is CTG_ERR_UNSUPPORTED.
+ *
+ * Both calls use call-sized buffers only: a CTG_DEFER_STATS handle of the same
+ * device stays valid across them.  ctg_last_timings of a profiled call:
+ * ctg_threshold_components [0] range, [1] tiles, [2] seams, [3] flatten,
+ * [4] scan, [5] write, [6] total; ctg_merge_assignments [0] init, [1] pairs,
+ * [2] flatten, [3] scan, [4] write, [6] total.
+ */
+#define CTG_CC_GREATER 0
+#define CTG_CC_LESS 1
+#define CTG_CC_EQUAL 2
+int ctg_threshold_components(const void* data, int data_kind, const void* mask, const int64_t* shape,
+                             const int64_t* begin, const int64_t* end, float threshold, int mode, int normalize,
+                             int connectivity, uint64_t* out, int mem, void* stream, uint64_t* n_components);
+int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, uint64_t* table, int mem,
+                          void* stream, uint64_t* max_id);
 
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
