@@ -322,6 +322,29 @@ int ctg_last_timings(double* ms, int n) {
     return CTG_OK;
 }
 
+int ctg_last_sort(int64_t* out, int n) {
+    if (!out || n < 0) {
+        set_error("ctg_last_sort: null argument");
+        return CTG_ERR_ARG;
+    }
+    const SortReport& r = ws(current_device()).last_sort;
+    int64_t v[CTG_SORT_WORDS];
+    v[CTG_SORT_PATH] = r.path;
+    v[CTG_SORT_PACKED] = r.packed;
+    v[CTG_SORT_GROUP_TRIED] = r.group_tried;
+    v[CTG_SORT_GROUP_DONE] = r.group_done;
+    v[CTG_SORT_GROUP_WHY] = r.group_tried && !r.group_done ? (int)r.group.why : 0;
+    v[CTG_SORT_GROUP_SHIFT] = r.group.shift;
+    v[CTG_SORT_GROUP_BUCKETS] = r.group.nbk;
+    v[CTG_SORT_GROUP_LARGEST] = r.largest;
+    v[CTG_SORT_IB] = r.ib;
+    v[CTG_SORT_NB] = r.nb;
+    v[CTG_SORT_UB] = r.ub;
+    v[CTG_SORT_N] = r.n;
+    for (int i = 0; i < n && i < CTG_SORT_WORDS; ++i) out[i] = v[i];
+    return CTG_OK;
+}
+
 int ctg_result_num_blocks(const ctg_result* r) { return r ? (int)std::max<size_t>(r->edge_off.size(), 1) - 1 : -1; }
 
 int ctg_result_block_offsets(const ctg_result* r, int64_t* edge_off, int64_t* node_off) {

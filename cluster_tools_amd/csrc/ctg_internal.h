@@ -239,7 +239,12 @@ struct Counters {               // device-side counters, zeroed per call
     unsigned long long n_direct;     // faces emitted past a full LDS table
     unsigned long long label_overflow;  // labels >= 2^32 seen by the 32-bit key path
     unsigned long long max_v;        // largest label in any key
-    unsigned long long max_nu;       // largest ~u (32 bits) of any key: the smallest u is ~max_nu (0: no key)
+    // largest ~u (32 bits) of any key: the smallest u is ~max_nu (0: no key).  It is a lower bound the back half
+    // relies on: min_u <= u of every sorted key -- the group sort's buckets start at min_u << nb, and the node
+    // bitmap of collect_nodes starts at word min_u >> 5, so a key whose u came out below min_u (a wrong bucket
+    // base, say) would index in front of the bitmap.  The host keeps the bound (plan_group_sort, tests/test_plan.py);
+    // the device does not check it.
+    unsigned long long max_nu;
     unsigned long long pad[8];      // diagnostics (ablation checks, s_memtime stamps)
     unsigned long long rcount[NREG];  // records reserved per region (may exceed rcap: overflow)
 };
@@ -330,6 +335,7 @@ struct Workspace {
     hipEvent_t ev[7] = {};   // 0..6: the phase marks of a call
     double last_ms[8] = {0};   // scan, pack, sort, segment, reduce, nodes, total, narrow (always 0: no such pass)
     int64_t last_records = 0, last_direct = 0;
+    SortReport last_sort;   // the last record sort (ctg_last_sort); host values, a few stores per call
     int profiling = 0;
 };
 
@@ -401,7 +407,7 @@ hipError_t bucket_sort_pairs(const uint64_t* keys, const uint32_t* vals, uint64_
 hipError_t group_sort_runs(const uint64_t* key, int64_t rcap, const RegionPrefix& pre, int64_t n, int nb, int ub,
                            int ib, uint64_t min_label, uint64_t max_label, uint32_t* small, uint32_t* host_word,
                            uint64_t* items, uint32_t* perm, uint64_t* uniq, uint32_t* runs, uint32_t* roffs,
-                           uint32_t* dE, bool* done, hipStream_t s);
+                           uint32_t* dE, bool* done, SortReport* rep, hipStream_t s);
 // ctg_reduce.hip
 hipError_t launch_pack_keys(int64_t n, const uint64_t* key, int nb, uint64_t* sk, uint32_t* idx, hipStream_t s);
 hipError_t launch_pack_regions(const uint64_t* key, int64_t rcap, const RegionPrefix& pre, int nb, int ib, uint64_t* sk,

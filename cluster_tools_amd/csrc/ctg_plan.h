@@ -2,8 +2,10 @@
 // batched-block plan, record-buffer and candidate-buffer sizes, the Bloom
 // filter's size, the narrow-row mode, the channel classification, the
 // adjacency rule of the reduce, the count-matrix sums of the multi-GPU
-// exchange, the choice between the record-sort paths and the key range of the
-// bucket sort.  Plain C++17 -- no HIP, no getenv: the environment switches are
+// exchange, the choice between the record-sort paths, the key range of the
+// bucket sort and the bucket geometry of the bucket and group sorts.  Plain
+// C++17 -- no HIP (the bucket arithmetic the kernels share is marked CTG_HD),
+// no getenv: the environment switches are
 // read by the callers (scan_switches, sort_switches) and passed in as values --
 // so a host program can exercise them without a GPU (tools/plan_check.cpp,
 // tests/test_plan.py).
@@ -14,6 +16,15 @@
 #include <vector>
 
 #include "../../include/ctg.h"
+
+// the bucket arithmetic below is shared with the sort kernels (as ctg_uf.h)
+#ifndef CTG_HD
+#ifdef __HIPCC__
+#define CTG_HD __host__ __device__
+#else
+#define CTG_HD
+#endif
+#endif
 
 namespace ctg {
 
@@ -576,5 +587,130 @@ inline KeyRange packed_key_range(uint64_t min_u, uint64_t max_v, int nb, int ib)
     const uint64_t kmin = std::min<uint64_t>((std::min<uint64_t>(min_u, vmax) << nb) << ib, kmax);
     return {kmin, kmax};
 }
+
+// ---------------------------------------------------------------------------
+// bucket geometry of the packed-key bucket sort (ctg_sort.hip: bucket_sort_keys)
+// ---------------------------------------------------------------------------
+constexpr int BK_MAX_BITS = 12;  // at most 4096 buckets (LDS counters)
+
+// bucket bits for n keys of key_bits bits: ~1 K keys per bucket
+inline int bucket_bits(int64_t n, int key_bits) {
+    int bb = 1;
+    while (bb < BK_MAX_BITS && (n >> (bb + 10)) > 0) ++bb;
+    return std::min(bb, key_bits);
+}
+
+// The bucket a key of either sort goes to, and the bucket bits of a key
+// rebuilt from its bucket.  A key's bits above `shift` less those of the
+// smallest key (bk0) are its bucket.  The index is formed modulo 2^32: the
+// true difference (pk >> shift) - bk0 lies in [0, nbk) with nbk <= 2^16, so
+// its low 32 bits are the difference itself however large pk >> shift and bk0
+// are.  The way back is not modular: b + bk0 passes 2^32 for labels near 2^30
+// and above (shift <= 29 at nb = 31), so the sum is formed in 64 bits.
+CTG_HD inline uint32_t gs_bucket_of(uint64_t pk, int shift, uint64_t bk0) {
+    return (uint32_t)(pk >> shift) - (uint32_t)bk0;
+}
+CTG_HD inline uint64_t gs_bucket_key(uint32_t b, uint64_t bk0, int shift) { return ((uint64_t)b + bk0) << shift; }
+
+struct BucketKeysPlan {
+    bool ok;        // false: an argument out of range (nothing else is set)
+    int bb;         // bucket bits aimed at
+    int shift;      // bucket = gs_bucket_of(key, shift, bk0)
+    uint32_t nbk;   // <= 2^bb
+    uint64_t bk0;
+};
+
+// n keys with key bits [lo_bit, hi_bit) (slot bits below), all in [kmin, kmax].
+// 2^bb buckets over [kmin, kmax] (every key lies there), not over [0,
+// 2^hi_bit): a z-slab's labels start far above 0, and buckets over the
+// whole key domain put its keys in a few of them (rank 3 of 8 of the
+// weak-scaling 512^3 slabs: sort + segment 0.10 -> 0.24 ms, the large
+// segments of the segmented sort).  The smallest shift (down to lo_bit, where
+// the buckets are the keys) at which 2^bb buckets still cover the range: runs
+// of equal key bits never cross a bucket.
+inline BucketKeysPlan plan_bucket_keys(int64_t n, int lo_bit, int hi_bit, uint64_t kmin, uint64_t kmax) {
+    BucketKeysPlan p{};
+    if (n <= 0 || n > 0xFFFFFFFFll || hi_bit > 64 || lo_bit < 0 || hi_bit <= lo_bit || kmin > kmax) return p;
+    p.bb = bucket_bits(n, hi_bit - lo_bit);
+    p.shift = hi_bit - p.bb;
+    while (p.shift > lo_bit && (kmax >> (p.shift - 1)) - (kmin >> (p.shift - 1)) < (1ull << p.bb)) --p.shift;
+    const uint64_t nbk = (kmax >> p.shift) - (kmin >> p.shift) + 1;
+    if (nbk > (1ull << BK_MAX_BITS)) return p;   // kmax past 2^hi_bit: the counters would not hold it
+    p.nbk = (uint32_t)nbk;
+    p.bk0 = kmin >> p.shift;
+    p.ok = true;
+    return p;
+}
+
+// ---------------------------------------------------------------------------
+// bucket geometry of the group sort (ctg_sort.hip: group_sort_runs)
+// ---------------------------------------------------------------------------
+constexpr int GS_CAP = 8192;       // items of one bucket in LDS (512 threads x 16: ctg_sort.hip)
+constexpr int GS_TARGET = 3072;    // records per bucket aimed at
+constexpr int GS_BB_MAX = 16;      // 64 K buckets
+constexpr int GS_M = 1 << GS_BB_MAX;
+constexpr int GS_GB = 11;          // group bits of the in-bucket counting sort
+
+struct GroupSortPlan {
+    // why the group sort declines (the caller sorts another way).  N_RANGE: no
+    // record or 2^32 and more; KEY_BITS: ub + nb > 63 (bit 63 marks a run
+    // head); ITEM_BITS: shift + ib > 64, the bucket-local key and the slot do
+    // not fit one item; LOW_BITS: shift - min(GS_GB, shift) > 32, the key bits
+    // below the group bits do not fit the 32-bit LDS words; BUCKET_CAP: not
+    // the plan's -- the host read a bucket above GS_CAP from the device
+    enum Why { OK = 0, N_RANGE = 1, KEY_BITS = 2, ITEM_BITS = 3, LOW_BITS = 4, BUCKET_CAP = 5 } why;
+    int shift;                 // bucket = gs_bucket_of(packed key, shift, bk0); -1 before it is chosen
+    uint32_t nbk;              // <= GS_M
+    uint64_t bk0;              // bucket of the smallest key (a slab's labels start far above 0): up to 63 - shift bits
+    uint64_t min_pk, max_pk;   // every packed key (u << nb) | v lies between them
+    bool ok() const { return why == OK; }
+};
+
+// n records with keys (u, v), min_label <= u < v <= max_label, packed as
+// (u << nb) | v (ub: bits of u); ib: slot bits of an item.
+// Buckets of 2^shift packed keys from the smallest to the largest key: the
+// largest shift whose buckets average at most GS_TARGET records, and at most
+// GS_M buckets.  The range starts at the smallest u, not at 0: a z-slab of
+// rank r of N holds labels from about r/N of the volume's label range, and
+// buckets over [0, max] put its records in the top (N - r)/N of them -- past
+// GS_CAP per bucket (the onesweep fallback, twice the sort time) from rank 3
+// of 8 on.
+inline GroupSortPlan plan_group_sort(int64_t n, int nb, int ub, int ib, uint64_t min_label, uint64_t max_label) {
+    GroupSortPlan p{};
+    p.shift = -1;
+    p.why = GroupSortPlan::N_RANGE;
+    if (n <= 0 || n > 0xFFFFFFFFll) return p;
+    const int kb = ub + nb;
+    p.why = GroupSortPlan::KEY_BITS;
+    if (kb > 63) return p;
+    const uint64_t umax = (1ull << ub) - 1ull;
+    p.max_pk = (std::min<uint64_t>(max_label, umax) << nb) | max_label;
+    p.min_pk = std::min<uint64_t>(std::min<uint64_t>(min_label, max_label), umax) << nb;
+    const uint64_t lo = p.min_pk, hi = p.max_pk;
+    auto nbk_at = [lo, hi](int sh) { return (hi >> sh) - (lo >> sh) + 1; };
+    int shift = kb;
+    while (shift > 0 && nbk_at(shift - 1) <= (uint64_t)GS_M && (double)n / (double)nbk_at(shift) > (double)GS_TARGET)
+        --shift;
+    while (nbk_at(shift) > (uint64_t)GS_M) ++shift;
+    p.shift = shift;
+    p.nbk = (uint32_t)nbk_at(shift);
+    p.bk0 = lo >> shift;
+    p.why = shift + ib > 64                       ? GroupSortPlan::ITEM_BITS
+            : shift - std::min(GS_GB, shift) > 32 ? GroupSortPlan::LOW_BITS
+                                                  : GroupSortPlan::OK;
+    return p;
+}
+
+// What ctg_last_sort reports of a workspace's last record sort (ctg.h: the
+// CTG_SORT_* words).  Host values only.
+struct SortReport {
+    int path = -1;      // SortPath, 5: the group sort, -1: no record
+    int packed = 0;
+    int group_tried = 0, group_done = 0;
+    GroupSortPlan group{GroupSortPlan::OK, -1, 0, 0, 0, 0};   // as far as the group sort got
+    int64_t largest = -1;   // the largest bucket the host read (-1: none read)
+    int ib = 0, nb = 0, ub = 0;
+    int64_t n = 0;
+};
 
 }  // namespace ctg

@@ -76,13 +76,26 @@ static hipError_t sort_to_runs(Workspace& w, const ReduceJob& J, int nb, int ub,
     const RecordSortPlan plan =
         plan_record_sort(J.keys != nullptr, J.regions != nullptr, n, ub, nb, ib, spread, sort_switches());
     T = RunTable{plan.packed, ib};
+    // what ctg_last_sort reports: host values this function holds anyway
+    SortReport& rep = w.last_sort;
+    rep = SortReport{};
+    rep.path = (int)plan.path;
+    rep.packed = plan.packed;
+    rep.group_tried = plan.try_group;
+    rep.ib = ib;
+    rep.nb = nb;
+    rep.ub = ub;
+    rep.n = n;
     if (plan.try_group) {
         bool grouped = false;
         ev.mark(2);   // (phases: the whole group sort is "sort")
         CTG_TRY(group_sort_runs(J.keys, J.R.rcap, *J.regions, n, nb, ub, ib, J.min_u, J.max_v, w.gsort,
-                                w.small_host + SLOT_GROUP_SORT, S.sk_out, S.idx_out, S.uniq, S.runs, S.offs, dE_all, &grouped, s));
+                                w.small_host + SLOT_GROUP_SORT, S.sk_out, S.idx_out, S.uniq, S.runs, S.offs, dE_all, &grouped, &rep, s));
         if (grouped) {
             ev.mark(3);
+            rep.group_done = 1;
+            rep.path = CTG_SORT_PATH_GROUP;
+            rep.packed = 0;
             T.packed = false;   // (key, slot) runs and a u32 slot permutation, as for unpackable records
             return hipSuccess;
         }
@@ -333,6 +346,9 @@ hipError_t reduce_records(Workspace& w, const ReduceJob& J, hipStream_t s, ctg_r
     const int ub = J.ub ? J.ub : nb;
     if (nb > 32 || ub > 32) return hipErrorInvalidValue;
     if (n == 0) {
+        w.last_sort = SortReport{};   // (path -1: nothing to sort)
+        w.last_sort.nb = nb;
+        w.last_sort.ub = ub;
         res->n_edges = 0;
         res->edges = (uint64_t*)dev_alloc(16);
         res->features = J.stats ? (double*)dev_alloc(N_FEATURES * 8) : nullptr;

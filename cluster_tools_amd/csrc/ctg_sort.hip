@@ -31,7 +31,7 @@ namespace ctg {
 
 constexpr int BK_THREADS = 256;
 constexpr int BK_CHUNK = 4096;   // keys per workgroup in the histogram / scatter
-constexpr int BK_MAX_BITS = 12;  // at most 4096 buckets (LDS counters)
+// (BK_MAX_BITS, bucket_bits and the bucket geometry: ctg_plan.h)
 static_assert(5 * (1 << BK_MAX_BITS) + 2 <= BK_SMALL_WORDS, "bucket-sort scratch (ctg_internal.h)");
 
 __global__ __launch_bounds__(BK_THREADS) void k_bucket_hist(const uint64_t* __restrict__ keys, int64_t n, int shift,
@@ -136,12 +136,6 @@ __global__ __launch_bounds__(BK_THREADS) void k_bucket_scatter_pairs(const uint6
             vout[d] = vals[i];
         }
     }
-}
-
-static int bucket_bits(int64_t n, int key_bits) {
-    int bb = 1;
-    while (bb < BK_MAX_BITS && (n >> (bb + 10)) > 0) ++bb;   // ~1 K keys per bucket
-    return std::min(bb, key_bits);
 }
 
 // (keys, vals) sorted by key bits [0, hi_bit) into (kout, vout); ktmp / vtmp: n each
@@ -266,18 +260,13 @@ hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, 
                             uint64_t kmin, uint64_t kmax, uint32_t* small, GrowBuf& temp, uint32_t* nbk_out,
                             hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    if (n > 0xFFFFFFFFll || hi_bit > 64 || lo_bit < 0 || hi_bit <= lo_bit || kmin > kmax) return hipErrorInvalidValue;
-    const int bb = bucket_bits(n, hi_bit - lo_bit);
-    // 2^bb buckets over [kmin, kmax] (every key lies there), not over [0,
-    // 2^hi_bit): a z-slab's labels start far above 0, and buckets over the
-    // whole key domain put its keys in a few of them (rank 3 of 8 of the
-    // weak-scaling 512^3 slabs: sort + segment 0.10 -> 0.24 ms, the large
-    // segments of the segmented sort).  The bucket is the key's bits above
-    // `shift` less kmin's: runs of equal key bits never cross a bucket.
-    int shift = hi_bit - bb;
-    while (shift > lo_bit && (kmax >> (shift - 1)) - (kmin >> (shift - 1)) < (1ull << bb)) --shift;
-    const uint32_t bk0 = (uint32_t)(kmin >> shift);
-    const uint32_t nbk = (uint32_t)((kmax >> shift) - (kmin >> shift) + 1);
+    // the buckets over [kmin, kmax]: plan_bucket_keys (ctg_plan.h)
+    const BucketKeysPlan plan = plan_bucket_keys(n, lo_bit, hi_bit, kmin, kmax);
+    if (!plan.ok) return hipErrorInvalidValue;
+    const int shift = plan.shift;
+    // the kernels take the bucket modulo 2^32 (gs_bucket_of's rule) and sort the whole keys: no way back
+    const uint32_t bk0 = (uint32_t)plan.bk0;
+    const uint32_t nbk = plan.nbk;
     *nbk_out = nbk;
     uint32_t* counts = small;
     uint32_t* offs = small + (1 << BK_MAX_BITS);
@@ -329,16 +318,12 @@ hipError_t bucket_sort_keys(const uint64_t* keys, uint64_t* tmp, uint64_t* out, 
 // ---------------------------------------------------------------------------
 constexpr int GS_THREADS = 512;               // k_gs_sort / k_gs_runs (three workgroups per CU)
 constexpr int GS_IPT = 16;
-constexpr int GS_CAP = GS_THREADS * GS_IPT;   // items of one bucket in LDS
-constexpr int GS_TARGET = 3072;               // records per bucket aimed at
+static_assert(GS_CAP == GS_THREADS * GS_IPT, "items of one bucket in LDS (GS_CAP, GS_TARGET, GS_M, GS_GB: ctg_plan.h)");
 constexpr int GS_PASS_THREADS = 1024;         // bucket passes
 constexpr int GS_CHUNK = GS_PASS_THREADS * GS_IPT; // records per workgroup of the bucket passes
-constexpr int GS_BB_MAX = 16;                 // 64 K buckets
-constexpr int GS_M = 1 << GS_BB_MAX;
 constexpr uint32_t GS_HALF = 8192;            // LDS bucket counters per window pass of the bucket kernels (32 KB:
                                               // two 1024-thread workgroups per CU; a workgroup's bucket range
                                               // is usually far narrower, a wider one takes several passes)
-constexpr int GS_GB = 11;                     // group bits of the in-bucket counting sort
 constexpr int GS_NG = 1 << GS_GB;
 constexpr uint64_t GS_HEAD = 1ull << 63;      // sorted key of a run head (keys use at most 63 bits)
 static_assert(GS_SMALL_WORDS >= 5 * GS_M + 9, "group-sort scratch (ctg_internal.h): roff holds M + 1 entries");
@@ -364,10 +349,11 @@ struct GsParams {
     int64_t rcap;          // slots per region
     RegionPrefix pre;      // records per region (exclusive prefix)
     int nb;                // bits of v in the packed key (u << nb) | v
-    int shift;             // bucket = (packed key >> shift) - bk0
+    int shift;             // bucket = gs_bucket_of(packed key, shift, bk0)
     int ib;                // slot bits of an item
     uint32_t nbk;
-    uint32_t bk0;          // bucket of the smallest key (a slab's labels start far above 0)
+    uint64_t bk0;          // bucket of the smallest key (a slab's labels start far above 0): past 32 bits for
+                           // labels near 2^30 and above
 };
 
 __device__ __forceinline__ uint64_t gs_packed(uint64_t k, int nb) { return ((k >> 32) << nb) | (k & 0xFFFFFFFFull); }
@@ -417,7 +403,8 @@ __global__ __launch_bounds__(GS_PASS_THREADS) void k_gs_hist(GsParams P, uint32_
     for (int q = 0; q < GS_IPT; ++q) {
         const uint32_t j = c0 + q * GS_PASS_THREADS + threadIdx.x;
         const uint64_t k = src[min(j, cnt - 1)];
-        const uint32_t b = (uint32_t)(gs_packed(k, P.nb) >> P.shift) - P.bk0;
+        // modulo 2^32, exact: the true difference is below nbk <= 2^16 (gs_bucket_of, ctg_plan.h)
+        const uint32_t b = gs_bucket_of(gs_packed(k, P.nb), P.shift, P.bk0);
         bk[q] = j < cnt && b < P.nbk ? b : 0xFFFFFFFFu;   // (the bucket loop's bound, as before the window)
     }
     __shared__ uint32_t red[2];
@@ -509,7 +496,7 @@ __global__ __launch_bounds__(GS_PASS_THREADS) void k_gs_scatter(GsParams P, cons
     for (int q = 0; q < GS_IPT; ++q) {
         const uint32_t j = c0 + q * GS_PASS_THREADS + threadIdx.x;
         const uint64_t pk = gs_packed(it[q], P.nb);
-        const uint32_t b = (uint32_t)(pk >> P.shift) - P.bk0;
+        const uint32_t b = gs_bucket_of(pk, P.shift, P.bk0);   // (modulo 2^32, exact: as k_gs_hist)
         bk[q] = j < cnt && b < P.nbk ? b : 0xFFFFFFFFu;
         it[q] = ((pk & rmask) << P.ib) | ((uint64_t)r * (uint64_t)P.rcap + j);
     }
@@ -595,7 +582,7 @@ __device__ __forceinline__ unsigned long long gs_stamp() {
 // taken in group order (lanes of a wave on consecutive positions read the
 // same group entries: broadcasts, not bank conflicts).
 __global__ __launch_bounds__(GS_THREADS) void k_gs_sort(uint64_t* __restrict__ items, uint32_t* __restrict__ small,
-                                                        int shift, int ib, uint32_t bk0, uint32_t* __restrict__ perm,
+                                                        int shift, int ib, uint64_t bk0, uint32_t* __restrict__ perm,
                                                         unsigned long long* diag) {
     unsigned long long t_prev = diag ? gs_stamp() : 0ull;
     __shared__ uint32_t grem[GS_CAP + 8];         // low key bits by group position, then sorted (+ read pad)
@@ -698,7 +685,7 @@ __global__ __launch_bounds__(GS_THREADS) void k_gs_sort(uint64_t* __restrict__ i
     }
     __syncthreads();   // every item read (and grem sorted) before the keys overwrite the items
     GS_STAMP(4);
-    const uint64_t bkey = (uint64_t)(b + bk0) << shift;
+    const uint64_t bkey = gs_bucket_key(b, bk0, shift);   // b + bk0 in 64 bits: it passes 2^32 for labels near 2^30
 #pragma unroll
     for (int q = 0; q < GS_IPT; ++q)
         if (vb[q] != 0xFFFFFFFFu) {
@@ -791,30 +778,18 @@ __global__ __launch_bounds__(GS_THREADS) void k_gs_runs(const uint64_t* __restri
 // Records of the face scan (keys in NREG regions) -> perm / uniq / runs / roffs
 // / *dE as the reduction reads them.  *done = false (nothing written): the
 // geometry does not fit or some bucket exceeds GS_CAP; the caller sorts
-// another way.  One host read (the largest bucket).
+// another way.  One host read (the largest bucket).  rep: the plan and that
+// bucket, for ctg_last_sort.
 hipError_t group_sort_runs(const uint64_t* key, int64_t rcap, const RegionPrefix& pre, int64_t n, int nb, int ub,
                            int ib, uint64_t min_label, uint64_t max_label, uint32_t* small, uint32_t* host_word, uint64_t* items,
                            uint32_t* perm, uint64_t* uniq, uint32_t* runs, uint32_t* roffs, uint32_t* dE,
-                           bool* done, hipStream_t s) {
+                           bool* done, SortReport* rep, hipStream_t s) {
     *done = false;
-    if (n <= 0 || n > 0xFFFFFFFFll) return hipSuccess;
-    const int kb = ub + nb;
-    if (kb > 63) return hipSuccess;
-    // buckets of 2^shift packed keys from the smallest to the largest key
-    // (min_label <= u < v <= max_label): the largest shift whose buckets average
-    // at most GS_TARGET records, and at most GS_M buckets.  The range starts at
-    // the smallest u, not at 0: a z-slab of rank r of N holds labels from
-    // about r/N of the volume's label range, and buckets over [0, max] put its
-    // records in the top (N - r)/N of them -- past GS_CAP per bucket (the
-    // onesweep fallback, twice the sort time) from rank 3 of 8 on.
-    const uint64_t max_pk = (std::min<uint64_t>(max_label, (1ull << ub) - 1ull) << nb) | max_label;
-    const uint64_t min_pk = std::min<uint64_t>(std::min<uint64_t>(min_label, max_label), (1ull << ub) - 1ull) << nb;
-    auto nbk_at = [&](int sh) { return (max_pk >> sh) - (min_pk >> sh) + 1; };
-    int shift = kb;
-    while (shift > 0 && nbk_at(shift - 1) <= (uint64_t)GS_M && (double)n / (double)nbk_at(shift) > (double)GS_TARGET)
-        --shift;
-    while (nbk_at(shift) > (uint64_t)GS_M) ++shift;
-    if (shift + ib > 64 || shift - std::min(GS_GB, shift) > 32) return hipSuccess;
+    // the buckets from the smallest to the largest key: plan_group_sort (ctg_plan.h)
+    const GroupSortPlan plan = plan_group_sort(n, nb, ub, ib, min_label, max_label);
+    rep->group = plan;
+    if (!plan.ok()) return hipSuccess;
+    const int shift = plan.shift;
     GsParams P;
     P.key = key;
     P.rcap = rcap;
@@ -822,8 +797,8 @@ hipError_t group_sort_runs(const uint64_t* key, int64_t rcap, const RegionPrefix
     P.nb = nb;
     P.shift = shift;
     P.ib = ib;
-    P.nbk = (uint32_t)nbk_at(shift);
-    P.bk0 = (uint32_t)(min_pk >> shift);
+    P.nbk = plan.nbk;
+    P.bk0 = plan.bk0;
     GsLayout L(small);
     uint32_t mx = 0;
     for (int r = 0; r < NREG; ++r) mx = std::max(mx, pre.off[r + 1] - pre.off[r]);
@@ -836,7 +811,11 @@ hipError_t group_sort_runs(const uint64_t* key, int64_t rcap, const RegionPrefix
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(host_word, L.misc, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    if (*host_word > (uint32_t)GS_CAP) return hipSuccess;   // skewed: a bucket does not fit LDS
+    rep->largest = *host_word;
+    if (*host_word > (uint32_t)GS_CAP) {   // skewed: a bucket does not fit LDS
+        rep->group.why = GroupSortPlan::BUCKET_CAP;
+        return hipSuccess;
+    }
     hipLaunchKernelGGL(k_gs_scatter, grid, dim3(GS_PASS_THREADS), lds, s, P, L.offs, L.cursor, items);
 #ifdef CTG_DIAG   // per-phase s_memtime sums of k_gs_sort (variant builds, CTG_GS_DIAG set)
     static unsigned long long* diag = nullptr;

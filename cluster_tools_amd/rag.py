@@ -1294,3 +1294,20 @@ def last_timings():
     buf = (ctypes.c_double * 8)()
     L.check(L.load().ctg_last_timings(buf, 8), 'ctg_last_timings')
     return dict(zip(['scan', 'pack', 'sort', 'segment', 'reduce', 'nodes', 'total', 'narrow'], list(buf)))
+
+
+SORT_PATHS = ('bucket_keys', 'onesweep_keys', 'bucket_pairs', 'onesweep_pairs_wide', 'onesweep_pairs_default',
+              'group')
+SORT_DECLINES = ('none', 'n_range', 'key_bits', 'item_bits', 'low_bits', 'bucket_cap')
+
+
+def last_sort():
+    """Which way the last record sort of the current device went (ctg_last_sort, include/ctg.h): path (one
+    of SORT_PATHS, None when there was no record), packed, group_tried, group_done, group_decline (one of
+    SORT_DECLINES), group_shift, group_buckets, largest_bucket (-1: not read), ib, nb, ub and n."""
+    buf = (ctypes.c_int64 * L.CTG_SORT_WORDS)()
+    L.check(L.load().ctg_last_sort(buf, L.CTG_SORT_WORDS), 'ctg_last_sort')
+    v = list(buf)
+    return dict(path=SORT_PATHS[v[0]] if v[0] >= 0 else None, packed=v[1], group_tried=v[2], group_done=v[3],
+                group_decline=SORT_DECLINES[v[4]], group_shift=v[5], group_buckets=v[6], largest_bucket=v[7],
+                ib=v[8], nb=v[9], ub=v[10], n=v[11])

@@ -620,6 +620,43 @@ int ctg_trim(void);
 int ctg_set_profiling(int on);
 int ctg_last_timings(double* ms, int n);
 
+/* Which way the last record sort of this thread's device went (the back half of
+ * every scan call, of ctg_merge_stats and of the unique-pairs calls): the first
+ * n (<= CTG_SORT_WORDS) of
+ *   [CTG_SORT_PATH]     0 packed keys, bucket pass + segmented sort; 1 packed keys,
+ *                       onesweep; 2 (key, index) pairs, bucket pass + segmented sort;
+ *                       3 pairs, onesweep with wide digits; 4 pairs, onesweep with the
+ *                       default digits; CTG_SORT_PATH_GROUP the group sort; -1 no record
+ *   [CTG_SORT_PACKED]   the record slot rode in the sort key
+ *   [CTG_SORT_GROUP_TRIED] the records were offered to the group sort,
+ *   [CTG_SORT_GROUP_DONE]  which took them, or declined for
+ *   [CTG_SORT_GROUP_WHY]   0 nothing (taken, or not offered), 1 no record or 2^32 and more,
+ *                       2 more than 63 key bits, 3 bucket-local key and slot past 64 bits,
+ *                       4 more than 32 key bits below the group bits (1 - 4: before any
+ *                       launch), 5 a bucket above the LDS capacity
+ *   [CTG_SORT_GROUP_SHIFT], [CTG_SORT_GROUP_BUCKETS] the group sort's bucket shift and
+ *                       bucket count (-1, 0: it chose none)
+ *   [CTG_SORT_GROUP_LARGEST] the largest bucket as read back (-1: not read)
+ *   [CTG_SORT_IB], [CTG_SORT_NB], [CTG_SORT_UB] bits of the record slot, of the largest
+ *                       label and of the key's u field
+ *   [CTG_SORT_N]        records
+ * Host values the call held anyway: no device read, no synchronisation. */
+#define CTG_SORT_PATH 0
+#define CTG_SORT_PACKED 1
+#define CTG_SORT_GROUP_TRIED 2
+#define CTG_SORT_GROUP_DONE 3
+#define CTG_SORT_GROUP_WHY 4
+#define CTG_SORT_GROUP_SHIFT 5
+#define CTG_SORT_GROUP_BUCKETS 6
+#define CTG_SORT_GROUP_LARGEST 7
+#define CTG_SORT_IB 8
+#define CTG_SORT_NB 9
+#define CTG_SORT_UB 10
+#define CTG_SORT_N 11
+#define CTG_SORT_WORDS 12
+#define CTG_SORT_PATH_GROUP 5
+int ctg_last_sort(int64_t* out, int n);
+
 /* bounds checks of CTG_DIAG builds (no reference counterpart: hardening): the
  * first index into a call-sized workspace buffer (records, sorted positions,
  * run tables, permutations, node bitmaps, exchange rows) that reached past

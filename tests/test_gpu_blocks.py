@@ -207,5 +207,9 @@ def test_blocks_independent_of_workspace_history(gpu, monkeypatch, packed):
     lt, bt = rag.synth_volume((512, 512, 512), cell=10, seed=1)
     rag.rag_features_handle(lt, bt).free()
     del lt, bt
-    test_blocks_affinity_features(None, S.NN_OFFSETS)
-    test_blocks_affinity_features(None, S.LR_OFFSETS)
+    for offsets in (S.NN_OFFSETS, S.LR_OFFSETS):
+        test_blocks_affinity_features(None, offsets)
+        info = rag.last_sort()      # tagged keys: onesweep, packed only where key and slot leave bit 63 free
+        fits = packed == '1' and 32 + info['nb'] + info['ib'] <= 63
+        assert info['ub'] == 32 and info['ib'] >= 23 and info['group_tried'] == 0, info
+        assert (info['path'], info['packed']) == (('onesweep_keys', 1) if fits else ('onesweep_pairs_wide', 0)), info

@@ -647,6 +647,13 @@ def test_variance_constant_and_near_constant_edges(gpu):
     check_features(m['features'], f_ref)
 
 
+def _took(**want):
+    """The last record sort went as `want` says (rag.last_sort() fields)."""
+    info = rag.last_sort()
+    assert {k: info[k] for k in want} == want, str(info)
+    return info
+
+
 def test_bucket_sort_skewed_keys(gpu, monkeypatch):
     """The record sort's MSD bucket pass (ctg_sort.hip) on a skewed key set:
     every third plane is background label 0, adjacent to nearly every cell, so
@@ -656,8 +663,10 @@ def test_bucket_sort_skewed_keys(gpu, monkeypatch):
     lab = lab.copy()
     lab[::3] = 0
     out = rag.rag_features(lab, bnd)
+    _took(path='bucket_keys', packed=1, group_tried=0)     # 12-bit labels pack beside any slot width
     monkeypatch.setenv('CTG_BUCKET_SORT', '0')
     ref = rag.rag_features(lab, bnd)
+    _took(path='onesweep_keys', packed=1, group_tried=0)
     np.testing.assert_array_equal(out['edges'], ref['edges'])
     np.testing.assert_array_equal(out['nodes'], ref['nodes'])
     np.testing.assert_array_equal(out['features'][:, 9], ref['features'][:, 9])
@@ -667,17 +676,32 @@ def test_bucket_sort_skewed_keys(gpu, monkeypatch):
     check_features(out['features'], f_o)
 
 
-@pytest.mark.parametrize('offset', [5_000_003, (1 << 20) - 7, 0])
+@pytest.mark.parametrize('offset', [5_000_003, 4_000_003, (1 << 20) - 7, 0])
 def test_bucket_sort_offset_labels(gpu, monkeypatch, offset):
     """The packed-key MSD bucket pass spans [smallest key, largest key]: ids
     of a z-slab start far above 0 (offset), and a range starting right below
     a power of two straddles a bucket boundary.  Same result as the plain
-    radix sort and the oracle."""
+    radix sort and the oracle.  The record buffer starts from its smallest
+    size (18 slot bits), whatever the calls before grew it to: labels of up to
+    22 bits pack beside them; the 23-bit ids from 5 000 003 do not and take
+    the group sort with either setting."""
     lab, bnd = S.generate((40, 64, 96), cell=4, seed=17)
     lab = lab + np.uint64(offset)
+    monkeypatch.setenv('CTG_REC_FRESH', '1')
     out = rag.rag_features(lab, bnd)
+    info = rag.last_sort()
+    fits = 2 * info['nb'] + info['ib'] <= 63
+    assert fits == (offset != 5_000_003), info
+    if fits:
+        _took(path='bucket_keys', packed=1, group_tried=0)
+    else:
+        _took(path='group', packed=0, group_tried=1, group_done=1)
     monkeypatch.setenv('CTG_BUCKET_SORT', '0')
     ref = rag.rag_features(lab, bnd)
+    if fits:
+        _took(path='onesweep_keys', packed=1, group_tried=0)
+    else:
+        _took(path='group', packed=0, group_tried=1, group_done=1)
     _same_result(out, ref)
     e_o, f_o = O.boundary_features(lab, bnd)
     np.testing.assert_array_equal(out['edges'], e_o)
@@ -688,12 +712,17 @@ def test_bucket_sort_offset_labels(gpu, monkeypatch, offset):
 def test_group_sort_first_on_packable_records(gpu, monkeypatch, shape, cell, offset):
     """CTG_GROUP_FIRST=1: records whose key and slot pack into one word take
     the group sort (u32 slot permutation) instead of the packed-key bucket
-    sort (slots in the sorted keys): same result, and the oracle's."""
+    sort (slots in the sorted keys): same result, and the oracle's.  (The
+    record buffer starts from its smallest size: 22-bit labels pack beside
+    at most 19 slot bits.)"""
     lab, bnd = S.generate(shape, cell=cell, seed=23)
     lab = lab + np.uint64(offset)
+    monkeypatch.setenv('CTG_REC_FRESH', '1')
     ref = rag.rag_features(lab, bnd, keep_stats=True)
+    _took(path='bucket_keys', packed=1, group_tried=0)
     monkeypatch.setenv('CTG_GROUP_FIRST', '1')
     out = rag.rag_features(lab, bnd, keep_stats=True)
+    _took(path='group', packed=0, group_tried=1, group_done=1, group_decline='none')
     _same_result(out, ref)
     # histograms, count | ADJ, min, max (the pivot word follows the records' order within a key)
     np.testing.assert_array_equal(out['records'][:, :45], ref['records'][:, :45])
@@ -718,30 +747,42 @@ def test_group_sort_matches_other_paths(gpu, monkeypatch, shape, cell, seed):
     lab, bnd = S.generate(shape, cell=cell, seed=seed)
     monkeypatch.setenv('CTG_SORT_PACKED', '0')   # small volumes would pack key + slot into one word
     out = rag.rag_features(lab, bnd)
+    _took(path='group', packed=0, group_tried=1, group_done=1, group_decline='none')
     monkeypatch.setenv('CTG_GROUP_SORT', '0')
     monkeypatch.setenv('CTG_BUCKET_SORT_PAIRS', '0')
     ref = rag.rag_features(lab, bnd)
+    _took(path='onesweep_pairs_wide', packed=0, group_tried=0, group_done=0)
     _same_result(out, ref)
     e_o, f_o = O.boundary_features(lab, bnd)
     np.testing.assert_array_equal(out['edges'], e_o)
     check_features(out['features'], f_o)
 
 
-@pytest.mark.parametrize('case', ['boundary', 'ignore', 'graph', 'affinity_lr', 'far_labels', 'offset_labels',
-                                  'top_labels'])
+@pytest.mark.parametrize('case', ['boundary', 'ignore', 'ignore_sparse', 'graph', 'affinity_lr', 'far_labels',
+                                  'offset_labels', 'top_labels'])
 def test_group_sort_cases(gpu, monkeypatch, case):
     """The group sort path (run table and node bitmap from its run pass:
     ctg_sort.hip k_gs_runs, node window in LDS) against the onesweep path
     (CTG_GROUP_SORT=0) and the oracle: boundary maps, ignore_label (kept-edge
     compaction), graph only, long-range affinities (adjacency filter), and
     labels spread so that a bucket's node window does not fit LDS (global node
-    atomics)."""
+    atomics).  Three of the cases the group sort declines, so they compare
+    the bucket pair sort with onesweep: far_labels (58 key bits in a few
+    buckets: a bucket-local key and the slot pass 64 bits, or more than 32
+    bits stay below the group bits) and top_labels (64 key bits) before any
+    launch, ignore on the device's counts (the background label's bucket
+    passes the LDS capacity); ignore_sparse, with few background voxels, is
+    the kept-edge compaction behind the group sort."""
     lab, bnd = S.generate((40, 72, 100), cell=5, seed=41)
     kw = {}
     data = bnd
     if case == 'ignore':
         lab = lab.copy()
         lab[::4, ::3] = 0
+        kw['ignore_label'] = True
+    elif case == 'ignore_sparse':
+        lab = lab.copy()
+        lab[::8, ::12, ::10] = 0
         kw['ignore_label'] = True
     elif case == 'graph':
         data = None
@@ -756,36 +797,58 @@ def test_group_sort_cases(gpu, monkeypatch, case):
         lab = lab + np.uint64((1 << 32) - 1 - int(lab.max()))
     monkeypatch.setenv('CTG_SORT_PACKED', '0')
     out = rag.rag_features(lab, data, **kw)
+    info = rag.last_sort()
+    declined = {'far_labels': 'item_bits' if info['group_shift'] + info['ib'] > 64 else 'low_bits',
+                'top_labels': 'key_bits', 'ignore': 'bucket_cap'}.get(case)
+    if declined:
+        _took(path='bucket_pairs', packed=0, group_tried=1, group_done=0, group_decline=declined)
+        assert (info['largest_bucket'] > 8192) if case == 'ignore' else (info['largest_bucket'] == -1), info
+    else:
+        _took(path='group', packed=0, group_tried=1, group_done=1, group_decline='none')
     monkeypatch.setenv('CTG_GROUP_SORT', '0')
     monkeypatch.setenv('CTG_BUCKET_SORT_PAIRS', '0')
     ref = rag.rag_features(lab, data, **kw)
+    _took(path='onesweep_pairs_wide', packed=0, group_tried=0, group_done=0)
     np.testing.assert_array_equal(out['edges'], ref['edges'])
     np.testing.assert_array_equal(out['nodes'], ref['nodes'])
     if data is not None:
         np.testing.assert_array_equal(out['features'][:, [2, 8, 9]], ref['features'][:, [2, 8, 9]])
         np.testing.assert_allclose(out['features'], ref['features'], rtol=1e-12, atol=1e-15)
-    if case in ('boundary', 'ignore', 'far_labels', 'offset_labels', 'top_labels'):
-        e_o, f_o = O.boundary_features(lab, bnd, ignore_label=case == 'ignore')
+    if case in ('boundary', 'ignore', 'ignore_sparse', 'far_labels', 'offset_labels', 'top_labels'):
+        e_o, f_o = O.boundary_features(lab, bnd, ignore_label=case.startswith('ignore'))
         np.testing.assert_array_equal(out['edges'], e_o)
         check_features(out['features'], f_o)
-        if case != 'ignore':   # every label has a face: the nodes are the volume's labels
+        if not case.startswith('ignore'):   # every label has a face: the nodes are the volume's labels
             np.testing.assert_array_equal(out['nodes'], O.unique_labels(lab))
 
 
 def test_group_sort_one_label_group(gpu, monkeypatch):
-    """Every record of one bucket in one in-bucket group (label 1 under a
-    plane of ~10 K cells: keys (1, v) only differ in v), and labels >= 2^20 so
-    the group bits are u's: the in-group rank pass over a ~10 K-item group."""
-    lab2, bnd2 = S.generate((1, 512, 512), cell=5, seed=3)
-    lab = np.empty((2, 512, 512), np.uint64)
-    lab[0] = 1
-    lab[1] = lab2[0] + np.uint64(1 << 20)
-    bnd = np.concatenate([np.full((1, 512, 512), 0.3, np.float32), bnd2])
+    """Every record of one bucket in one in-bucket group: 3968 cells of 3 x 7
+    voxels, each alone in label 1 (the plane under them and the gaps between
+    them), so the keys (1, v) only differ in v, and labels >= 2^20 so the
+    group bits are u's: the in-group rank pass over a group of thousands.  Two
+    cells touch, so the key range reaches up to u = 2^20 and the buckets stay
+    wide.  (A Voronoi plane instead of the separated cells put its ~15 K
+    in-plane edges in one more bucket, past the bucket capacity: the call fell
+    back to the pair sort.)"""
+    ny, nx = 248, 512
+    lab = np.ones((2, ny, nx), np.uint64)
+    cell = np.arange((ny // 4) * (nx // 8), dtype=np.uint64).reshape(ny // 4, nx // 8) + np.uint64(1 << 20)
+    for dy in range(3):
+        for dx in range(7):
+            lab[1, dy::4, dx::8] = cell
+    lab[1, 0:3, 7] = cell[0, 0]                         # cell 0 reaches cell 1
+    bnd = np.random.default_rng(3).random(lab.shape, dtype=np.float32)
     monkeypatch.setenv('CTG_SORT_PACKED', '0')
     out = rag.rag_features(lab, bnd)
+    info = _took(path='group', packed=0, group_tried=1, group_done=1, group_decline='none')
+    # label 1's records (one or more a cell) in one bucket and one group: the group bits lie above v's 21 bits
+    assert 3968 <= info['largest_bucket'] <= 8192 and info['largest_bucket'] >= info['n'] - 8, str(info)
+    assert info['group_shift'] - 11 >= 21, str(info)
     monkeypatch.setenv('CTG_GROUP_SORT', '0')
     monkeypatch.setenv('CTG_BUCKET_SORT_PAIRS', '0')
     ref = rag.rag_features(lab, bnd)
+    _took(path='onesweep_pairs_wide', packed=0, group_tried=0, group_done=0)
     _same_result(out, ref)
     e_o, f_o = O.boundary_features(lab, bnd)
     np.testing.assert_array_equal(out['edges'], e_o)
@@ -801,9 +864,12 @@ def test_group_sort_oversized_bucket_falls_back(gpu, monkeypatch):
     lab[::2] = 1
     monkeypatch.setenv('CTG_SORT_PACKED', '0')
     out = rag.rag_features(lab, bnd)
+    info = _took(path='bucket_pairs', packed=0, group_tried=1, group_done=0, group_decline='bucket_cap')
+    assert info['largest_bucket'] > 8192 and info['group_shift'] >= 0, info      # tried, and declined on the device's counts
     monkeypatch.setenv('CTG_GROUP_SORT', '0')
     monkeypatch.setenv('CTG_BUCKET_SORT_PAIRS', '0')
     ref = rag.rag_features(lab, bnd)
+    _took(path='onesweep_pairs_wide', packed=0, group_tried=0, group_done=0, largest_bucket=-1)
     _same_result(out, ref)
     assert np.all(out['edges'][:, 0][out['edges'][:, 1] > 1] >= 1)
 
@@ -863,6 +929,10 @@ def test_single_edge_many_records(gpu, monkeypatch):
     for packed in ('1', '0'):
         monkeypatch.setenv('CTG_SORT_PACKED', packed)
         out = rag.rag_features(lab, bnd)
+        if packed == '1':
+            _took(path='bucket_keys', packed=1, group_tried=0, n=8192)
+        else:
+            _took(path='group', packed=0, group_tried=1, group_done=1, n=8192, largest_bucket=8192)
         assert out['edges'].tolist() == [[1, 2]]
         f = out['features'][0]
         assert f[9] == 2 * 4096 * 4096 and f[0] == 0.5 and f[2] == 0.25 and f[8] == 0.75

@@ -1,6 +1,6 @@
 """The host layer's decisions (csrc/ctg_plan.h: call boxes, tile depths, the
 batched-block plan, buffer sizes, channel classes, record-sort path, bucket
-key range, ...) are pure functions; tools/plan_check.cpp
+key range, bucket geometry of the two bucket sorts, ...) are pure functions; tools/plan_check.cpp
 drives them on the CPU -- built with the host compiler and
 -fsanitize=address,undefined -- and its answers are compared with the tables
 below (no GPU, no library)."""
@@ -392,3 +392,173 @@ def test_exchange_counts(plan):
     assert [tuple(map(int, g.split())) for g in plan(q)] == exp
     assert exp[0] == (1 + 2 + 3, 0 + 7 + 14, (2 + 3) * 28 + 7 + 14)      # rank 0 by hand
     assert plan(['xchg 1 0 28 0 5 9', 'xchg 1 0 28 1 5 9']) == ['5 9 0', '5 9 0']     # one rank: nothing moves
+
+
+# ---------------------------------------------------------------------------
+# bucket geometry of the group sort and of the packed-key bucket sort
+# (plan_group_sort, plan_bucket_keys, gs_bucket_of, gs_bucket_key) against
+# tests/sort_plan.py, the rules restated in Python integers
+# ---------------------------------------------------------------------------
+import sort_plan as SP  # noqa: E402
+
+WHY = {name: i for i, name in enumerate(SP.DECLINES)}
+
+
+def _label_ranges(nb):
+    """[lo, hi] label ranges of 2, 16, 1000 labels and the full range, at the
+    bottom, at the top and across the middle of [0, 2^nb)."""
+    size = 1 << nb
+    out = set()
+    for width in (2, 16, 1000, size):
+        w = min(width, size)
+        for lo in (0, size - w, max(0, min(size - w, size // 2 - w // 2))):
+            out.add((lo, lo + w - 1))
+    return sorted(out)
+
+
+def _gs_n_values(nb, ub, lo, hi):
+    """1 .. 2^32 - 1, and for every shift the record counts that put the
+    average bucket at GS_TARGET exactly and one record above it."""
+    ns = {1, 2, SP.GS_TARGET, SP.GS_TARGET + 1, 100000, 1 << 20, 1 << 31, (1 << 32) - 1}
+    kmin, kmax = SP.key_range(nb, ub, lo, hi)
+    for s in range(ub + nb, -1, -1):
+        c = (kmax >> s) - (kmin >> s) + 1
+        if c > SP.GS_M:
+            break
+        ns.update(n for n in (SP.GS_TARGET * c - 1, SP.GS_TARGET * c, SP.GS_TARGET * c + 1) if 0 < n < (1 << 32))
+    return sorted(ns)
+
+
+@pytest.fixture(scope='module')
+def gs_sweep(plan):
+    """(inputs, the plan's answer) for the whole sweep: nb 1 .. 32 (ub = nb, as
+    whole arrays sort; kb = 64 at nb = 32), every label range, two slot widths."""
+    cases = []
+    for nb in range(1, 33):
+        for lo, hi in _label_ranges(nb):
+            for n in _gs_n_values(nb, nb, lo, hi):
+                for ib in (16, 28):
+                    cases.append((n, nb, nb, ib, lo, hi))
+    # block-tagged geometry for completeness: u has 32 bits whatever the labels
+    cases += [(n, nb, 32, 20, lo, hi) for nb in (9, 20, 31) for lo, hi in _label_ranges(nb) for n in (5, 1 << 22)]
+    got = plan(['gsort %d %d %d %d %d %d' % c for c in cases])
+    return cases, [[int(v) for v in g.split()] for g in got]
+
+
+def test_group_sort_plan_matches_rule(gs_sweep):
+    cases, got = gs_sweep
+    seen = set()
+    for c, g in zip(cases, got):
+        exp = SP.plan_group_sort(*c)
+        seen.add(exp['why'])
+        assert g[0] == WHY[exp['why']], (c, g, exp)
+        if 'shift' in exp:
+            assert g[1:] == [exp['shift'], exp['nbk'], exp['bk0'], exp['min_pk'], exp['max_pk']], (c, g, exp)
+        else:
+            assert g[1] == -1, (c, g)
+    assert seen == {'none', 'key_bits', 'item_bits', 'low_bits'}
+    assert len(cases) > 10000
+
+
+def test_group_sort_plan_declines(plan):
+    """The reasons in their order: the record count first, then the key bits,
+    then the item and the low key bits."""
+    q = ['gsort 0 20 20 16 0 1000', 'gsort -1 20 20 16 0 1000', 'gsort 4294967296 20 20 16 0 1000',
+         'gsort 0 32 32 16 0 4294967295',           # n before kb
+         'gsort 5 32 32 16 0 4294967295', 'gsort 5 33 31 16 0 4294967295', 'gsort 5 31 33 16 0 2147483647',
+         'gsort 5 32 31 16 0 4294967295',           # 63 key bits pass; one bucket of 2^63 keys + 16 slot bits
+         'gsort 5 31 31 2 0 2147483647',            # 62 key bits, 5 records: one bucket of 2^62 keys (fits with 2 slot bits)
+         'gsort 5 20 20 40 0 1000000',              # shift 40 + 40 slot bits
+         'gsort 4294967295 31 31 16 2147483000 2147483647']
+    got = [[int(v) for v in g.split()] for g in plan(q)]
+    assert [g[0] for g in got] == [1, 1, 1, 1, 2, 2, 2, 3, 4, 3, 0]
+    assert all(g[1] == -1 and g[2:] == [0, 0, 0, 0] for g in got[:7])
+    assert got[7][1:3] == [63, 1] and got[8][1:3] == [62, 1]
+
+
+def _sample_keys(kmin, kmax, shift, bk0, nbk):
+    ks = {kmin, kmax}
+    ks.update(kmin + (kmax - kmin) * k // 7 for k in range(1, 7))
+    for j in (1, nbk // 2, nbk - 1):     # both sides of a bucket boundary
+        edge = (bk0 + j) << shift
+        ks.update(k for k in (edge - 1, edge) if kmin <= k <= kmax)
+    return sorted(ks)
+
+
+def _check_bucket_keys(plan, plans, max_buckets):
+    """For every (kmin, kmax, shift, bk0, nbk): the smallest key in bucket 0,
+    the largest in the last one, and every sampled key's bucket bits rebuilt
+    from its bucket.  Returns the largest (kmax >> shift) met."""
+    queries, expect = [], []
+    top = 0
+    for kmin, kmax, shift, bk0, nbk in sorted(plans):
+        assert 1 <= nbk <= max_buckets and bk0 == kmin >> shift and nbk == (kmax >> shift) - bk0 + 1
+        top = max(top, kmax >> shift)
+        for k in _sample_keys(kmin, kmax, shift, bk0, nbk):
+            queries.append('gskey %d %d %d' % (k, shift, bk0))
+            expect.append(((k >> shift) - bk0, (k >> shift) << shift, k == kmin, k == kmax, nbk))
+    got = plan(queries)
+    for q, g, (b, key, first, last, nbk) in zip(queries, got, expect):
+        gb, gkey = (int(v) for v in g.split())
+        assert gb == b and 0 <= gb < nbk, (q, g, b)
+        assert not first or gb == 0, (q, g)
+        assert not last or gb == nbk - 1, (q, g)
+        assert gkey == key, 'bucket bits rebuilt wrong: %s -> %s, expected %d' % (q, g, key)
+    return top
+
+
+def test_group_sort_bucket_key_rebuild(plan, gs_sweep):
+    """Every accepted plan of the sweep: at most GS_M buckets, min_pk in bucket
+    0, max_pk in bucket nbk - 1, and gs_bucket_key(gs_bucket_of(pk)) == (pk >>
+    shift) << shift at both ends, between them and on both sides of bucket
+    boundaries -- also where pk >> shift needs more than 32 bits (labels near
+    2^30 and above with many records a label), which the sweep must contain."""
+    cases, got = gs_sweep
+    plans = {(g[4], g[5], g[1], g[3], g[2]) for g in got if g[0] == 0}
+    assert len(plans) > 1000
+    top = _check_bucket_keys(plan, plans, SP.GS_M)
+    assert top >= 1 << 32
+    # bk0 below 2^32 and b + bk0 above it; and bk0 itself above 2^32
+    assert any(bk0 < (1 << 32) <= bk0 + nbk - 1 for _, _, _, bk0, nbk in plans)
+    assert any(bk0 >= (1 << 32) for _, _, _, bk0, _ in plans)
+
+
+def test_group_sort_record_heavy_labels_near_2_30(plan):
+    """The volumes of tests/test_gpu_label_widths.py, by the plan alone: 16
+    (5) labels from 2^30 with 7168 (8192) records a face reach shift 29, where
+    the bucket index passes 2^32; 16 labels from 2^29 stay below it."""
+    q = ['gsort %d 31 31 16 %d %d' % (15 * 7168, 1 << 30, (1 << 30) + 15),
+         'gsort %d 31 31 16 %d %d' % (4 * 8192, 1 << 30, (1 << 30) + 4),
+         'gsort %d 31 31 16 %d %d' % (15 * 7168, (1 << 30) - 8, (1 << 30) + 7),
+         'gsort %d 30 30 16 %d %d' % (15 * 7168, 1 << 29, (1 << 29) + 15)]
+    got = [[int(v) for v in g.split()] for g in plan(q)]
+    assert [g[:2] for g in got] == [[0, 29], [0, 29], [0, 29], [0, 28]]
+    assert [(g[5] >> g[1]) >= (1 << 32) for g in got] == [True, True, True, False]
+    assert got[2][3] < (1 << 32) <= got[2][3] + got[2][2] - 1      # bk0 fits 32 bits, bk0 + b does not
+    _check_bucket_keys(plan, {(g[4], g[5], g[1], g[3], g[2]) for g in got}, SP.GS_M)
+
+
+def test_bucket_keys_plan(plan):
+    """plan_bucket_keys over packed-key ranges (packed_key_range of label
+    ranges, slot bits 0 / 16 / 23) and record counts around every bucket-bit
+    step: the rule's shift, at most 2^BK_MAX_BITS buckets, kmin in bucket 0,
+    kmax in the last, bucket bits rebuilt."""
+    ns = sorted({1, 1023, (1 << 32) - 1} | {(1 << b) + d for b in range(10, 23) for d in (-1, 0)})
+    cases = []
+    for ib in (0, 16, 23):
+        for nb in range(1, (63 - ib) // 2 + 1):
+            for lo, hi in _label_ranges(nb):
+                kmin, kmax = _key_range(lo, hi, nb, ib)
+                cases += [(n, ib, ib + 2 * nb, kmin, kmax) for n in ns]
+    got = [[int(v) for v in g.split()] for g in plan(['bkeys %d %d %d %d %d' % c for c in cases])]
+    plans = set()
+    for c, g in zip(cases, got):
+        exp = SP.plan_bucket_keys(*c)
+        assert g == [1, exp['bb'], exp['shift'], exp['nbk'], exp['bk0']], (c, g, exp)
+        assert g[3] <= 1 << g[1] <= 1 << SP.BK_MAX_BITS and c[1] <= g[2] <= c[2] - g[1]
+        plans.add((c[3], c[4], g[2], g[4], g[3]))
+    assert len(cases) > 10000 and {g[1] for g in got} == set(range(1, SP.BK_MAX_BITS + 1))
+    assert _check_bucket_keys(plan, plans, 1 << SP.BK_MAX_BITS) >= 1 << 32
+    bad = ['bkeys 0 0 20 0 5', 'bkeys 4294967296 0 20 0 5', 'bkeys 5 0 65 0 5', 'bkeys 5 -1 20 0 5', 'bkeys 5 20 20 0 5',
+           'bkeys 5 0 20 6 5', 'bkeys 5000000 0 20 0 %d' % (1 << 40)]      # (the last: kmax past 2^hi_bit)
+    assert [g.split()[0] for g in plan(bad)] == ['0'] * len(bad)

@@ -25,6 +25,10 @@
 //   adjblocks N_CHANNELS                     -> need_adj of a batched call
 //   fold r[NREG]                             -> total fullest off[NREG + 1]
 //   xchg WORLD RANK ROW_WORDS RECEIVE counts[WORLD * WORLD * 2] -> rows nodes words
+//   gsort N NB UB IB MIN_LABEL MAX_LABEL     -> why shift nbk bk0 min_pk max_pk   (why: GroupSortPlan::Why; shift -1,
+//                                               the rest 0 where it declined before choosing)
+//   gskey PK SHIFT BK0                       -> gs_bucket_of(pk)  gs_bucket_key(that bucket)
+//   bkeys N LO_BIT HI_BIT KMIN KMAX          -> ok bb shift nbk bk0
 //
 // g++ -std=c++17 -fsanitize=address,undefined tools/plan_check.cpp -o plan_check
 #include <cinttypes>
@@ -170,6 +174,27 @@ int main() {
             for (int64_t& v : c) in >> v;
             const ExchangeCounts x = exchange_counts(c.data(), world, rank, row_words, receive);
             printf("%" PRId64 " %" PRId64 " %" PRId64 "\n", x.rows, x.nodes, x.words);
+        } else if (cmd == "gsort") {
+            int64_t n;
+            int nb, ub, ib;
+            uint64_t lo, hi;
+            in >> n >> nb >> ub >> ib >> lo >> hi;
+            const GroupSortPlan p = plan_group_sort(n, nb, ub, ib, lo, hi);
+            printf("%d %d %u %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", (int)p.why, p.shift, p.nbk, p.bk0, p.min_pk,
+                   p.max_pk);
+        } else if (cmd == "gskey") {
+            uint64_t pk, bk0;
+            int shift;
+            in >> pk >> shift >> bk0;
+            const uint32_t b = gs_bucket_of(pk, shift, bk0);
+            printf("%u %" PRIu64 "\n", b, gs_bucket_key(b, bk0, shift));
+        } else if (cmd == "bkeys") {
+            int64_t n;
+            int lo_bit, hi_bit;
+            uint64_t kmin, kmax;
+            in >> n >> lo_bit >> hi_bit >> kmin >> kmax;
+            const BucketKeysPlan p = plan_bucket_keys(n, lo_bit, hi_bit, kmin, kmax);
+            printf("%d %d %d %u %" PRIu64 "\n", (int)p.ok, p.bb, p.shift, p.nbk, p.bk0);
         } else {
             fprintf(stderr, "plan_check: unknown query '%s'\n", cmd.c_str());
             return 2;
