@@ -11,8 +11,6 @@
 
 using namespace ctg;
 
-constexpr int64_t TABLE_MAX_VOXELS = 0xFFFFFFFFll;   // a record per voxel at most; the run table numbers records in 32 bits
-
 // an overlaps / a morphology result without rows: the placeholders of
 // empty_result plus the counts' / the moments'
 static ResultPtr empty_overlaps(int device) {
@@ -52,7 +50,7 @@ struct DenseSide {
             return ctg_unique_labels((const uint64_t*)vol, shape, b, e, CTG_MEM_DEVICE, stream, u);
         });
         if (rc) return rc;
-        if (U->n_nodes > 0xFFFFFFFFll) {
+        if (U->n_nodes > RECORD_LIMIT) {
             set_error(std::string(who) + ": more than 2^32 distinct labels in one box");
             return CTG_ERR_UNSUPPORTED;
         }
@@ -65,6 +63,126 @@ struct DenseSide {
         return CTG_OK;
     }
 };
+
+// step 2: the ignore label as a rank of side's table; absent from the box: nothing to skip
+static int dense_ignore_rank(const DenseSide& side, int* has_ignore, uint64_t* ignore_label, hipStream_t s,
+                             const char* who) {
+    if (!side.U || !*has_ignore) return CTG_OK;
+    DevBuf<uint32_t> rank(4);
+    uint32_t h = 0;
+    if (!rank) return hip_status(hipErrorOutOfMemory, who);
+    CTG_CHECK(launch_overlap_find(side.U->nodes, side.U->n_nodes, *ignore_label, rank, s));
+    CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    *has_ignore = h != 0xFFFFFFFFu;
+    *ignore_label = h;
+    return CTG_OK;
+}
+
+// The scan of a table call, with its re-entry where labels reach 2^32 and do not fit the 32-bit keys.  vol, bits: the
+// call's n label volumes (device) and their widths; scan(&over) scans them as they stand then -- it reads them and the
+// ignore pair anew on every call.  0: the scan as given.  If it reports overflow (bit k: volume k), 1: those volumes
+// become monotone dense ids (d[k]); 2: so does the ignore label, if it is one of volume `ignore_vol`'s; 3: the scan
+// runs again on the ids; 4: which cannot overflow; 5: r's nodes, which are the first volume's, map back to labels
+// through d[0].U.  Whatever else holds ids (the pairs of the overlaps) the caller maps back.
+template <class Scan>
+static int dense_reentry(const char* who, const void** vol, int* bits, int n, int ignore_vol, int* has_ignore,
+                         uint64_t* ignore_label, const int64_t* shape, const int64_t* b, const int64_t* e,
+                         void* stream, Scan&& scan, DenseSide* d, ctg_result* r) {
+    unsigned over = 0, again = 0;
+    int rc = hip_status(scan(&over), who);
+    if (rc || !over) return rc;
+    for (int k = 0; k < n; ++k) {
+        if (!(over >> k & 1u)) continue;
+        if ((rc = d[k].build(vol[k], shape, b, e, stream, who)) != CTG_OK) return rc;
+        vol[k] = d[k].ids.p;
+        bits[k] = 32;
+    }
+    if (ignore_vol >= 0 &&
+        (rc = dense_ignore_rank(d[ignore_vol], has_ignore, ignore_label, (hipStream_t)stream, who)) != CTG_OK)
+        return rc;
+    if ((rc = hip_status(scan(&again), who)) != CTG_OK) return rc;
+    if (again) {
+        set_error(std::string(who) + ": dense ids past 2^32");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    if (d[0].U) CTG_CHECK(launch_gather_labels(d[0].U->nodes, r->nodes, r->n_nodes, (hipStream_t)stream));
+    return CTG_OK;
+}
+
+// ctg_merge_morphology and ctg_merge_region_features: n float64 rows of `cols` columns -> a result of `empty`'s kind
+// by `merge`.  (clear_first: the region call clears *out before its argument check, the morphology call after it.)
+static int merge_rows_entry(const char* who, const double* rows, int64_t n, int cols, int mem, void* stream,
+                            ResultPtr (*empty)(int),
+                            hipError_t (*merge)(Workspace&, const double*, int64_t, hipStream_t, ctg_result*, int*),
+                            const char* bad_message, bool clear_first, ctg_result** out) {
+    ApiCall c;
+    if (clear_first && out) *out = nullptr;
+    if (!out || n < 0 || (n > 0 && !rows)) {
+        set_error(std::string(who) + ": bad arguments");
+        return CTG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (n >= RECORD_LIMIT) {
+        set_error(std::string(who) + ": 2^32 rows or more in one call");
+        return CTG_ERR_UNSUPPORTED;
+    }
+    int rc = c.begin(stream, empty);
+    if (rc) return rc;
+    if (n == 0) return c.end(false, out);
+    hipStream_t s = c.s;
+    DevInput<double> dr;
+    if ((rc = dr.put(rows, (size_t)n * cols * 8, mem, s, who)) != CTG_OK) return rc;
+    int bad = 0;
+    if ((rc = hip_status(merge(c.w(), dr, n, s, c.r.get(), &bad), who)) != CTG_OK) return rc;
+    if (bad) {
+        set_error(std::string(who) + bad_message);
+        return CTG_ERR_ARG;
+    }
+    CTG_CHECK(hipStreamSynchronize(s));
+    return c.end(false, out);
+}
+
+// ctg_morphology_rows and ctg_region_rows, after the checks of their own: the N nodes of r as float64 rows of `cols`
+// columns, dense over [label_begin, label_end) into out and / or compact into rows, by launch(od, orw).  copy_fn: the
+// call that holds any label.  (range_first: the region call checks the label range before the top label, the
+// morphology call after it.)
+template <class Launch>
+static int rows_entry(const char* who, const ctg_result* r, uint64_t label_begin, uint64_t label_end, int cols,
+                      const char* copy_fn, bool range_first, double* out, double* rows, int mem, hipStream_t s,
+                      Launch&& launch) {
+    const int64_t N = r->n_nodes;
+    const uint64_t n = label_end - label_begin;
+    const auto range = [&]() -> int {
+        if (n <= (1ull << 40)) return CTG_OK;
+        set_error(std::string(who) + ": label range too large");
+        return CTG_ERR_ARG;
+    };
+    // the id column is a float64: the largest label (the last: nodes ascend) must fit it
+    const auto top_label = [&]() -> int {
+        uint64_t top = 0;
+        if (N == 0) return CTG_OK;
+        CTG_CHECK(hipMemcpyAsync(&top, r->nodes + (N - 1), 8, hipMemcpyDeviceToHost, s));
+        CTG_CHECK(hipStreamSynchronize(s));
+        if (top < (1ull << 53)) return CTG_OK;
+        set_error(std::string(who) + ": a label of 2^53 or more does not fit the float64 id column (" + copy_fn +
+                  " holds any label)");
+        return CTG_ERR_UNSUPPORTED;
+    };
+    int rc = range_first ? range() : top_label();
+    if (!rc) rc = range_first ? top_label() : range();
+    if (rc) return rc;
+    DenseOut<double> od, orw;
+    rc = hip_status(od.open(out, (size_t)n * cols * 8, mem, true, s), who);
+    if (!rc) rc = hip_status(orw.open(rows, (size_t)N * cols * 8, mem, false, s), who);
+    if (rc) return rc;
+    if (!od.d && !orw.d) return CTG_OK;
+    CTG_CHECK(launch(od.d, orw.d));
+    CTG_CHECK(od.copy_back(s));
+    CTG_CHECK(orw.copy_back(s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
 
 extern "C" {
 
@@ -83,7 +201,7 @@ int ctg_label_overlaps(const void* labels, int label_bits, const void* values, i
         return CTG_ERR_ARG;
     }
     CallBox box;
-    int rc = box_of(who, shape, begin, end, TABLE_MAX_VOXELS, &box);
+    int rc = box_of(who, shape, begin, end, RECORD_LIMIT, &box);
     if (rc || (rc = c.begin(stream, empty_overlaps)) != CTG_OK) return rc;
     if (box.voxels == 0) return c.end(false, out);
     const int64_t *b = box.b, *e = box.e;
@@ -95,46 +213,20 @@ int ctg_label_overlaps(const void* labels, int label_bits, const void* values, i
     rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
     if (!rc) rc = stage_in(w.stage[1], values, (size_t)V * (value_bits / 8), mem, s, &dv);
     if (rc) return rc;
-    unsigned over = 0;
-    if ((rc = hip_status(overlap_tables(w, dl, label_bits, dv, value_bits, shape, b, e, with_ignore, ignore_label, s,
-                                        r, &over),
-                         who)) != CTG_OK)
-        return rc;
-    if (over) {
-        // labels >= 2^32 do not fit the 32 + 32 bit keys.  1: the side(s) that
-        // hold them become monotone dense ids
-        DenseSide da, db;
-        if ((over & 1u) && (rc = da.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
-        if ((over & 2u) && (rc = db.build(dv, shape, b, e, stream, who)) != CTG_OK) return rc;
-        // 2: so does the ignore label (absent from the box: nothing to skip)
-        if ((over & 2u) && with_ignore) {
-            DevBuf<uint32_t> rank(4);
-            uint32_t h = 0;
-            if (!rank) return hip_status(hipErrorOutOfMemory, who);
-            CTG_CHECK(launch_overlap_find(db.U->nodes, db.U->n_nodes, ignore_label, rank, s));
-            CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
-            CTG_CHECK(hipStreamSynchronize(s));
-            with_ignore = h != 0xFFFFFFFFu;
-            ignore_label = h;
-        }
-        // 3: the scan runs again on the ids
-        unsigned again = 0;
-        if ((rc = hip_status(overlap_tables(w, da.U ? (const void*)da.ids.p : dl, da.U ? 32 : label_bits,
-                                            db.U ? (const void*)db.ids.p : dv, db.U ? 32 : value_bits, shape, b, e,
-                                            with_ignore, ignore_label, s, r, &again),
-                             who)) != CTG_OK)
-            return rc;
-        // 4: which cannot overflow
-        if (again) {
-            set_error("ctg_label_overlaps: dense ids past 2^32");
-            return CTG_ERR_UNSUPPORTED;
-        }
-        // 5: the sorted tables map back to labels
-        CTG_CHECK(launch_overlap_map_back(r->n_edges, r->edges, da.U ? da.U->nodes : nullptr,
-                                          da.U ? da.U->n_nodes : 0, db.U ? db.U->nodes : nullptr,
-                                          db.U ? db.U->n_nodes : 0, s));
-        if (da.U) CTG_CHECK(launch_gather_labels(da.U->nodes, r->nodes, r->n_nodes, s));
-    }
+    const void* vol[2] = {dl, dv};
+    int bits[2] = {label_bits, value_bits};
+    DenseSide d[2];
+    rc = dense_reentry(who, vol, bits, 2, 1, &with_ignore, &ignore_label, shape, b, e, stream,
+                       [&](unsigned* over) {
+                           return overlap_tables(w, vol[0], bits[0], vol[1], bits[1], shape, b, e, with_ignore,
+                                                 ignore_label, s, r, over);
+                       },
+                       d, r);
+    if (rc) return rc;
+    // 5, the overlaps' own: the pairs map back to labels
+    CTG_CHECK(launch_overlap_map_back(r->n_edges, r->edges, d[0].U ? d[0].U->nodes : nullptr,
+                                      d[0].U ? d[0].U->n_nodes : 0, d[1].U ? d[1].U->nodes : nullptr,
+                                      d[1].U ? d[1].U->n_nodes : 0, s));
     return c.end(r->n_records > 0, out, true);
 }
 
@@ -146,7 +238,7 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
         return CTG_ERR_ARG;
     }
     *out = nullptr;
-    if (n >= 0xFFFFFFFFll) {
+    if (n >= RECORD_LIMIT) {
         set_error("ctg_merge_overlaps: 2^32 rows or more in one call");
         return CTG_ERR_UNSUPPORTED;
     }
@@ -168,7 +260,7 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
     const uint64_t* src = dp;
     if (w.counters_host->max_v >> 32) {
         if ((rc = dense.build(dp, n, s)) != CTG_OK) return rc;
-        if (dense.U->n_nodes > 0xFFFFFFFFll) {
+        if (dense.U->n_nodes > RECORD_LIMIT) {
             set_error("ctg_merge_overlaps: more than 2^32 distinct labels");
             return CTG_ERR_UNSUPPORTED;
         }
@@ -224,7 +316,7 @@ int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, con
     }
     CallBox box;
     int64_t o[3];
-    int rc = box_of(who, shape, begin, end, TABLE_MAX_VOXELS, &box);
+    int rc = box_of(who, shape, begin, end, RECORD_LIMIT, &box);
     if (rc) return rc;
     const int64_t *b = box.b, *e = box.e;
     for (int k = 0; k < 3; ++k) {
@@ -243,53 +335,19 @@ int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, con
     const int64_t V = shape[0] * shape[1] * shape[2];
     const void* dl = nullptr;
     if ((rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl)) != CTG_OK) return rc;
-    unsigned over = 0;
-    if ((rc = hip_status(morph_tables(w, dl, label_bits, shape, b, e, o, s, r, &over), who)) != CTG_OK) return rc;
-    if (over) {
-        // labels >= 2^32 do not fit the table's 32-bit keys.  1: the labels
-        // become monotone dense ids (2: no ignore label here)
-        DenseSide d;
-        if ((rc = d.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
-        // 3: the scan runs again on the ids
-        unsigned again = 0;
-        if ((rc = hip_status(morph_tables(w, d.ids.p, 32, shape, b, e, o, s, r, &again), who)) != CTG_OK) return rc;
-        // 4: which cannot overflow
-        if (again) {
-            set_error("ctg_morphology: dense ids past 2^32");
-            return CTG_ERR_UNSUPPORTED;
-        }
-        // 5: the sorted ids map back to labels
-        CTG_CHECK(launch_gather_labels(d.U->nodes, r->nodes, r->n_nodes, s));
-    }
+    DenseSide d;
+    rc = dense_reentry(   // (2: no ignore label here)
+        who, &dl, &label_bits, 1, -1, nullptr, nullptr, shape, b, e, stream,
+        [&](unsigned* over) { return morph_tables(w, dl, label_bits, shape, b, e, o, s, r, over); }, &d, r);
+    if (rc) return rc;
     return c.end(true, out, true);
 }
 
 int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
-    ApiCall c;
-    if (!out || n < 0 || (n > 0 && !rows)) {
-        set_error("ctg_merge_morphology: bad arguments");
-        return CTG_ERR_ARG;
-    }
-    *out = nullptr;
-    if (n >= 0xFFFFFFFFll) {
-        set_error("ctg_merge_morphology: 2^32 rows or more in one call");
-        return CTG_ERR_UNSUPPORTED;
-    }
-    int rc = c.begin(stream, empty_morphology);
-    if (rc) return rc;
-    if (n == 0) return c.end(false, out);
-    hipStream_t s = c.s;
-    DevInput<double> dr;
-    if ((rc = dr.put(rows, (size_t)n * CTG_MORPH_COLS * 8, mem, s, "ctg_merge_morphology")) != CTG_OK) return rc;
-    int bad = 0;
-    if ((rc = hip_status(morph_merge(c.w(), dr, n, s, c.r.get(), &bad), "ctg_merge_morphology")) != CTG_OK) return rc;
-    if (bad) {
-        set_error("ctg_merge_morphology: a row's id is not an integer in [0, 2^53), or its size, centre or box is "
-                  "negative or not finite");
-        return CTG_ERR_ARG;
-    }
-    CTG_CHECK(hipStreamSynchronize(s));
-    return c.end(false, out);
+    return merge_rows_entry(
+        "ctg_merge_morphology", rows, n, CTG_MORPH_COLS, mem, stream, empty_morphology, morph_merge,
+        ": a row's id is not an integer in [0, 2^53), or its size, centre or box is negative or not finite", false,
+        out);
 }
 
 int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end, double* out, double* rows,
@@ -304,32 +362,9 @@ int ctg_morphology_rows(const ctg_result* r, uint64_t label_begin, uint64_t labe
         return CTG_ERR_ARG;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int64_t N = r->n_nodes;
-    if (N > 0) {   // the id column is a float64: the largest label (the last: nodes ascend) must fit it
-        uint64_t top = 0;
-        CTG_CHECK(hipMemcpyAsync(&top, r->nodes + (N - 1), 8, hipMemcpyDeviceToHost, s));
-        CTG_CHECK(hipStreamSynchronize(s));
-        if (top >= (1ull << 53)) {
-            set_error("ctg_morphology_rows: a label of 2^53 or more does not fit the float64 id column "
-                      "(ctg_result_copy_moments holds any label)");
-            return CTG_ERR_UNSUPPORTED;
-        }
-    }
-    const uint64_t n = label_end - label_begin;
-    if (n > (1ull << 40)) {
-        set_error("ctg_morphology_rows: label range too large");
-        return CTG_ERR_ARG;
-    }
-    DenseOut<double> od, orw;
-    int rc = hip_status(od.open(out, (size_t)n * CTG_MORPH_COLS * 8, mem, true, s), "ctg_morphology_rows");
-    if (!rc) rc = hip_status(orw.open(rows, (size_t)N * CTG_MORPH_COLS * 8, mem, false, s), "ctg_morphology_rows");
-    if (rc) return rc;
-    if (!od.d && !orw.d) return CTG_OK;
-    CTG_CHECK(launch_morph_rows(r, label_begin, label_end, od.d, orw.d, s));
-    CTG_CHECK(od.copy_back(s));
-    CTG_CHECK(orw.copy_back(s));
-    CTG_CHECK(hipStreamSynchronize(s));
-    return CTG_OK;
+    return rows_entry("ctg_morphology_rows", r, label_begin, label_end, CTG_MORPH_COLS, "ctg_result_copy_moments",
+                      false, out, rows, mem, s,
+                      [&](double* od, double* oc) { return launch_morph_rows(r, label_begin, label_end, od, oc, s); });
 }
 
 int ctg_region_features(const void* labels, int label_bits, const void* data, int data_kind, const int64_t* shape,
@@ -355,7 +390,7 @@ int ctg_region_features(const void* labels, int label_bits, const void* data, in
         return CTG_ERR_ARG;
     }
     CallBox box;
-    int rc = box_of(who, shape, begin, end, TABLE_MAX_VOXELS, &box);
+    int rc = box_of(who, shape, begin, end, RECORD_LIMIT, &box);
     if (rc || (rc = c.begin(stream, empty_region)) != CTG_OK) return rc;
     if (box.voxels == 0) return c.end(false, out);
     const int64_t *b = box.b, *e = box.e;
@@ -367,71 +402,21 @@ int ctg_region_features(const void* labels, int label_bits, const void* data, in
     rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl);
     if (!rc) rc = stage_in(w.stage[1], data, (size_t)V * (data_kind == CTG_DATA_U8 ? 1 : 4), mem, s, &dd);
     if (rc) return rc;
-    unsigned over = 0;
-    if ((rc = hip_status(region_tables(w, dl, label_bits, dd, data_kind, shape, b, e, has_ignore, ignore_label, s, r,
-                                       &over),
-                         who)) != CTG_OK)
-        return rc;
-    if (over) {
-        // labels >= 2^32 do not fit the table's 32-bit keys.  1: the labels
-        // become monotone dense ids
-        DenseSide d;
-        if ((rc = d.build(dl, shape, b, e, stream, who)) != CTG_OK) return rc;
-        // 2: so does the ignore label (absent from the box: nothing to skip)
-        if (has_ignore) {
-            DevBuf<uint32_t> rank(4);
-            uint32_t h = 0;
-            if (!rank) return hip_status(hipErrorOutOfMemory, who);
-            CTG_CHECK(launch_overlap_find(d.U->nodes, d.U->n_nodes, ignore_label, rank, s));
-            CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
-            CTG_CHECK(hipStreamSynchronize(s));
-            has_ignore = h != 0xFFFFFFFFu;
-            ignore_label = h;
-        }
-        // 3: the scan runs again on the ids
-        unsigned again = 0;
-        if ((rc = hip_status(region_tables(w, d.ids.p, 32, dd, data_kind, shape, b, e, has_ignore, ignore_label, s, r,
-                                           &again),
-                             who)) != CTG_OK)
-            return rc;
-        // 4: which cannot overflow
-        if (again) {
-            set_error("ctg_region_features: dense ids past 2^32");
-            return CTG_ERR_UNSUPPORTED;
-        }
-        // 5: the sorted ids map back to labels
-        CTG_CHECK(launch_gather_labels(d.U->nodes, r->nodes, r->n_nodes, s));
-    }
+    DenseSide d;
+    rc = dense_reentry(who, &dl, &label_bits, 1, 0, &has_ignore, &ignore_label, shape, b, e, stream,
+                       [&](unsigned* over) {
+                           return region_tables(w, dl, label_bits, dd, data_kind, shape, b, e, has_ignore,
+                                                ignore_label, s, r, over);
+                       },
+                       &d, r);
+    if (rc) return rc;
     return c.end(r->n_records > 0, out, true);
 }
 
 int ctg_merge_region_features(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
-    ApiCall c;
-    if (out) *out = nullptr;
-    if (!out || n < 0 || (n > 0 && !rows)) {
-        set_error("ctg_merge_region_features: bad arguments");
-        return CTG_ERR_ARG;
-    }
-    if (n >= 0xFFFFFFFFll) {
-        set_error("ctg_merge_region_features: 2^32 rows or more in one call");
-        return CTG_ERR_UNSUPPORTED;
-    }
-    int rc = c.begin(stream, empty_region);
-    if (rc) return rc;
-    if (n == 0) return c.end(false, out);
-    hipStream_t s = c.s;
-    DevInput<double> dr;
-    if ((rc = dr.put(rows, (size_t)n * CTG_REGION_COLS * 8, mem, s, "ctg_merge_region_features")) != CTG_OK) return rc;
-    int bad = 0;
-    if ((rc = hip_status(region_merge(c.w(), dr, n, s, c.r.get(), &bad), "ctg_merge_region_features")) != CTG_OK)
-        return rc;
-    if (bad) {
-        set_error("ctg_merge_region_features: a row's id is not an integer in [0, 2^53), or its count is negative or "
-                  "not finite");
-        return CTG_ERR_ARG;
-    }
-    CTG_CHECK(hipStreamSynchronize(s));
-    return c.end(false, out);
+    return merge_rows_entry(
+        "ctg_merge_region_features", rows, n, CTG_REGION_COLS, mem, stream, empty_region, region_merge,
+        ": a row's id is not an integer in [0, 2^53), or its count is negative or not finite", true, out);
 }
 
 int ctg_region_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_end, int form, double norm, double* out,
@@ -453,33 +438,11 @@ int ctg_region_rows(const ctg_result* r, uint64_t label_begin, uint64_t label_en
         set_error("ctg_region_rows: not a region-features result (ctg_region_features, ctg_merge_region_features)");
         return CTG_ERR_ARG;
     }
-    const uint64_t n = label_end - label_begin;
-    if (n > (1ull << 40)) {
-        set_error("ctg_region_rows: label range too large");
-        return CTG_ERR_ARG;
-    }
     hipStream_t s = (hipStream_t)stream;
-    const int64_t N = r->n_nodes;
-    if (N > 0) {   // the id column is a float64: the largest label (the last: nodes ascend) must fit it
-        uint64_t top = 0;
-        CTG_CHECK(hipMemcpyAsync(&top, r->nodes + (N - 1), 8, hipMemcpyDeviceToHost, s));
-        CTG_CHECK(hipStreamSynchronize(s));
-        if (top >= (1ull << 53)) {
-            set_error("ctg_region_rows: a label of 2^53 or more does not fit the float64 id column "
-                      "(ctg_result_copy_region holds any label)");
-            return CTG_ERR_UNSUPPORTED;
-        }
-    }
-    DenseOut<double> od, orw;
-    int rc = hip_status(od.open(out, (size_t)n * CTG_REGION_COLS * 8, mem, true, s), "ctg_region_rows");
-    if (!rc) rc = hip_status(orw.open(rows, (size_t)N * CTG_REGION_COLS * 8, mem, false, s), "ctg_region_rows");
-    if (rc) return rc;
-    if (!od.d && !orw.d) return CTG_OK;
-    CTG_CHECK(launch_region_rows(r, label_begin, label_end, form, norm, od.d, orw.d, s));
-    CTG_CHECK(od.copy_back(s));
-    CTG_CHECK(orw.copy_back(s));
-    CTG_CHECK(hipStreamSynchronize(s));
-    return CTG_OK;
+    return rows_entry("ctg_region_rows", r, label_begin, label_end, CTG_REGION_COLS, "ctg_result_copy_region", true,
+                      out, rows, mem, s, [&](double* od, double* orw) {
+                          return launch_region_rows(r, label_begin, label_end, form, norm, od, orw, s);
+                      });
 }
 
 int ctg_assignment_dense(const uint64_t* table, int64_t n, int mem, void* stream, ctg_assignment** out) {

@@ -85,6 +85,11 @@ constexpr uint32_t PIV_EMPTY = 0xFFFFFFFFu;   // table entry without a pivot yet
 constexpr uint32_t ADJ_FLAG = 0x80000000u;  // record/edge came from a nearest-neighbour face
 constexpr uint64_t EMPTY_KEY = ~0ull;
 constexpr int N_FEATURES = 10;
+// The label-table calls (overlaps, morphology, region features) take fewer
+// voxels, rows and records than this in one call: a record per voxel at most,
+// and the run fold numbers records and rows in 32 bits, all ones being no row
+// (ctg_run_fold.h)
+constexpr int64_t RECORD_LIMIT = 0xFFFFFFFFll;
 
 // order-preserving float <-> u32 mapping for LDS/global atomicMin/Max
 __host__ __device__ inline uint32_t f2ord(float f) {

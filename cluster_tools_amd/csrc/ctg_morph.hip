@@ -7,7 +7,8 @@
 //                  per (tile flush, label): a tile-table scan (ctg_tile_table.h)
 //   k_morph_merge  float64 rows [id, size, com, min, max] -> the same records
 //   sort_and_number   (key, record slot) sorted by key, the distinct labels numbered
-//   k_morph_runs   per label: n and the three sums add in u64, the box folds
+//   k_morph_runs   per label: n and the three sums add in u64, the box folds: a
+//                  run fold (ctg_run_fold.h)
 //   k_morph_finish origin added in integers: sums += n * origin, box += origin
 //   k_morph_rows   moments -> float64 rows, compact and / or dense over a label range
 //
@@ -32,13 +33,9 @@
 // cell 10): the compiled scan takes 58 VGPRs and no scratch, so the LDS bounds
 // the waves per SIMD -- measured at 512^3 / 1024^3, 2048 entries (56 KiB) 1.10 /
 // 8.54 ms, 1024 0.51 / 3.80 ms, 512 0.40 / 2.97 ms, 256 0.41 / 3.01 ms.
-//
-// Every buffer here is call-sized and comes from the pool (DevBuf); nothing
-// touches the workspace's record or sort buffers, so a CTG_DEFER_STATS handle
-// stays valid across these calls.
 #include <hip/hip_runtime.h>
 
-#include "ctg_tile_table.h"
+#include "ctg_run_fold.h"
 
 namespace ctg {
 
@@ -195,11 +192,6 @@ __global__ void k_morph_merge(int64_t n, const double* __restrict__ rows, uint64
     for (int c = 0; c < MORPH_WORDS; ++c) rec[i * MORPH_WORDS + c] = q[c];
 }
 
-__global__ void k_morph_iota(int64_t n, uint32_t* __restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) idx[i] = (uint32_t)i;
-}
-
 // the identity of k_morph_runs' folds: sums 0, min all ones, max 0
 __global__ void k_morph_init(int64_t N, uint64_t* __restrict__ mom) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -208,50 +200,51 @@ __global__ void k_morph_init(int64_t N, uint64_t* __restrict__ mom) {
     mom[i] = (c >= 4 && c < 7) ? ~0ull : 0ull;
 }
 
-// Sorted position i holds record slot[i] of label number scan[i].lo - 1.  A
-// wave folds the records of its 64 positions per label (segmented suffix folds
-// by shuffles: add for n and the sums, min / max for the box) and the first
-// lane of every segment applies the fold to the label's row -- one atomic set
-// per (wave, label), none contended unless a label spans waves.  mom is
-// initialised by k_morph_init before the launch.
-__global__ __launch_bounds__(256) void k_morph_runs(int64_t n, const uint64_t* __restrict__ key,
-                                                    const uint32_t* __restrict__ slot,
-                                                    const uint64_t* __restrict__ scan,
-                                                    const uint64_t* __restrict__ rec, int64_t n_rec,
-                                                    uint64_t* __restrict__ nodes,
-                                                    unsigned long long* __restrict__ mom, int64_t N) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const bool in = i < n;
-    const uint64_t sc = in ? scan[i] : 0ull, sp = (in && i) ? scan[i - 1] : 0ull;
-    const uint32_t seg = in ? (uint32_t)sc - 1u : 0xFFFFFFFFu;   // (labels < 2^32 - 1: the record limit)
-    uint64_t v[MORPH_WORDS];
-    if (in) {
-        const uint32_t j = slot[i];
-        CTG_IDX(j, n_rec);
-        for (int c = 0; c < MORPH_WORDS; ++c) v[c] = rec[(int64_t)j * MORPH_WORDS + c];
-    } else {
-        for (int c = 0; c < MORPH_WORDS; ++c) v[c] = (c >= 4 && c < 7) ? ~0ull : 0ull;
+// The run-fold policy of the morphology (ctg_run_fold.h): sorted position i
+// holds the 10-word record slot[i]; n and the three sums add, the box folds by
+// min / max, all in u64, onto the label's row of mom (k_morph_init's identities
+// before the launch).  A run head writes the label.
+struct MorphRuns {
+    using Value = uint64_t[MORPH_WORDS];
+    const uint64_t *__restrict__ key, *__restrict__ rec;
+    const uint32_t* __restrict__ slot;
+    int64_t n_rec;
+    uint64_t* __restrict__ nodes;
+    unsigned long long* __restrict__ mom;
+    __device__ __forceinline__ void load(Value& v, int64_t i, bool in) const {
+        if (in) {
+            const uint32_t j = slot[i];
+            CTG_IDX(j, n_rec);
+            for (int c = 0; c < MORPH_WORDS; ++c) v[c] = rec[(int64_t)j * MORPH_WORDS + c];
+        } else {
+            for (int c = 0; c < MORPH_WORDS; ++c) v[c] = (c >= 4 && c < 7) ? ~0ull : 0ull;
+        }
     }
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t so = __shfl_down(seg, o, WAVE);
-        const bool take = lane + o < WAVE && so == seg;
+    __device__ __forceinline__ void combine(Value& v, int o, bool take) const {
 #pragma unroll
         for (int c = 0; c < MORPH_WORDS; ++c) {
             const uint64_t vo = shfl_down_u64(v[c], o);
             if (take) v[c] = c < 4 ? v[c] + vo : c < 7 ? (vo < v[c] ? vo : v[c]) : (vo > v[c] ? vo : v[c]);
         }
     }
-    const uint32_t sprev = __shfl_up(seg, 1, WAVE);
-    if (!in) return;
-    if (lane == 0 || sprev != seg) {
-        CTG_IDX(seg, N);
+    __device__ __forceinline__ void apply(uint32_t seg, const Value& v) const {
         unsigned long long* m = mom + (int64_t)seg * MORPH_WORDS;
         for (int c = 0; c < 4; ++c) atomicAdd(&m[c], (unsigned long long)v[c]);
         for (int c = 4; c < 7; ++c) atomicMin(&m[c], (unsigned long long)v[c]);
         for (int c = 7; c < 10; ++c) atomicMax(&m[c], (unsigned long long)v[c]);
     }
-    if ((uint32_t)sc != (uint32_t)sp) nodes[seg] = key[i];
+    __device__ __forceinline__ void name(int64_t i, uint32_t seg, bool head, uint64_t, uint64_t) const {
+        if (head) nodes[seg] = key[i];
+    }
+};
+
+__global__ __launch_bounds__(256) void k_morph_runs(int64_t n, const uint64_t* __restrict__ key,
+                                                    const uint32_t* __restrict__ slot,
+                                                    const uint64_t* __restrict__ scan,
+                                                    const uint64_t* __restrict__ rec, int64_t n_rec,
+                                                    uint64_t* __restrict__ nodes,
+                                                    unsigned long long* __restrict__ mom, int64_t N) {
+    run_fold(MorphRuns{key, rec, slot, n_rec, nodes, mom}, n, scan, N);
 }
 
 // coordinates = array index + origin: sums += n * origin, box += origin; a
@@ -290,87 +283,48 @@ __global__ void k_morph_rows(int64_t N, const uint64_t* __restrict__ nodes, cons
         for (int c = 0; c < CTG_MORPH_COLS; ++c) out[(a - lb) * CTG_MORPH_COLS + c] = r[c];
 }
 
-// n (key, record) pairs -> r's nodes and moments (array coordinates + origin):
-// sort the record slots by key, number the labels, fold.  n in (0, 2^32 - 1);
-// keys compare in their low end_bit bits.
+// n (key, record) pairs -> r's nodes and moments (array coordinates + origin);
+// keys compare in their low end_bit bits
 static hipError_t morph_reduce(Workspace& w, const uint64_t* key, const uint64_t* rec, int64_t n, unsigned end_bit,
                                const int64_t* origin, hipStream_t s, ctg_result* r) {
-    Ev ev{w, s};
-    DevBuf<uint64_t> ks((size_t)n * 8), scan((size_t)n * 8);
-    DevBuf<uint32_t> idx((size_t)n * 4), is((size_t)n * 4);
-    if (!ks || !scan || !idx || !is) return hipErrorOutOfMemory;
-    hipLaunchKernelGGL(k_morph_iota, grid_for(n), dim3(256), 0, s, n, idx.p);
-    CTG_TRY(hipGetLastError());
-    uint64_t last = 0;
-    CTG_TRY(sort_and_number(w, key, (const uint32_t*)idx.p, n, end_bit, s, ks.p, is.p, scan.p, &last));
-    idx.reset();
-    const int64_t N = (int64_t)(uint32_t)last;
-    DevBuf<uint64_t> nodes((size_t)N * 8), mom((size_t)N * MORPH_WORDS * 8);
-    if (!nodes || !mom) return hipErrorOutOfMemory;
-    hipLaunchKernelGGL(k_morph_init, grid_for(N * MORPH_WORDS), dim3(256), 0, s, N, mom.p);
-    CTG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_morph_runs, grid_for(n), dim3(256), 0, s, n, ks.p, is.p, scan.p, rec, n, nodes.p,
-                       (unsigned long long*)mom.p, N);
-    CTG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_morph_finish, grid_for(N), dim3(256), 0, s, N, mom.p, (uint64_t)origin[0],
-                       (uint64_t)origin[1], (uint64_t)origin[2]);
-    CTG_TRY(hipGetLastError());
-    ev.mark(5);
-    dev_free(r->nodes);
-    dev_free(r->moments);
-    r->nodes = nodes.release();
-    r->moments = mom.release();
-    r->n_nodes = N;
-    return hipSuccess;
+    return fold_records<true, uint32_t>(
+        w, key, nullptr, n, end_bit, s,
+        [&](const uint64_t* ks, const uint32_t* is, const uint64_t* scan, int64_t N, int64_t) {
+            DevBuf<uint64_t> nodes((size_t)N * 8), mom((size_t)N * MORPH_WORDS * 8);
+            if (!nodes || !mom) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(k_morph_init, grid_for(N * MORPH_WORDS), dim3(256), 0, s, N, mom.p);
+            CTG_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_morph_runs, grid_for(n), dim3(256), 0, s, n, ks, is, scan, rec, n, nodes.p,
+                               (unsigned long long*)mom.p, N);
+            CTG_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_morph_finish, grid_for(N), dim3(256), 0, s, N, mom.p, (uint64_t)origin[0],
+                               (uint64_t)origin[1], (uint64_t)origin[2]);
+            CTG_TRY(hipGetLastError());
+            swap_in(r->nodes, nodes);
+            swap_in(r->moments, mom);
+            r->n_nodes = N;
+            return hipSuccess;
+        });
 }
 
 hipError_t morph_tables(Workspace& w, const void* A, int bits, const int64_t* shape, const int64_t* b,
                         const int64_t* e, const int64_t* origin, hipStream_t s, ctg_result* r, unsigned* overflow) {
-    Ev ev{w, s};
-    DevBuf<uint64_t> rkey, rec;
-    int64_t m = 0;
-    CTG_TRY(scan_into_records(
-        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s,
-        [&](int64_t cap) {
-            rkey.reset();
-            rec.reset();
-            if (!rkey.alloc((size_t)cap * 8) || !rec.alloc((size_t)cap * MORPH_WORDS * 8)) return hipErrorOutOfMemory;
+    return scan_tables<uint64_t>(
+        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s, MORPH_WORDS,
+        [&](uint64_t* rkey, uint64_t* rec, int64_t cap) {
             return bits == 32 ? launch_morph_scan_t<uint32_t>(A, shape, b, e, rkey, rec, cap, w.counters, s)
                               : launch_morph_scan_t<uint64_t>(A, shape, b, e, rkey, rec, cap, w.counters, s);
         },
-        &m, overflow));
-    if (*overflow) return hipSuccess;
-    if (m <= 0 || m >= 0xFFFFFFFFll) return hipErrorInvalidValue;   // (the API refuses empty and 2^32-voxel boxes)
-    r->n_records = m;
-    r->n_direct = (int64_t)w.counters_host->n_direct;
-    CTG_TRY(morph_reduce(w, rkey, rec, m, 32u, origin, s, r));
-    ev.mark(6);
-    return hipSuccess;
+        [&](const uint64_t* k, const uint64_t* q, int64_t m) { return morph_reduce(w, k, q, m, 32u, origin, s, r); },
+        false, r, overflow);   // (no ignore label: a box without records is refused)
 }
 
 hipError_t morph_merge(Workspace& w, const double* rows, int64_t n, hipStream_t s, ctg_result* r, int* bad) {
-    *bad = 0;
-    Ev ev{w, s};
-    DevBuf<uint64_t> key((size_t)n * 8), rec((size_t)n * MORPH_WORDS * 8);
-    if (!key || !rec) return hipErrorOutOfMemory;
-    CTG_TRY(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
-    ev.mark(0);
-    hipLaunchKernelGGL(k_morph_merge, grid_for(n), dim3(256), 0, s, n, rows, key.p, rec.p,
-                       &w.counters->label_overflow);
-    CTG_TRY(hipGetLastError());
-    ev.mark(1);
-    ev.mark(2);
-    CTG_TRY(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
-    CTG_TRY(hipStreamSynchronize(s));
-    if (w.counters_host->label_overflow) {
-        *bad = 1;
-        return hipSuccess;
-    }
     const int64_t zero[3] = {0, 0, 0};
-    CTG_TRY(morph_reduce(w, key, rec, n, 53u, zero, s, r));
-    ev.mark(6);
-    r->n_records = n;
-    return hipSuccess;
+    return merge_rows(
+        w, rows, n, MORPH_WORDS, k_morph_merge,
+        [&](const uint64_t* key, const uint64_t* rec) { return morph_reduce(w, key, rec, n, 53u, zero, s, r); }, s, r,
+        bad);
 }
 
 hipError_t launch_morph_rows(const ctg_result* r, uint64_t lb, uint64_t le, double* out, double* rows, hipStream_t s) {

@@ -7,21 +7,18 @@
 //                    records, one per (tile flush, pair): a tile-table scan
 //                    (ctg_tile_table.h)
 //   radix sort       records by key (rocPRIM radix_sort_pairs)   \ sort_and_number, shared
-//   k_overlap_heads  run heads of the sorted keys: a new (a, b), a new a   / with the morphology
+//   k_overlap_heads  run heads of the sorted keys: a new (a, b), a new a   / with the other two
 //   k_overlap_runs   run sums in u64 -> the sorted unique (a, b) table, its
-//                    counts, the distinct a (nodes) and their CSR row offsets
+//                    counts, the distinct a (nodes) and their CSR row offsets: a
+//                    run fold (ctg_run_fold.h)
 //   k_overlap_argmax per node: the b with the largest count, ties to the smallest b
-//
-// Every buffer here is call-sized and comes from the pool (DevBuf); nothing
-// touches the workspace's record or sort buffers, so a CTG_DEFER_STATS handle
-// stays valid across these calls.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 
-#include "ctg_tile_table.h"
+#include "ctg_run_fold.h"
 
 namespace ctg {
 
@@ -120,11 +117,43 @@ __global__ void k_overlap_heads(int64_t n, const uint64_t* __restrict__ key, uin
     flags[i] = (k != p ? 1ull : 0ull) | ((k >> 32) != (p >> 32) ? 1ull << 32 : 0ull);
 }
 
-// Record i of the sorted list belongs to table row scan[i].lo - 1 of node
-// scan[i].hi - 1.  A wave sums the counts of its 64 records per row (segmented
-// suffix sums by shuffles; u64: merged counts pass 2^32) and the first lane of
-// every segment adds the sum to the row -- one atomic per (wave, row), none
-// contended unless a row spans waves.  counts is zeroed before the launch.
+// The run-fold policy of the overlaps (ctg_run_fold.h): the sort's payload is
+// the count itself, summed in u64 (merged counts pass 2^32) and added to
+// counts, zeroed before the launch.  A run head writes its (a, b) pair, the
+// first row of a node (the high scan word steps) the node and its row offset.
+template <typename CountT>
+struct OverlapRuns {
+    using Value = uint64_t;
+    const uint64_t* __restrict__ key;
+    const CountT* __restrict__ cnt;
+    uint64_t *__restrict__ pairs, *__restrict__ nodes;
+    unsigned long long* __restrict__ counts;
+    int64_t* __restrict__ row_off;
+    int64_t n, E, N;
+    __device__ __forceinline__ void load(Value& v, int64_t i, bool in) const { v = in ? (uint64_t)cnt[i] : 0ull; }
+    __device__ __forceinline__ void combine(Value& v, int o, bool take) const {
+        const uint64_t vo = shfl_down_u64(v, o);
+        v += take ? vo : 0ull;
+    }
+    __device__ __forceinline__ void apply(uint32_t seg, const Value& v) const {
+        atomicAdd(&counts[seg], (unsigned long long)v);
+    }
+    __device__ __forceinline__ void name(int64_t i, uint32_t seg, bool head, uint64_t sc, uint64_t sp) const {
+        const uint64_t k = key[i];
+        if (head) {
+            pairs[2 * (int64_t)seg] = k >> 32;
+            pairs[2 * (int64_t)seg + 1] = k & 0xFFFFFFFFull;
+        }
+        if ((sc >> 32) != (sp >> 32)) {
+            const int64_t nd = (int64_t)(sc >> 32) - 1;
+            CTG_IDX(nd, N);
+            nodes[nd] = k >> 32;
+            row_off[nd] = (int64_t)seg;
+        }
+        if (i == n - 1) row_off[N] = E;
+    }
+};
+
 template <typename CountT>
 __global__ __launch_bounds__(256) void k_overlap_runs(int64_t n, const uint64_t* __restrict__ key,
                                                       const CountT* __restrict__ cnt,
@@ -132,35 +161,7 @@ __global__ __launch_bounds__(256) void k_overlap_runs(int64_t n, const uint64_t*
                                                       unsigned long long* __restrict__ counts,
                                                       uint64_t* __restrict__ nodes, int64_t* __restrict__ row_off,
                                                       int64_t E, int64_t N) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const bool in = i < n;
-    const uint64_t sc = in ? scan[i] : 0ull, sp = (in && i) ? scan[i - 1] : 0ull;
-    const uint32_t seg = in ? (uint32_t)sc - 1u : 0xFFFFFFFFu;   // (rows < 2^32 - 1: the record limit)
-    uint64_t v = in ? (uint64_t)cnt[i] : 0ull;
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint64_t vo = shfl_down_u64(v, o);
-        const uint32_t so = __shfl_down(seg, o, WAVE);
-        if (lane + o < WAVE && so == seg) v += vo;
-    }
-    const uint32_t sprev = __shfl_up(seg, 1, WAVE);
-    if (!in) return;
-    if (lane == 0 || sprev != seg) {
-        CTG_IDX(seg, E);
-        atomicAdd(&counts[seg], (unsigned long long)v);
-    }
-    const uint64_t k = key[i];
-    if ((uint32_t)sc != (uint32_t)sp) {
-        pairs[2 * (int64_t)seg] = k >> 32;
-        pairs[2 * (int64_t)seg + 1] = k & 0xFFFFFFFFull;
-    }
-    if ((sc >> 32) != (sp >> 32)) {
-        const int64_t nd = (int64_t)(sc >> 32) - 1;
-        CTG_IDX(nd, N);
-        nodes[nd] = k >> 32;
-        row_off[nd] = (int64_t)seg;
-    }
-    if (i == n - 1) row_off[N] = E;
+    run_fold(OverlapRuns<CountT>{key, cnt, pairs, nodes, counts, row_off, n, E, N}, n, scan, E);
 }
 
 // One thread per node: the first largest count of its rows -- b ascends within
@@ -244,37 +245,27 @@ template hipError_t sort_and_number<uint32_t>(Workspace&, const uint64_t*, const
 template hipError_t sort_and_number<uint64_t>(Workspace&, const uint64_t*, const uint64_t*, int64_t, unsigned,
                                               hipStream_t, uint64_t*, uint64_t*, uint64_t*, uint64_t*);
 
-// n (key, count) records -> the result's table: sort by key, number the runs,
-// sum them.  n in (0, 2^32 - 1).
+// n (key, count) records -> the result's table: equal keys add their counts
 template <typename CountT>
 static hipError_t overlap_reduce_t(Workspace& w, const uint64_t* key, const CountT* cnt, int64_t n, hipStream_t s,
                                    ctg_result* r) {
-    Ev ev{w, s};
-    DevBuf<uint64_t> ks((size_t)n * 8), scan((size_t)n * 8);
-    DevBuf<CountT> cs((size_t)n * sizeof(CountT));
-    if (!ks || !scan || !cs) return hipErrorOutOfMemory;
-    uint64_t last = 0;
-    CTG_TRY(sort_and_number(w, key, cnt, n, 64u, s, ks.p, cs.p, scan.p, &last));
-    const int64_t E = (int64_t)(uint32_t)last, N = (int64_t)(last >> 32);
-    DevBuf<uint64_t> pairs((size_t)E * 16), counts((size_t)E * 8), nodes((size_t)N * 8);
-    DevBuf<int64_t> row_off((size_t)(N + 1) * 8);
-    if (!pairs || !counts || !nodes || !row_off) return hipErrorOutOfMemory;
-    CTG_TRY(hipMemsetAsync(counts.p, 0, (size_t)E * 8, s));
-    hipLaunchKernelGGL(k_overlap_runs<CountT>, grid_for(n), dim3(256), 0, s, n, ks.p, cs.p, scan.p, pairs.p,
-                       (unsigned long long*)counts.p, nodes.p, row_off.p, E, N);
-    CTG_TRY(hipGetLastError());
-    ev.mark(5);
-    dev_free(r->edges);
-    dev_free(r->nodes);
-    dev_free(r->counts);
-    dev_free(r->row_off);
-    r->edges = pairs.release();
-    r->counts = counts.release();
-    r->nodes = nodes.release();
-    r->row_off = row_off.release();
-    r->n_edges = E;
-    r->n_nodes = N;
-    return hipSuccess;
+    return fold_records<false>(
+        w, key, cnt, n, 64u, s, [&](const uint64_t* ks, const CountT* cs, const uint64_t* scan, int64_t E, int64_t N) {
+            DevBuf<uint64_t> pairs((size_t)E * 16), counts((size_t)E * 8), nodes((size_t)N * 8);
+            DevBuf<int64_t> row_off((size_t)(N + 1) * 8);
+            if (!pairs || !counts || !nodes || !row_off) return hipErrorOutOfMemory;
+            CTG_TRY(hipMemsetAsync(counts.p, 0, (size_t)E * 8, s));
+            hipLaunchKernelGGL(k_overlap_runs<CountT>, grid_for(n), dim3(256), 0, s, n, ks, cs, scan, pairs.p,
+                               (unsigned long long*)counts.p, nodes.p, row_off.p, E, N);
+            CTG_TRY(hipGetLastError());
+            swap_in(r->edges, pairs);
+            swap_in(r->counts, counts);
+            swap_in(r->nodes, nodes);
+            swap_in(r->row_off, row_off);
+            r->n_edges = E;
+            r->n_nodes = N;
+            return hipSuccess;
+        });
 }
 
 hipError_t overlap_reduce(Workspace& w, const uint64_t* key, const uint64_t* cnt, int64_t n, hipStream_t s,
@@ -285,31 +276,14 @@ hipError_t overlap_reduce(Workspace& w, const uint64_t* key, const uint64_t* cnt
 hipError_t overlap_tables(Workspace& w, const void* A, int abits, const void* B, int bbits, const int64_t* shape,
                           const int64_t* b, const int64_t* e, int with_ignore, uint64_t ignore, hipStream_t s,
                           ctg_result* r, unsigned* overflow) {
-    Ev ev{w, s};
-    DevBuf<uint64_t> rkey;
-    DevBuf<uint32_t> rcnt;
-    int64_t m = 0;
-    CTG_TRY(scan_into_records(
-        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s,
-        [&](int64_t cap) {
-            rkey.reset();
-            rcnt.reset();
-            if (!rkey.alloc((size_t)cap * 8) || !rcnt.alloc((size_t)cap * 4)) return hipErrorOutOfMemory;
+    return scan_tables<uint32_t>(
+        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s, 1,
+        [&](uint64_t* rkey, uint32_t* rcnt, int64_t cap) {
             return launch_overlap_scan(A, abits, B, bbits, shape, b, e, with_ignore, ignore, rkey, rcnt, cap,
                                        w.counters, s);
         },
-        &m, overflow));
-    if (*overflow) return hipSuccess;
-    if (m >= 0xFFFFFFFFll) return hipErrorInvalidValue;   // (the API refuses boxes that large)
-    r->n_records = m;
-    r->n_direct = (int64_t)w.counters_host->n_direct;
-    if (m == 0) {   // every voxel ignored: the caller's empty placeholders stay
-        for (int i = 3; i <= 6; ++i) ev.mark(i);
-        return hipSuccess;
-    }
-    CTG_TRY(overlap_reduce_t<uint32_t>(w, rkey, rcnt, m, s, r));
-    ev.mark(6);
-    return hipSuccess;
+        [&](const uint64_t* rkey, const uint32_t* rcnt, int64_t m) { return overlap_reduce_t(w, rkey, rcnt, m, s, r); },
+        true, r, overflow);
 }
 
 hipError_t launch_overlap_pack(int64_t n, const uint64_t* pairs, uint64_t* key, hipStream_t s) {

@@ -9,7 +9,8 @@
 //                   (ctg_tile_table.h) whose heads carry their run's folded samples
 //   k_region_merge  float64 rows [id, count, sum, min, max] -> the same records
 //   sort_and_number   (key, record slot) sorted by key, the distinct labels numbered
-//   k_region_runs   per label: n adds in u64, the sums in f64, min / max fold
+//   k_region_runs   per label: n adds in u64, the sums in f64, min / max fold: a
+//                   run fold (ctg_run_fold.h)
 //   k_region_finish ordered min / max words -> f32; zeros for a label without voxels
 //   k_region_rows   moments -> float64 rows of either form, compact and / or dense
 //
@@ -28,13 +29,9 @@
 //   mx   u32   f2ord(maximum) (max)
 // Four no-return LDS atomics per run head, after the segmented fold of the
 // run's samples over the wave (RegionTable::fold).
-//
-// Every buffer here is call-sized and comes from the pool (DevBuf); nothing
-// touches the workspace's record or sort buffers, so a CTG_DEFER_STATS handle
-// stays valid across these calls.
 #include <hip/hip_runtime.h>
 
-#include "ctg_tile_table.h"
+#include "ctg_run_fold.h"
 
 namespace ctg {
 
@@ -211,11 +208,6 @@ __global__ void k_region_merge(int64_t n, const double* __restrict__ rows, uint6
                c ? f2ord((float)r[3]) : 0xFFFFFFFFu, c ? f2ord((float)r[4]) : 0u);
 }
 
-__global__ void k_region_iota(int64_t n, uint32_t* __restrict__ idx) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) idx[i] = (uint32_t)i;
-}
-
 // the identity of k_region_runs' folds: n 0, sum 0, min all ones, max 0
 __global__ void k_region_init(int64_t N, unsigned long long* __restrict__ cnt, double* __restrict__ sum,
                               uint32_t* __restrict__ mm) {
@@ -227,11 +219,57 @@ __global__ void k_region_init(int64_t N, unsigned long long* __restrict__ cnt, d
     mm[2 * j + 1] = 0u;
 }
 
-// Sorted position i holds record slot[i] of label number scan[i].lo - 1.  A
-// wave folds the records of its 64 positions per label (segmented suffix folds
-// by shuffles) and the first lane of every segment applies the fold to the
-// label's row -- one atomic set per (wave, label), none contended unless a
-// label spans waves.  The rows are initialised by k_region_init before the launch.
+// The run-fold policy of the region features (ctg_run_fold.h): sorted position
+// i holds the 3-word record slot[i]; n adds in u64, the sum in f64, the ordered
+// min / max words fold, onto the label's row of cnt / sum / mm (k_region_init's
+// identities before the launch).  A run head writes the label.
+struct RegionRuns {
+    struct Value {
+        uint64_t n;
+        double sum;
+        uint32_t mn, mx;
+    };
+    const uint64_t *__restrict__ key, *__restrict__ rec;
+    const uint32_t* __restrict__ slot;
+    int64_t n_rec;
+    uint64_t* __restrict__ nodes;
+    unsigned long long* __restrict__ cnt;
+    double* __restrict__ sum;
+    uint32_t* __restrict__ mm;
+    __device__ __forceinline__ void load(Value& v, int64_t i, bool in) const {
+        v = Value{0ull, 0.0, 0xFFFFFFFFu, 0u};
+        if (in) {
+            const uint32_t j = slot[i];
+            CTG_IDX(j, n_rec);
+            const uint64_t* q = rec + (int64_t)j * REGION_WORDS;
+            v.n = q[0];
+            v.sum = __longlong_as_double((long long)q[1]);
+            v.mn = (uint32_t)q[2];
+            v.mx = (uint32_t)(q[2] >> 32);
+        }
+    }
+    __device__ __forceinline__ void combine(Value& v, int o, bool take) const {
+        const uint64_t no = shfl_down_u64(v.n, o);
+        const double uo = __longlong_as_double((long long)shfl_down_u64((uint64_t)__double_as_longlong(v.sum), o));
+        const uint32_t mo = __shfl_down(v.mn, o, WAVE), xo = __shfl_down(v.mx, o, WAVE);
+        if (take) {
+            v.n += no;
+            v.sum += uo;
+            v.mn = mo < v.mn ? mo : v.mn;
+            v.mx = xo > v.mx ? xo : v.mx;
+        }
+    }
+    __device__ __forceinline__ void apply(uint32_t seg, const Value& v) const {
+        atomicAdd(&cnt[seg], (unsigned long long)v.n);
+        atomicAdd(&sum[seg], v.sum);
+        atomicMin(&mm[2 * (int64_t)seg], v.mn);
+        atomicMax(&mm[2 * (int64_t)seg + 1], v.mx);
+    }
+    __device__ __forceinline__ void name(int64_t i, uint32_t seg, bool head, uint64_t, uint64_t) const {
+        if (head) nodes[seg] = key[i];
+    }
+};
+
 __global__ __launch_bounds__(256) void k_region_runs(int64_t n, const uint64_t* __restrict__ key,
                                                      const uint32_t* __restrict__ slot,
                                                      const uint64_t* __restrict__ scan,
@@ -239,46 +277,7 @@ __global__ __launch_bounds__(256) void k_region_runs(int64_t n, const uint64_t* 
                                                      uint64_t* __restrict__ nodes,
                                                      unsigned long long* __restrict__ cnt, double* __restrict__ sum,
                                                      uint32_t* __restrict__ mm, int64_t N) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const bool in = i < n;
-    const uint64_t sc = in ? scan[i] : 0ull, sp = (in && i) ? scan[i - 1] : 0ull;
-    const uint32_t seg = in ? (uint32_t)sc - 1u : 0xFFFFFFFFu;   // (labels < 2^32 - 1: the record limit)
-    uint64_t vn = 0ull;
-    double vs = 0.0;
-    uint32_t vmn = 0xFFFFFFFFu, vmx = 0u;
-    if (in) {
-        const uint32_t j = slot[i];
-        CTG_IDX(j, n_rec);
-        const uint64_t* q = rec + (int64_t)j * REGION_WORDS;
-        vn = q[0];
-        vs = __longlong_as_double((long long)q[1]);
-        vmn = (uint32_t)q[2];
-        vmx = (uint32_t)(q[2] >> 32);
-    }
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const uint32_t so = __shfl_down(seg, o, WAVE);
-        const bool take = lane + o < WAVE && so == seg;
-        const uint64_t no = shfl_down_u64(vn, o);
-        const double uo = __longlong_as_double((long long)shfl_down_u64((uint64_t)__double_as_longlong(vs), o));
-        const uint32_t mo = __shfl_down(vmn, o, WAVE), xo = __shfl_down(vmx, o, WAVE);
-        if (take) {
-            vn += no;
-            vs += uo;
-            vmn = mo < vmn ? mo : vmn;
-            vmx = xo > vmx ? xo : vmx;
-        }
-    }
-    const uint32_t sprev = __shfl_up(seg, 1, WAVE);
-    if (!in) return;
-    if (lane == 0 || sprev != seg) {
-        CTG_IDX(seg, N);
-        atomicAdd(&cnt[seg], (unsigned long long)vn);
-        atomicAdd(&sum[seg], vs);
-        atomicMin(&mm[2 * (int64_t)seg], vmn);
-        atomicMax(&mm[2 * (int64_t)seg + 1], vmx);
-    }
-    if ((uint32_t)sc != (uint32_t)sp) nodes[seg] = key[i];
+    run_fold(RegionRuns{key, rec, slot, n_rec, nodes, cnt, sum, mm}, n, scan, N);
 }
 
 // ordered words -> the f32 they stand for, in place; a label without voxels
@@ -324,97 +323,51 @@ __global__ void k_region_rows(int64_t N, const uint64_t* __restrict__ nodes, con
         for (int c = 0; c < CTG_REGION_COLS; ++c) out[(a - lb) * CTG_REGION_COLS + c] = r[c];
 }
 
-// n (key, record) pairs -> r's nodes and region moments: sort the record slots
-// by key, number the labels, fold.  n in (0, 2^32 - 1); keys compare in their
-// low end_bit bits.
+// n (key, record) pairs -> r's nodes and region moments; keys compare in their
+// low end_bit bits
 static hipError_t region_reduce(Workspace& w, const uint64_t* key, const uint64_t* rec, int64_t n, unsigned end_bit,
                                 hipStream_t s, ctg_result* r) {
-    Ev ev{w, s};
-    DevBuf<uint64_t> ks((size_t)n * 8), scan((size_t)n * 8);
-    DevBuf<uint32_t> idx((size_t)n * 4), is((size_t)n * 4);
-    if (!ks || !scan || !idx || !is) return hipErrorOutOfMemory;
-    hipLaunchKernelGGL(k_region_iota, grid_for(n), dim3(256), 0, s, n, idx.p);
-    CTG_TRY(hipGetLastError());
-    uint64_t last = 0;
-    CTG_TRY(sort_and_number(w, key, (const uint32_t*)idx.p, n, end_bit, s, ks.p, is.p, scan.p, &last));
-    idx.reset();
-    const int64_t N = (int64_t)(uint32_t)last;
-    DevBuf<uint64_t> nodes((size_t)N * 8), cnt((size_t)N * 8);
-    DevBuf<double> sum((size_t)N * 8);
-    DevBuf<float> mm((size_t)N * 8);
-    if (!nodes || !cnt || !sum || !mm) return hipErrorOutOfMemory;
-    hipLaunchKernelGGL(k_region_init, grid_for(N), dim3(256), 0, s, N, (unsigned long long*)cnt.p, sum.p,
-                       (uint32_t*)mm.p);
-    CTG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_region_runs, grid_for(n), dim3(256), 0, s, n, ks.p, is.p, scan.p, rec, n, nodes.p,
-                       (unsigned long long*)cnt.p, sum.p, (uint32_t*)mm.p, N);
-    CTG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_region_finish, grid_for(N), dim3(256), 0, s, N, cnt.p, (uint32_t*)mm.p);
-    CTG_TRY(hipGetLastError());
-    ev.mark(5);
-    dev_free(r->nodes);
-    dev_free(r->reg_count);
-    dev_free(r->reg_sum);
-    dev_free(r->reg_minmax);
-    r->nodes = nodes.release();
-    r->reg_count = cnt.release();
-    r->reg_sum = sum.release();
-    r->reg_minmax = mm.release();
-    r->n_nodes = N;
-    return hipSuccess;
+    return fold_records<true, uint32_t>(
+        w, key, nullptr, n, end_bit, s,
+        [&](const uint64_t* ks, const uint32_t* is, const uint64_t* scan, int64_t N, int64_t) {
+            DevBuf<uint64_t> nodes((size_t)N * 8), cnt((size_t)N * 8);
+            DevBuf<double> sum((size_t)N * 8);
+            DevBuf<float> mm((size_t)N * 8);
+            if (!nodes || !cnt || !sum || !mm) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(k_region_init, grid_for(N), dim3(256), 0, s, N, (unsigned long long*)cnt.p, sum.p,
+                               (uint32_t*)mm.p);
+            CTG_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_region_runs, grid_for(n), dim3(256), 0, s, n, ks, is, scan, rec, n, nodes.p,
+                               (unsigned long long*)cnt.p, sum.p, (uint32_t*)mm.p, N);
+            CTG_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_region_finish, grid_for(N), dim3(256), 0, s, N, cnt.p, (uint32_t*)mm.p);
+            CTG_TRY(hipGetLastError());
+            swap_in(r->nodes, nodes);
+            swap_in(r->reg_count, cnt);
+            swap_in(r->reg_sum, sum);
+            swap_in(r->reg_minmax, mm);
+            r->n_nodes = N;
+            return hipSuccess;
+        });
 }
 
 hipError_t region_tables(Workspace& w, const void* A, int bits, const void* D, int kind, const int64_t* shape,
                          const int64_t* b, const int64_t* e, int has_ignore, uint64_t ignore, hipStream_t s,
                          ctg_result* r, unsigned* overflow) {
-    Ev ev{w, s};
-    DevBuf<uint64_t> rkey, rec;
-    int64_t m = 0;
-    CTG_TRY(scan_into_records(
-        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s,
-        [&](int64_t cap) {
-            rkey.reset();
-            rec.reset();
-            if (!rkey.alloc((size_t)cap * 8) || !rec.alloc((size_t)cap * REGION_WORDS * 8)) return hipErrorOutOfMemory;
+    return scan_tables<uint64_t>(
+        w, (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]), s, REGION_WORDS,
+        [&](uint64_t* rkey, uint64_t* rec, int64_t cap) {
             return launch_region_scan(A, bits, D, kind, shape, b, e, has_ignore, ignore, rkey, rec, cap, w.counters,
                                       s);
         },
-        &m, overflow));
-    if (*overflow) return hipSuccess;
-    if (m >= 0xFFFFFFFFll) return hipErrorInvalidValue;   // (the API refuses boxes that large)
-    r->n_records = m;
-    r->n_direct = (int64_t)w.counters_host->n_direct;
-    if (m == 0) {   // every voxel ignored: the caller's empty placeholders stay
-        for (int i = 3; i <= 6; ++i) ev.mark(i);
-        return hipSuccess;
-    }
-    CTG_TRY(region_reduce(w, rkey, rec, m, 32u, s, r));
-    ev.mark(6);
-    return hipSuccess;
+        [&](const uint64_t* rkey, const uint64_t* rec, int64_t m) { return region_reduce(w, rkey, rec, m, 32u, s, r); },
+        true, r, overflow);
 }
 
 hipError_t region_merge(Workspace& w, const double* rows, int64_t n, hipStream_t s, ctg_result* r, int* bad) {
-    *bad = 0;
-    Ev ev{w, s};
-    DevBuf<uint64_t> key((size_t)n * 8), rec((size_t)n * REGION_WORDS * 8);
-    if (!key || !rec) return hipErrorOutOfMemory;
-    CTG_TRY(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
-    ev.mark(0);
-    hipLaunchKernelGGL(k_region_merge, grid_for(n), dim3(256), 0, s, n, rows, key.p, rec.p,
-                       &w.counters->label_overflow);
-    CTG_TRY(hipGetLastError());
-    ev.mark(1);
-    ev.mark(2);
-    CTG_TRY(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
-    CTG_TRY(hipStreamSynchronize(s));
-    if (w.counters_host->label_overflow) {
-        *bad = 1;
-        return hipSuccess;
-    }
-    CTG_TRY(region_reduce(w, key, rec, n, 53u, s, r));
-    ev.mark(6);
-    r->n_records = n;
-    return hipSuccess;
+    return merge_rows(
+        w, rows, n, REGION_WORDS, k_region_merge,
+        [&](const uint64_t* key, const uint64_t* rec) { return region_reduce(w, key, rec, n, 53u, s, r); }, s, r, bad);
 }
 
 hipError_t launch_region_rows(const ctg_result* r, uint64_t lb, uint64_t le, int form, double norm, double* out,
