@@ -1,9 +1,10 @@
 // C ABI of libctg.so (include/ctg.h): the error state, the result handles and
-// the entry points that are neither the face scan (ctg_api_scan.hip) nor a
-// label table (ctg_api_tables.hip) -- device and profiling, unique / merge /
-// map, the multi-GPU exchange, the synthetic volumes -- and the definitions
-// behind ctg_api.h, the sorting ones included: of the three API files only
-// this one instantiates rocPRIM.  The allocator and the workspace live in
+// the entry points that are neither the face scan (ctg_api_scan.hip), a label
+// table (ctg_api_tables.hip), the thresholded components (ctg_api_cc.hip) nor
+// the multi-GPU exchange (ctg_api_mgpu.hip) -- device and profiling, unique /
+// merge / map, the synthetic volumes -- and the definitions behind ctg_api.h,
+// the sorting ones included: of the API files only this one instantiates
+// rocPRIM.  The allocator and the workspace live in
 // ctg_workspace.hip (ctg_pool.h, ctg_buffers.h), the record back half in
 // ctg_records.hip, the host decisions in ctg_plan.h.
 #include <hip/hip_runtime.h>
@@ -148,122 +149,6 @@ extern "C" {
 int ctg_version(void) { return 1; }
 
 const char* ctg_last_error(void) { return g_err.c_str(); }
-
-int ctg_mgpu_slab(int64_t Z, int world_size, int rank, const int64_t* offsets, int n_channels, int64_t* out) {
-    if (Z <= 0 || world_size <= 0 || rank < 0 || rank >= world_size || !out || n_channels < 0 ||
-        (n_channels > 0 && !offsets)) {
-        set_error("ctg_mgpu_slab: invalid arguments");
-        return CTG_ERR_ARG;
-    }
-    if (world_size > Z) {
-        set_error("ctg_mgpu_slab: more ranks than z planes");
-        return CTG_ERR_ARG;
-    }
-    int64_t down = 1, up = 0;   // planes a face / partner reaches below and above a voxel
-    for (int c = 0; c < n_channels; ++c) {
-        down = std::max<int64_t>(down, -offsets[3 * c]);
-        up = std::max<int64_t>(up, offsets[3 * c]);
-    }
-    if (up > 0 && world_size > 1) {
-        set_error("ctg_mgpu_slab: positive z offsets need an upper halo, which the z-slab layout does not have");
-        return CTG_ERR_UNSUPPORTED;
-    }
-    const int64_t z0 = Z * rank / world_size, z1 = Z * (rank + 1) / world_size;
-    out[0] = z0 - std::min(down, z0);
-    out[1] = z0;
-    out[2] = z1;
-    return CTG_OK;
-}
-
-static bool mgpu_args(const ctg_result* r, int world, const char* who) {
-    if (!r || world <= 0 || world > CTG_MGPU_MAX_WORLD) {
-        set_error(std::string(who) + ": bad arguments (world size must be 1.." +
-                  std::to_string(CTG_MGPU_MAX_WORLD) + ")");
-        return false;
-    }
-    return true;
-}
-
-int ctg_mgpu_sample(const ctg_result* local, int64_t* meta, void* stream) {
-    DevLock dev_lock;
-    if (!mgpu_args(local, 1, "ctg_mgpu_sample") || !meta) return CTG_ERR_ARG;
-    CTG_CHECK(mgpu_sample(local->edges, local->n_edges, meta, (hipStream_t)stream));
-    return CTG_OK;
-}
-
-int ctg_mgpu_split(const ctg_result* local, const int64_t* meta_all, int world_size, int64_t* counts, void* stream) {
-    ApiCall c;
-    if (!mgpu_args(local, world_size, "ctg_mgpu_split") || !meta_all || !counts) return CTG_ERR_ARG;
-    if (int rc = c.begin(stream)) return rc;
-    Workspace& w = c.w();
-    // one splitter buffer per device: a split on another stream must not
-    // overwrite it while an earlier split's k_mgpu_bounds still reads it
-    if (w.mgpu_spl_ev) CTG_CHECK(hipStreamWaitEvent((hipStream_t)stream, w.mgpu_spl_ev, 0));
-    else CTG_CHECK(hipEventCreateWithFlags(&w.mgpu_spl_ev, hipEventDisableTiming));
-    CTG_CHECK(mgpu_split(local->edges, local->n_edges, local->nodes, local->n_nodes, meta_all, world_size,
-                         w.mgpu_spl, counts, (hipStream_t)stream));
-    CTG_CHECK(hipEventRecord(w.mgpu_spl_ev, (hipStream_t)stream));
-    return CTG_OK;
-}
-
-int ctg_mgpu_pack(const ctg_result* local, const int64_t* counts_all, int world_size, int rank, int64_t* send,
-                  void* stream) {
-    DevLock dev_lock;
-    if (!mgpu_args(local, world_size, "ctg_mgpu_pack") || !counts_all || rank < 0 || rank >= world_size)
-        return CTG_ERR_ARG;
-    const ExchangeCounts n = exchange_counts(counts_all, world_size, rank, CTG_MGPU_ROW_WORDS, false);
-    const int64_t words = n.words;
-    if (n.rows != local->n_edges || n.nodes != local->n_nodes) {
-        set_error("ctg_mgpu_pack: counts do not cover this rank's table");
-        return CTG_ERR_ARG;
-    }
-    if (words > 0 && (!send || (!(local->stats && local->stat_sums) && !local->defer.on))) {
-        set_error("ctg_mgpu_pack: rows to send need a CTG_KEEP_STATS table and a send buffer");
-        return CTG_ERR_ARG;
-    }
-    if (words > 0 && local->defer.on && local->defer.gen != ws(local->device).gen) {
-        set_error("ctg_mgpu_pack: the CTG_DEFER_STATS table's records were overwritten by a later call");
-        return CTG_ERR_STALE;
-    }
-    CTG_CHECK(mgpu_pack(local, counts_all, world_size, rank, send, (hipStream_t)stream));
-    return CTG_OK;
-}
-
-int ctg_mgpu_merge(ctg_result* local, const int64_t* recv, const int64_t* counts_all, int world_size, int rank,
-                   double hist_lo, double hist_hi, void* stream, ctg_result** out) {
-    ApiCall c;
-    if (!mgpu_args(local, world_size, "ctg_mgpu_merge") || !counts_all || !out || rank < 0 || rank >= world_size ||
-        !(hist_hi > hist_lo))
-        return CTG_ERR_ARG;
-    *out = nullptr;
-    if (!local->owned.empty()) {   // a shard's arrays are interior pointers of its owned blocks
-        set_error("ctg_mgpu_merge: the local table is itself a merge shard; pass the rank's local call");
-        return CTG_ERR_ARG;
-    }
-    const ExchangeCounts n = exchange_counts(counts_all, world_size, rank, CTG_MGPU_ROW_WORDS, true);
-    const int64_t recv_words = n.words;
-    if (n.rows != local->n_edges || n.nodes != local->n_nodes) {
-        set_error("ctg_mgpu_merge: counts do not cover this rank's table");
-        return CTG_ERR_ARG;
-    }
-    if (recv_words > 0 && !recv) {
-        set_error("ctg_mgpu_merge: null receive buffer");
-        return CTG_ERR_ARG;
-    }
-    if (recv_words > 0 && local->defer.on && local->defer.gen != ws(local->device).gen) {
-        set_error("ctg_mgpu_merge: the CTG_DEFER_STATS table's records were overwritten by a later call");
-        return CTG_ERR_STALE;
-    }
-    int rc = c.begin(stream, new_result);
-    if (rc) return rc;
-    int lib_rc = CTG_OK;
-    const hipError_t e = mgpu_merge(local, recv, counts_all, world_size, rank, hist_lo, hist_hi, c.s, c.r.get(), &lib_rc);
-    if (lib_rc != CTG_OK) return lib_rc;   // the message is set already
-    if ((rc = hip_status(e, "ctg_mgpu_merge")) != CTG_OK) return rc;
-    local->n_edges = 0;
-    local->n_nodes = 0;
-    return c.end(false, out);
-}
 
 int ctg_device_count(int* count) {
     CTG_CHECK(hipGetDeviceCount(count));

@@ -693,12 +693,55 @@ hipError_t launch_uf_write(const uint32_t* parent, const uint32_t* rank, const u
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,
                       int world, uint64_t* spl, int64_t* counts, hipStream_t s);
-hipError_t mgpu_pack(const ctg_result* r, const int64_t* counts_all, int world, int rank, int64_t* send,
-                     hipStream_t s);
-// *lib_rc: a library status (with its message set) when a nested C-ABI call
-// failed, or CTG_ERR_UNSUPPORTED for a shard past the u32 row indices
-hipError_t mgpu_merge(ctg_result* local, const int64_t* recv, const int64_t* counts_all, int world, int rank,
-                      double hist_lo, double hist_hi, hipStream_t s, ctg_result* out, int* lib_rc);
+// the rows and node ids of every send segment (ctg_plan.h: exchange_plan) into send
+hipError_t mgpu_pack(const ctg_result* r, const ExchangeSegs& S, int64_t* send, hipStream_t s);
+
+// What the merge kernels read and write: the own range of the local table,
+// the received rows, and one entry per distinct received key.
+struct MergeIO {
+    // own range of the local table (rows [0, n_own) after offsetting)
+    const uint64_t* own_edges;
+    const double* own_feats;
+    const uint32_t* own_wide;
+    const double2* own_sums;
+    DeferredStats defer;  // on: own rows' statistics from the records (own row i = run own_row0 + i)
+    int64_t own_row0;
+    int64_t n_own;
+    // received rows, sorted order and runs
+    const uint64_t* recv;
+    const uint32_t* order;
+    const uint64_t* skeys;
+    const uint32_t* run0;
+    const uint32_t* nK;
+    // per unique received key k
+    uint64_t* mkeys;      // (K,2)
+    double* mfeats;       // (K,10)
+    uint32_t* mkeep;      // keep (ADJ proved, or every key for boundary maps)
+    uint32_t* mnew;       // key absent from the own range
+    int64_t* mins;        // own rows with a smaller key
+    uint32_t* touched;    // (n_own) 1 + k of the received key that matches own row i, 0 none
+    int partial_adj;      // keys need the ADJ bit (affinity partials)
+    double scale, offset;
+};
+// The merge's launches over the receive segments S, in the order of the steps
+// of ctg_mgpu_merge (ctg_api_mgpu.hip).  own[0, n_own) and the node ids of
+// every received segment -> out:
+hipError_t mgpu_node_list(const ExchangeSegs& S, const int64_t* recv, const uint64_t* own, int64_t n_own,
+                          uint64_t* out, hipStream_t s);
+// the received rows in key order: order[pos] = received row, skeys[pos] = its (u,v)
+hipError_t mgpu_order(const ExchangeSegs& S, const int64_t* recv, uint32_t* order, uint64_t* skeys, hipStream_t s);
+// runs of equal keys among the M sorted keys: run0[k] = first position of run
+// k, run0[K] = M, K in *nK (head, rid: M words of scratch each)
+hipError_t mgpu_runs(Workspace& w, int64_t M, const uint64_t* skeys, uint32_t* head, uint32_t* rid, uint32_t* run0,
+                     uint32_t* nK, hipStream_t s);
+// every run combined with the own row of its key; nrank = exclusive scan of io.mnew
+hipError_t mgpu_combine(Workspace& w, const ExchangeSegs& S, const MergeIO& io, uint32_t* nrank, hipStream_t s);
+// the keep flag of every merged-order slot; fpos = its exclusive scan
+hipError_t mgpu_slots(Workspace& w, const MergeIO& io, const uint32_t* nrank, int64_t n_slots, uint32_t* keep,
+                      uint32_t* fpos, hipStream_t s);
+// the kept rows to out_e / out_f, their number to *n_out
+hipError_t mgpu_scatter(const MergeIO& io, const uint32_t* nrank, const uint32_t* keep, const uint32_t* fpos,
+                        int64_t n_slots, uint64_t* out_e, double* out_f, uint32_t* n_out, hipStream_t s);
 }  // namespace ctg
 
 // in functions that return hipError_t: pass a failure up

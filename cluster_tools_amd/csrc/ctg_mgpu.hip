@@ -48,20 +48,15 @@ __global__ void k_mgpu_sample(const uint64_t* __restrict__ edges, int64_t E, int
     if (i == MS) meta[MS] = E;
 }
 
-__device__ __forceinline__ int lower_i64(const int64_t* a, int n, int64_t v) {
-    int lo = 0, hi = n;
+// The one binary search: the first i of [0, n) that does not come before the
+// sought position -- before(i) holds on a prefix of the range.  A lower bound
+// asks "element i < x", an upper bound "element i <= x".
+template <class I, class Before>
+__device__ __forceinline__ I first_not(I n, Before before) {
+    I lo = 0, hi = n;
     while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int upper_i64(const int64_t* a, int n, int64_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1;
+        const I mid = (lo + hi) >> 1;
+        if (before(mid)) lo = mid + 1;
         else hi = mid;
     }
     return lo;
@@ -88,7 +83,9 @@ __global__ void k_mgpu_splitters(const int64_t* __restrict__ meta_all, int world
         const uint64_t cq = (uint64_t)row[MS];
         total += cq;
         if (cq == 0) continue;
-        const int c = q < r ? upper_i64(row, MS, v) : q > r ? lower_i64(row, MS, v) : j + 1;
+        const int c = q < r   ? first_not(MS, [&](int i) { return row[i] <= v; })
+                      : q > r ? first_not(MS, [&](int i) { return row[i] < v; })
+                              : j + 1;
         cw += cq * (uint64_t)c;
     }
     const uint64_t lo = (cw - cnt_r) * (uint64_t)world, hi = cw * (uint64_t)world;
@@ -100,13 +97,7 @@ __global__ void k_mgpu_splitters(const int64_t* __restrict__ meta_all, int world
 
 // first row of a sorted (u,v) table (stride words per row) whose u >= x
 __device__ __forceinline__ int64_t lower_u(const uint64_t* col, int stride, int64_t n, uint64_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (col[mid * stride] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return first_not(n, [&](int64_t i) { return col[i * stride] < x; });
 }
 
 // rows / node ids of this rank that fall in every rank's u range
@@ -124,27 +115,20 @@ __global__ void k_mgpu_bounds(const uint64_t* __restrict__ edges, int64_t E, con
 }
 
 // ---------------------------------------------------------------------------
-// pack: one segment per destination, rows then node ids
+// pack: one segment per destination, rows then node ids (the segment tables,
+// ExchangeSegs, and their lookup seg_of are ctg_plan.h's: exchange_plan)
 // ---------------------------------------------------------------------------
-struct Segs {   // destination segments of the send buffer (host-computed)
-    int64_t e_start[CTG_MGPU_MAX_WORLD], e_cnt[CTG_MGPU_MAX_WORLD];
-    int64_t n_start[CTG_MGPU_MAX_WORLD], n_cnt[CTG_MGPU_MAX_WORLD];
-    int64_t w_off[CTG_MGPU_MAX_WORLD + 1];   // word offset of segment i
-    int n;
-};
-
 // a row = (u, v, S1 bits, S2 bits, the 48-word wide record as 24 u64)
-__global__ void k_mgpu_pack(Segs S, const uint64_t* __restrict__ edges, const double2* __restrict__ sums,
+__global__ void k_mgpu_pack(ExchangeSegs S, const uint64_t* __restrict__ edges, const double2* __restrict__ sums,
                             const uint64_t* __restrict__ wide64, const uint64_t* __restrict__ nodes,
                             uint64_t* __restrict__ out) {
-    const int64_t total = S.w_off[S.n];
+    const int64_t total = S.words();
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {
-        int s = 0;
-        while (s + 1 < S.n && S.w_off[s + 1] <= i) ++s;
-        const int64_t off = i - S.w_off[s];
+        const int s = seg_of(S.w_off, S.n, i);
+        const int64_t off = i - S.w_off[s], row_words = (S.row0[s + 1] - S.row0[s]) * ROW;
         uint64_t val;
-        if (off < S.e_cnt[s] * ROW) {
+        if (off < row_words) {
             const int64_t r = S.e_start[s] + off / ROW;
             const int w = (int)(off % ROW);
             if (w < 2) val = edges[2 * r + w];
@@ -156,7 +140,7 @@ __global__ void k_mgpu_pack(Segs S, const uint64_t* __restrict__ edges, const do
                 val = wide64[r * (WREC_WORDS / 2) + (w - 4)];
             }
         } else {
-            val = nodes[S.n_start[s] + (off - S.e_cnt[s] * ROW)];
+            val = nodes[S.n_start[s] + (off - row_words)];
         }
         out[i] = val;
     }
@@ -165,13 +149,12 @@ __global__ void k_mgpu_pack(Segs S, const uint64_t* __restrict__ edges, const do
 // CTG_DEFER_STATS: one thread per row to send -- its statistics rebuilt from
 // its records (words 2..27 of the row; k_mgpu_pack writes the key words).
 // Boundary maps only: every key is an edge (the reduce's need_adj 0 sets ADJ).
-__global__ __launch_bounds__(256) void k_mgpu_pack_deferred(Segs S, DeferredStats D, uint64_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_mgpu_pack_deferred(ExchangeSegs S, DeferredStats D,
+                                                            uint64_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int s = 0;
-    int64_t before = 0;
-    while (s < S.n && i >= before + S.e_cnt[s]) before += S.e_cnt[s++];
-    if (s >= S.n) return;
-    const int64_t a = i - before, r = S.e_start[s] + a;
+    if (i >= S.rows()) return;
+    const int s = seg_of(S.row0, S.n, i);
+    const int64_t a = i - S.row0[s], r = S.e_start[s] + a;
     uint32_t h[NSLOTS];
 #pragma unroll
     for (int j = 0; j < NSLOTS; ++j) h[j] = 0;
@@ -194,40 +177,27 @@ __device__ __forceinline__ bool key_lt(uint64_t au, uint64_t av, uint64_t bu, ui
     return au < bu || (au == bu && av < bv);
 }
 
-struct RecvSegs {   // received segments (sources in rank order, own skipped)
-    int64_t row0[CTG_MGPU_MAX_WORLD + 1];   // first global received row of segment i
-    int64_t w_off[CTG_MGPU_MAX_WORLD];      // word offset of segment i in the receive buffer
-    int n;
-};
-
-__device__ __forceinline__ const uint64_t* recv_row(const RecvSegs& S, const uint64_t* recv, int s, int64_t a) {
+__device__ __forceinline__ const uint64_t* recv_row(const ExchangeSegs& S, const uint64_t* recv, int s, int64_t a) {
     return recv + S.w_off[s] + a * ROW;
 }
 
 // rows of segment q with key < (u,v) (lower) or <= (upper)
-__device__ __forceinline__ int64_t seg_rank(const RecvSegs& S, const uint64_t* recv, int q, uint64_t u, uint64_t v,
-                                            bool upper) {
-    int64_t lo = 0, hi = S.row0[q + 1] - S.row0[q];
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const uint64_t* p = recv_row(S, recv, q, mid);
-        const bool before = upper ? !key_lt(u, v, p[0], p[1]) : key_lt(p[0], p[1], u, v);
-        if (before) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+__device__ __forceinline__ int64_t seg_rank(const ExchangeSegs& S, const uint64_t* recv, int q, uint64_t u,
+                                            uint64_t v, bool upper) {
+    return first_not(S.row0[q + 1] - S.row0[q], [&](int64_t i) {
+        const uint64_t* p = recv_row(S, recv, q, i);
+        return upper ? !key_lt(u, v, p[0], p[1]) : key_lt(p[0], p[1], u, v);
+    });
 }
 
 // Received rows in one sorted order without a sort: every source's segment is
 // sorted, so row a of segment s lands at a + (rows of the other segments that
 // precede it; ties go to the lower source).  order[pos] = global row index.
-__global__ void k_mgpu_order(RecvSegs S, const uint64_t* __restrict__ recv, uint32_t* __restrict__ order,
+__global__ void k_mgpu_order(ExchangeSegs S, const uint64_t* __restrict__ recv, uint32_t* __restrict__ order,
                              uint64_t* __restrict__ skeys) {
-    const int64_t M = S.row0[S.n];
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= M) return;
-    int s = 0;
-    while (s + 1 < S.n && S.row0[s + 1] <= j) ++s;
+    if (j >= S.rows()) return;
+    const int s = seg_of(S.row0, S.n, j);
     const int64_t a = j - S.row0[s];
     const uint64_t* p = recv_row(S, recv, s, a);
     const uint64_t u = p[0], v = p[1];
@@ -261,50 +231,18 @@ __global__ void k_mgpu_runs(int64_t M, const uint32_t* __restrict__ head, const 
 
 // position of (u,v) in a sorted (u,v) table of n rows: lower bound
 __device__ __forceinline__ int64_t lower_uv(const uint64_t* t, int64_t n, uint64_t u, uint64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (key_lt(t[2 * mid], t[2 * mid + 1], u, v)) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
+    return first_not(n, [&](int64_t i) { return key_lt(t[2 * i], t[2 * i + 1], u, v); });
 }
-
-struct MergeIO {
-    // own range of the local table (rows [0, n_own) after offsetting)
-    const uint64_t* own_edges;
-    const double* own_feats;
-    const uint32_t* own_wide;
-    const double2* own_sums;
-    DeferredStats defer;  // on: own rows' statistics from the records (own row i = run own_row0 + i)
-    int64_t own_row0;
-    int64_t n_own;
-    // received rows, sorted order and runs
-    const uint64_t* recv;
-    const uint32_t* order;
-    const uint64_t* skeys;
-    const uint32_t* run0;
-    const uint32_t* nK;
-    // per unique received key k
-    uint64_t* mkeys;      // (K,2)
-    double* mfeats;       // (K,10)
-    uint32_t* mkeep;      // keep (ADJ proved, or every key for boundary maps)
-    uint32_t* mnew;       // key absent from the own range
-    int64_t* mins;        // own rows with a smaller key
-    uint32_t* touched;    // (n_own) 1 + k of the received key that matches own row i, 0 none
-    int partial_adj;      // keys need the ADJ bit (affinity partials)
-    double scale, offset;
-};
 
 // One thread per unique received key: its own-range match (binary search),
 // the combined statistics of the own row and every received row of the key,
 // and the re-finalised feature row.
-__global__ __launch_bounds__(256) void k_mgpu_combine(RecvSegs S, MergeIO io) {
+__global__ __launch_bounds__(256) void k_mgpu_combine(ExchangeSegs S, MergeIO io) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= (int64_t)*io.nK) return;
-    CTG_IDX(*io.nK, S.row0[S.n] + 1);   // unique received keys within the received rows
+    CTG_IDX(*io.nK, S.rows() + 1);   // unique received keys within the received rows
     const uint32_t p0 = io.run0[k], p1 = io.run0[k + 1];
-    CTG_IDX(p1, S.row0[S.n] + 1);
+    CTG_IDX(p1, S.rows() + 1);
     CTG_IDX(p0, p1);
     const uint64_t u = io.skeys[2 * (int64_t)p0], v = io.skeys[2 * (int64_t)p0 + 1];
     const int64_t ins = lower_uv(io.own_edges, io.n_own, u, v);
@@ -332,9 +270,8 @@ __global__ __launch_bounds__(256) void k_mgpu_combine(RecvSegs S, MergeIO io) {
     }
     for (uint32_t p = p0; p < p1; ++p) {
         const uint32_t j = io.order[p];
-        CTG_IDX(j, S.row0[S.n]);
-        int s = 0;
-        while (s + 1 < S.n && S.row0[s + 1] <= (int64_t)j) ++s;
+        CTG_IDX(j, S.rows());
+        const int s = seg_of(S.row0, S.n, (int64_t)j);
         const uint64_t* r = recv_row(S, io.recv, s, (int64_t)j - S.row0[s]);
 #pragma unroll
         for (int t = 0; t < WREC_WORDS / 2; ++t) {
@@ -353,29 +290,39 @@ __global__ __launch_bounds__(256) void k_mgpu_combine(RecvSegs S, MergeIO io) {
     finalize_row(h, cnt, mn, mx, mo, io.scale, io.offset, io.mfeats + k * N_FEATURES);
 }
 
-// merged-order slot of every own row and every new received key, and its keep
-// flag: own row i -> i + (new keys below it); new key k -> (own rows below it)
-// + (new keys before it).  nrank = exclusive scan of mnew.
+// received keys absent from the own range (nrank = exclusive scan of mnew)
+__device__ __forceinline__ uint32_t new_keys(const MergeIO& io, const uint32_t* nrank, int64_t K) {
+    return K ? nrank[K - 1] + io.mnew[K - 1] : 0u;
+}
+
+// The merged-order slot of entry i of (own rows, then received keys): own row
+// i -> i + (new keys below it); new key k = i - n_own -> (own rows below it) +
+// (new keys before it).  Received keys that are not new have no slot.
+__device__ __forceinline__ int64_t merged_slot(const MergeIO& io, const uint32_t* nrank, int64_t K, uint32_t n_new,
+                                               int64_t i) {
+    if (i >= io.n_own) return io.mins[i - io.n_own] + nrank[i - io.n_own];
+    const int64_t b = K ? lower_uv(io.mkeys, K, io.own_edges[2 * i], io.own_edges[2 * i + 1]) : 0;
+    return i + (b < K ? (int64_t)nrank[b] : (int64_t)n_new);
+}
+
+// the slot of every own row and every new received key, and its keep flag
 __global__ void k_mgpu_slots(MergeIO io, const uint32_t* __restrict__ nrank, uint32_t* __restrict__ keep,
                              int64_t n_slots) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t K = (int64_t)*io.nK;
-    const uint32_t n_new = K ? nrank[K - 1] + io.mnew[K - 1] : 0u;
+    const uint32_t n_new = new_keys(io, nrank, K);
     // slots past the merged table (the buffer is sized by the bound n_own + M)
     if (i >= io.n_own + (int64_t)n_new && i < n_slots) keep[i] = 0u;
     if (i == 0) CTG_IDX(io.n_own + (int64_t)n_new, n_slots + 1);
     if (i < io.n_own) {
-        const uint64_t u = io.own_edges[2 * i], v = io.own_edges[2 * i + 1];
-        const int64_t b = K ? lower_uv(io.mkeys, K, u, v) : 0;
-        const int64_t slot = i + (b < K ? (int64_t)nrank[b] : (int64_t)n_new);
         const uint32_t t = io.touched[i];
         const uint32_t kp = t ? io.mkeep[t - 1]
                               : ((!io.partial_adj || (io.own_wide[i * WREC_WORDS + 42] & ADJ_FLAG)) ? 1u : 0u);
-        keep[slot] = kp;
-    } else if (i < io.n_own + K) {
-        const int64_t k = i - io.n_own;
-        if (io.mnew[k]) CTG_IDX(io.mins[k] + nrank[k], n_slots);
-        if (io.mnew[k]) keep[io.mins[k] + nrank[k]] = io.mkeep[k];
+        keep[merged_slot(io, nrank, K, n_new, i)] = kp;
+    } else if (i < io.n_own + K && io.mnew[i - io.n_own]) {
+        const int64_t slot = merged_slot(io, nrank, K, n_new, i);
+        CTG_IDX(slot, n_slots);
+        keep[slot] = io.mkeep[i - io.n_own];
     }
 }
 
@@ -386,26 +333,21 @@ __global__ void k_mgpu_scatter(MergeIO io, const uint32_t* __restrict__ nrank, c
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t K = (int64_t)*io.nK;
     if (i == 0) *n_out = n_slots ? fpos[n_slots - 1] + keep[n_slots - 1] : 0u;
-    const uint32_t n_new = K ? nrank[K - 1] + io.mnew[K - 1] : 0u;
     const uint64_t* ke;
     const double* kf;
-    int64_t slot;
     if (i < io.n_own) {
-        const uint64_t u = io.own_edges[2 * i], v = io.own_edges[2 * i + 1];
-        const int64_t b = K ? lower_uv(io.mkeys, K, u, v) : 0;
-        slot = i + (b < K ? (int64_t)nrank[b] : (int64_t)n_new);
         const uint32_t t = io.touched[i];
         ke = io.own_edges + 2 * i;
         kf = t ? io.mfeats + (int64_t)(t - 1) * N_FEATURES : io.own_feats + i * N_FEATURES;
     } else if (i < io.n_own + K) {
         const int64_t k = i - io.n_own;
         if (!io.mnew[k]) return;
-        slot = io.mins[k] + nrank[k];
         ke = io.mkeys + 2 * k;
         kf = io.mfeats + k * N_FEATURES;
     } else {
         return;
     }
+    const int64_t slot = merged_slot(io, nrank, K, new_keys(io, nrank, K), i);
     CTG_IDX(slot, n_slots);
     if (!keep[slot]) return;
     const int64_t f = fpos[slot];
@@ -418,25 +360,36 @@ __global__ void k_mgpu_scatter(MergeIO io, const uint32_t* __restrict__ nrank, c
 }
 
 // node ids of the own range and every received segment -> one list
-__global__ void k_mgpu_node_list(RecvSegs S, const uint64_t* __restrict__ recv, const int64_t* __restrict__ rn,
-                                 const int64_t* __restrict__ rn_off, const uint64_t* __restrict__ own, int64_t n_own,
-                                 uint64_t* __restrict__ out, int64_t total) {
+__global__ void k_mgpu_node_list(ExchangeSegs S, const uint64_t* __restrict__ recv, const uint64_t* __restrict__ own,
+                                 int64_t n_own, uint64_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
+    if (i >= n_own + S.nodes()) return;
     if (i < n_own) {
         out[i] = own[i];
         return;
     }
-    int s = 0;
-    while (s + 1 < S.n && rn_off[s + 1] <= i - n_own) ++s;
-    const int64_t a = i - n_own - rn_off[s];
+    const int s = seg_of(S.node0, S.n, i - n_own);
+    const int64_t a = i - n_own - S.node0[s];
     const int64_t rows = S.row0[s + 1] - S.row0[s];
     out[i] = recv[S.w_off[s] + rows * ROW + a];
 }
 
+
 // ---------------------------------------------------------------------------
-// launchers (called from ctg_api.hip; declared in ctg_internal.h)
+// launchers (called from ctg_api_mgpu.hip; declared in ctg_internal.h)
 // ---------------------------------------------------------------------------
+static unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
+
+static const uint64_t* u64(const int64_t* p) { return reinterpret_cast<const uint64_t*>(p); }
+
+// exclusive prefix sum of n u32 (rocPRIM, the workspace's temp buffer)
+static hipError_t excl_scan(GrowBuf& temp, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    return with_temp(temp, [&](void* t, size_t& tb) {
+        return rocprim::exclusive_scan(t, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
+    });
+}
+
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s) {
     hipLaunchKernelGGL(k_mgpu_sample, dim3((MS + 1 + 255) / 256), dim3(256), 0, s, edges, E, meta);
     return hipGetLastError();
@@ -454,218 +407,58 @@ hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, i
     return hipGetLastError();
 }
 
-hipError_t mgpu_pack(const ctg_result* r, const int64_t* counts_all, int world, int rank, int64_t* send,
-                     hipStream_t s) {
-    Segs S;
-    std::memset(&S, 0, sizeof(S));
-    const int64_t* mine = counts_all + (int64_t)rank * world * 2;   // [dst][rows, nodes] of this rank
-    int64_t e0 = 0, n0 = 0, w = 0;
-    for (int d = 0; d < world; ++d) {
-        const int64_t ec = mine[2 * d], nc = mine[2 * d + 1];
-        if (d != rank && (ec || nc)) {
-            S.e_start[S.n] = e0;
-            S.e_cnt[S.n] = ec;
-            S.n_start[S.n] = n0;
-            S.n_cnt[S.n] = nc;
-            S.w_off[S.n] = w;
-            w += ec * ROW + nc;
-            ++S.n;
-        }
-        e0 += ec;
-        n0 += nc;
-    }
-    S.w_off[S.n] = w;
-    if (w == 0) return hipSuccess;
+hipError_t mgpu_pack(const ctg_result* r, const ExchangeSegs& S, int64_t* send, hipStream_t s) {
+    if (S.words() == 0) return hipSuccess;
     const bool defer = r->defer.on && !r->stats;
-    const int64_t blocks = std::min<int64_t>((w + 255) / 256, 8192);
+    const int64_t blocks = std::min<int64_t>((S.words() + 255) / 256, 8192);
     hipLaunchKernelGGL(k_mgpu_pack, dim3((unsigned)blocks), dim3(256), 0, s, S, r->edges, r->stat_sums,
                        defer ? nullptr : reinterpret_cast<const uint64_t*>(r->stats), r->nodes,
                        reinterpret_cast<uint64_t*>(send));
-    if (defer) {
-        int64_t rows = 0;
-        for (int i = 0; i < S.n; ++i) rows += S.e_cnt[i];
-        if (rows > 0)
-            hipLaunchKernelGGL(k_mgpu_pack_deferred, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, S,
-                               r->defer, reinterpret_cast<uint64_t*>(send));
-    }
+    if (defer && S.rows() > 0)
+        hipLaunchKernelGGL(k_mgpu_pack_deferred, dim3((unsigned)((S.rows() + 255) / 256)), dim3(256), 0, s, S,
+                           r->defer, reinterpret_cast<uint64_t*>(send));
     return hipGetLastError();
 }
 
-
-// exclusive prefix sum of n u32 (rocPRIM, the workspace's temp buffer)
-static hipError_t excl_scan(GrowBuf& temp, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    return with_temp(temp, [&](void* t, size_t& tb) {
-        return rocprim::exclusive_scan(t, tb, in, out, 0u, (size_t)n, rocprim::plus<uint32_t>(), s);
-    });
+hipError_t mgpu_node_list(const ExchangeSegs& S, const int64_t* recv, const uint64_t* own, int64_t n_own,
+                          uint64_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_mgpu_node_list, dim3(grid_of(n_own + S.nodes())), dim3(256), 0, s, S, u64(recv), own, n_own,
+                       out);
+    return hipGetLastError();
 }
 
-static unsigned grid_of(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
+hipError_t mgpu_order(const ExchangeSegs& S, const int64_t* recv, uint32_t* order, uint64_t* skeys, hipStream_t s) {
+    hipLaunchKernelGGL(k_mgpu_order, dim3(grid_of(S.rows())), dim3(256), 0, s, S, u64(recv), order, skeys);
+    return hipGetLastError();
+}
 
-// ctg_mgpu_merge (include/ctg.h): this rank's shard of the global table.
-hipError_t mgpu_merge(ctg_result* L, const int64_t* recv, const int64_t* counts_all, int world, int rank,
-                      double hist_lo, double hist_hi, hipStream_t s, ctg_result* r, int* lib_rc) {
-    Workspace& w = ws(r->device);
-    *lib_rc = CTG_OK;
-    // own range: rows / node ids this rank kept for itself
-    const int64_t* mine = counts_all + (int64_t)rank * world * 2;
-    int64_t e_lo = 0, n_lo = 0;
-    for (int d = 0; d < rank; ++d) {
-        e_lo += mine[2 * d];
-        n_lo += mine[2 * d + 1];
-    }
-    const int64_t e_cnt = mine[2 * rank], n_cnt = mine[2 * rank + 1];
-    // received segments, sources in rank order
-    RecvSegs S;
-    std::memset(&S, 0, sizeof(S));
-    int64_t rn[CTG_MGPU_MAX_WORLD], rn_off[CTG_MGPU_MAX_WORLD + 1];
-    int64_t M = 0, NM = 0, words = 0;
-    for (int q = 0; q < world; ++q) {
-        const int64_t* c = counts_all + ((int64_t)q * world + rank) * 2;
-        if (q == rank || (c[0] == 0 && c[1] == 0)) continue;
-        S.row0[S.n] = M;
-        S.w_off[S.n] = words;
-        rn[S.n] = c[1];
-        rn_off[S.n] = NM;
-        M += c[0];
-        NM += c[1];
-        words += c[0] * ROW + c[1];
-        ++S.n;
-    }
-    S.row0[S.n] = M;
-    rn_off[S.n] = NM;
-    const uint64_t* rv = reinterpret_cast<const uint64_t*>(recv);
-    std::vector<DevBuf<void>> tmp;   // back to the pool when the merge returns (stream-ordered reuse)
-    auto alloc = [&](size_t bytes) {
-        tmp.emplace_back(std::max<size_t>(bytes, 16));
-        return tmp.back().p;
-    };
-    hipError_t e = hipSuccess;
+hipError_t mgpu_runs(Workspace& w, int64_t M, const uint64_t* skeys, uint32_t* head, uint32_t* rid, uint32_t* run0,
+                     uint32_t* nK, hipStream_t s) {
+    hipLaunchKernelGGL(k_mgpu_heads, dim3(grid_of(M)), dim3(256), 0, s, M, skeys, head);
+    CTG_TRY(hipGetLastError());
+    CTG_TRY(excl_scan(w.temp, head, rid, M, s));
+    hipLaunchKernelGGL(k_mgpu_runs, dim3(grid_of(M)), dim3(256), 0, s, M, head, rid, run0, nK);
+    return hipGetLastError();
+}
 
-    // nodes: the own range, or the own range and every received id, unique
-    if (NM == 0) {
-        r->nodes = L->nodes + n_lo;
-        r->n_nodes = n_cnt;
-        r->owned.push_back(L->nodes);
-        L->nodes = nullptr;
-    } else {
-        const int64_t total = n_cnt + NM;
-        uint64_t* list = (uint64_t*)alloc((size_t)total * 8);
-        if (!list) return hipErrorOutOfMemory;
-        int64_t* rnd = (int64_t*)alloc((size_t)(2 * CTG_MGPU_MAX_WORLD + 1) * 8);
-        if (!rnd) return hipErrorOutOfMemory;
-        e = hipMemcpyAsync(rnd, rn, (size_t)S.n * 8, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(rnd + CTG_MGPU_MAX_WORLD, rn_off, (size_t)(S.n + 1) * 8, hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_mgpu_node_list, dim3(grid_of(total)), dim3(256), 0, s, S, rv, rnd,
-                           rnd + CTG_MGPU_MAX_WORLD, L->nodes + n_lo, n_cnt, list, total);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        ctg_result* raw = nullptr;
-        const int rc = ctg_unique_values(list, total, CTG_MEM_DEVICE, s, &raw);
-        ResultPtr U(raw);
-        if (rc) {   // its status and message pass through
-            *lib_rc = rc;
-            return hipErrorUnknown;
-        }
-        r->nodes = U->nodes;
-        r->n_nodes = U->n_nodes;
-        r->owned.push_back(U->nodes);
-        U->nodes = nullptr;
-    }
+hipError_t mgpu_combine(Workspace& w, const ExchangeSegs& S, const MergeIO& io, uint32_t* nrank, hipStream_t s) {
+    hipLaunchKernelGGL(k_mgpu_combine, dim3(grid_of(S.rows())), dim3(256), 0, s, S, io);
+    CTG_TRY(hipGetLastError());
+    return excl_scan(w.temp, io.mnew, nrank, S.rows(), s);
+}
 
-    // edges and features
-    if (M == 0 && !L->partial_adj) {   // nothing received, nothing to drop: the own range is the shard
-        r->edges = L->edges + 2 * e_lo;
-        r->features = L->features ? L->features + 10 * e_lo : nullptr;
-        r->n_edges = e_cnt;
-        r->owned.push_back(L->edges);
-        r->owned.push_back(L->features);
-        L->edges = nullptr;
-        L->features = nullptr;
-        return hipSuccess;
-    }
-    // needs a CTG_KEEP_STATS partial table (rows, or CTG_DEFER_STATS records)
-    if ((!L->stats && !L->defer.on) || !L->features) return hipErrorInvalidValue;
-    // row indices, run heads and output positions below are u32
-    if (M >= (1ll << 32) || e_cnt + M >= (1ll << 32) || NM >= (1ll << 32)) {
-        set_error("ctg_mgpu_merge: more than 2^32 rows in one shard (split the slab over more ranks)");
-        *lib_rc = CTG_ERR_UNSUPPORTED;
-        return hipErrorNotSupported;
-    }
-    MergeIO io{};
-    io.own_edges = L->edges + 2 * e_lo;
-    io.own_feats = L->features + 10 * e_lo;
-    io.own_wide = L->stats ? L->stats + WREC_WORDS * e_lo : nullptr;
-    io.own_sums = L->stat_sums ? L->stat_sums + e_lo : nullptr;
-    if (!L->stats) io.defer = L->defer;
-    io.own_row0 = e_lo;
-    io.n_own = e_cnt;
-    io.recv = rv;
-    io.partial_adj = L->partial_adj;
-    io.scale = (double)NBINS / (hist_hi - hist_lo);
-    io.offset = hist_lo;
-    const int64_t Mb = std::max<int64_t>(M, 1);
-    uint32_t* order = (uint32_t*)alloc(Mb * 4);
-    uint64_t* skeys = (uint64_t*)alloc(Mb * 16);
-    uint32_t* head = (uint32_t*)alloc(Mb * 4);
-    uint32_t* rid = (uint32_t*)alloc(Mb * 4);
-    uint32_t* run0 = (uint32_t*)alloc((Mb + 1) * 4);
-    uint64_t* mkeys = (uint64_t*)alloc(Mb * 16);
-    double* mfeats = (double*)alloc(Mb * N_FEATURES * 8);
-    uint32_t* mkeep = (uint32_t*)alloc(Mb * 4);
-    uint32_t* mnew = (uint32_t*)alloc(Mb * 4);
-    uint32_t* nrank = (uint32_t*)alloc(Mb * 4);
-    int64_t* mins = (int64_t*)alloc(Mb * 8);
-    uint32_t* touched = (uint32_t*)alloc(std::max<int64_t>(e_cnt, 1) * 4);
-    const int64_t n_slots = e_cnt + M;
-    uint32_t* keep = (uint32_t*)alloc(std::max<int64_t>(n_slots, 1) * 4);
-    uint32_t* fpos = (uint32_t*)alloc(std::max<int64_t>(n_slots, 1) * 4);
-    MergeCounts* mc = reinterpret_cast<MergeCounts*>(w.small + SLOT_MERGE);
-    uint32_t* nK = &mc->keys;
-    uint32_t* n_out = &mc->rows;
-    if (!order || !skeys || !head || !rid || !run0 || !mkeys || !mfeats || !mkeep || !mnew || !nrank || !mins ||
-        !touched || !keep || !fpos)
-        return hipErrorOutOfMemory;
-    io.order = order;
-    io.skeys = skeys;
-    io.run0 = run0;
-    io.nK = nK;
-    io.mkeys = mkeys;
-    io.mfeats = mfeats;
-    io.mkeep = mkeep;
-    io.mnew = mnew;
-    io.mins = mins;
-    io.touched = touched;
-    if ((e = hipMemsetAsync(mc, 0, sizeof(MergeCounts), s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(mnew, 0, Mb * 4, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(touched, 0, std::max<int64_t>(e_cnt, 1) * 4, s)) != hipSuccess) return e;
-    if (M > 0) {
-        hipLaunchKernelGGL(k_mgpu_order, dim3(grid_of(M)), dim3(256), 0, s, S, rv, order, skeys);
-        hipLaunchKernelGGL(k_mgpu_heads, dim3(grid_of(M)), dim3(256), 0, s, M, skeys, head);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = excl_scan(w.temp, head, rid, M, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_mgpu_runs, dim3(grid_of(M)), dim3(256), 0, s, M, head, rid, run0, nK);
-        hipLaunchKernelGGL(k_mgpu_combine, dim3(grid_of(M)), dim3(256), 0, s, S, io);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = excl_scan(w.temp, mnew, nrank, M, s)) != hipSuccess) return e;
-    }
+hipError_t mgpu_slots(Workspace& w, const MergeIO& io, const uint32_t* nrank, int64_t n_slots, uint32_t* keep,
+                      uint32_t* fpos, hipStream_t s) {
     hipLaunchKernelGGL(k_mgpu_slots, dim3(grid_of(n_slots)), dim3(256), 0, s, io, nrank, keep, n_slots);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = excl_scan(w.temp, keep, fpos, n_slots, s)) != hipSuccess) return e;
-    r->edges = (uint64_t*)dev_alloc((size_t)std::max<int64_t>(n_slots, 1) * 16);
-    r->features = (double*)dev_alloc((size_t)std::max<int64_t>(n_slots, 1) * N_FEATURES * 8);
-    r->owned.push_back(r->edges);
-    r->owned.push_back(r->features);
-    if (!r->edges || !r->features) return hipErrorOutOfMemory;
-    hipLaunchKernelGGL(k_mgpu_scatter, dim3(grid_of(n_slots)), dim3(256), 0, s, io, nrank, keep, fpos, n_slots,
-                       r->edges, r->features, n_out);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    uint32_t* rows_host = &reinterpret_cast<MergeCounts*>(w.small_host + SLOT_MERGE)->rows;
-    if ((e = hipMemcpyAsync(rows_host, n_out, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    r->n_edges = n_slots ? *rows_host : 0;
-    return hipSuccess;
+    CTG_TRY(hipGetLastError());
+    return excl_scan(w.temp, keep, fpos, n_slots, s);
+}
+
+hipError_t mgpu_scatter(const MergeIO& io, const uint32_t* nrank, const uint32_t* keep, const uint32_t* fpos,
+                        int64_t n_slots, uint64_t* out_e, double* out_f, uint32_t* n_out, hipStream_t s) {
+    hipLaunchKernelGGL(k_mgpu_scatter, dim3(grid_of(n_slots)), dim3(256), 0, s, io, nrank, keep, fpos, n_slots, out_e,
+                       out_f, n_out);
+    return hipGetLastError();
 }
 
 CTG_BOUNDS_TAKE(mgpu)

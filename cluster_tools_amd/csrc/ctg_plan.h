@@ -1,10 +1,11 @@
 // The host layer's decisions as pure functions: call boxes, tile depths, the
 // batched-block plan, record-buffer and candidate-buffer sizes, the Bloom
 // filter's size, the narrow-row mode, the channel classification, the
-// adjacency rule of the reduce, the count-matrix sums of the multi-GPU
-// exchange, the choice between the record-sort paths, the key range of the
-// bucket sort and the bucket geometry of the bucket and group sorts.  Plain
-// C++17 -- no HIP (the bucket arithmetic the kernels share is marked CTG_HD),
+// adjacency rule of the reduce, the slab range and the segment plan of the
+// multi-GPU exchange, the choice between the record-sort paths, the key range
+// of the bucket sort and the bucket geometry of the bucket and group sorts.  Plain
+// C++17 -- no HIP (the bucket arithmetic and the segment lookup the kernels
+// share are marked CTG_HD),
 // no getenv: the environment switches are
 // read by the callers (scan_switches, sort_switches) and passed in as values --
 // so a host program can exercise them without a GPU (tools/plan_check.cpp,
@@ -420,20 +421,87 @@ constexpr bool cc_seam_partner(int c, int64_t z, int64_t y, int64_t x, int dz, i
 // the multi-GPU exchange's count matrix: counts_all[(src * world + dst) * 2]
 // rows and [.. + 1] nodes of src's table that dst owns
 // ---------------------------------------------------------------------------
-struct ExchangeCounts {
-    int64_t rows, nodes;   // of this rank's table, over all destinations
-    int64_t words;         // u64 words this rank sends (pack) / receives (merge)
+// The segments of one direction of a rank's exchange, in rank order of the
+// other side: a pair with rows or nodes has a segment (its rows, row_words
+// words each, then its node ids), a pair with neither has none, and the rank
+// itself never has one.  Passed by value to the kernels (ctg_mgpu.hip).
+struct ExchangeSegs {
+    int64_t row0[CTG_MGPU_MAX_WORLD + 1];    // rows of the segments before segment i; [n]: all rows
+    int64_t node0[CTG_MGPU_MAX_WORLD + 1];   // the same of the node ids
+    int64_t w_off[CTG_MGPU_MAX_WORLD + 1];   // word offset of segment i in the buffer; [n]: its words
+    // send side: where segment i's rows / node ids start in this rank's table
+    int64_t e_start[CTG_MGPU_MAX_WORLD], n_start[CTG_MGPU_MAX_WORLD];
+    int n;
+    constexpr int64_t rows() const { return row0[n]; }
+    constexpr int64_t nodes() const { return node0[n]; }
+    constexpr int64_t words() const { return w_off[n]; }
 };
-inline ExchangeCounts exchange_counts(const int64_t* counts_all, int world, int rank, int row_words, bool receive) {
-    ExchangeCounts c{};
-    for (int d = 0; d < world; ++d) {
-        const int64_t* mine = counts_all + ((int64_t)rank * world + d) * 2;
-        const int64_t* other = receive ? counts_all + ((int64_t)d * world + rank) * 2 : mine;
-        c.rows += mine[0];
-        c.nodes += mine[1];
-        if (d != rank) c.words += other[0] * row_words + other[1];
+
+// The segment that holds element i of a prefix table (prefix[s] <= i <
+// prefix[s + 1]; an empty segment holds nothing), for 0 <= i < prefix[n].
+// Linear: at most CTG_MGPU_MAX_WORLD segments, mostly a handful.
+CTG_HD constexpr int seg_of(const int64_t* prefix, int n, int64_t i) {
+    int s = 0;
+    while (s + 1 < n && prefix[s + 1] <= i) ++s;
+    return s;
+}
+
+// Everything the host derives from the count matrix for one rank
+// (1 <= world <= CTG_MGPU_MAX_WORLD, 0 <= rank < world).
+struct ExchangePlan {
+    int64_t e_lo, e_cnt, n_lo, n_cnt;   // the own range: rows / node ids this rank keeps, in its table
+    int64_t rows, nodes;                // of this rank's table, over all destinations
+    ExchangeSegs send, recv;            // what leaves for / arrives from every other rank
+    bool any;                           // some rank sends something: the same answer on every rank
+    // the merge's row indices, run heads and output positions are u32
+    constexpr bool too_large() const {
+        return recv.rows() >= (1ll << 32) || e_cnt + recv.rows() >= (1ll << 32) || recv.nodes() >= (1ll << 32);
     }
-    return c;
+};
+
+inline ExchangePlan exchange_plan(const int64_t* counts_all, int world, int rank, int row_words = CTG_MGPU_ROW_WORDS) {
+    ExchangePlan p{};
+    auto push = [row_words](ExchangeSegs& S, int64_t rows, int64_t nodes, int64_t e_start, int64_t n_start) {
+        S.e_start[S.n] = e_start;
+        S.n_start[S.n] = n_start;
+        ++S.n;
+        S.row0[S.n] = S.row0[S.n - 1] + rows;
+        S.node0[S.n] = S.node0[S.n - 1] + nodes;
+        S.w_off[S.n] = S.w_off[S.n - 1] + rows * row_words + nodes;
+    };
+    for (int q = 0; q < world; ++q) {
+        const int64_t* to = counts_all + ((int64_t)rank * world + q) * 2;     // this rank -> q
+        const int64_t* from = counts_all + ((int64_t)q * world + rank) * 2;   // q -> this rank
+        if (q == rank) {
+            p.e_lo = p.rows, p.e_cnt = to[0];
+            p.n_lo = p.nodes, p.n_cnt = to[1];
+        } else {
+            if (to[0] || to[1]) push(p.send, to[0], to[1], p.rows, p.nodes);
+            if (from[0] || from[1]) push(p.recv, from[0], from[1], 0, 0);
+        }
+        p.rows += to[0];
+        p.nodes += to[1];
+    }
+    for (int64_t i = 0; i < (int64_t)world * world && !p.any; ++i)
+        p.any = i / world != i % world && (counts_all[2 * i] || counts_all[2 * i + 1]);
+    return p;
+}
+
+// The z planes of a rank's slab: owned [z0, z1), read from read_begin -- as
+// many halo planes below z0 as a face (1) or an offset reaches down.  up: the
+// reach above, for which the layout has no halo.
+struct SlabRange {
+    int64_t down, up;
+    int64_t read_begin, z0, z1;
+};
+inline SlabRange slab_range(int64_t Z, int world, int rank, const int64_t* offsets, int n_channels) {
+    SlabRange r{1, 0, 0, Z * rank / world, Z * (rank + 1) / world};
+    for (int c = 0; c < n_channels; ++c) {
+        r.down = std::max<int64_t>(r.down, -offsets[3 * c]);
+        r.up = std::max<int64_t>(r.up, offsets[3 * c]);
+    }
+    r.read_begin = r.z0 - std::min(r.down, r.z0);
+    return r;
 }
 
 // ---------------------------------------------------------------------------

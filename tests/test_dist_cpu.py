@@ -158,6 +158,35 @@ def test_segment_words():
     assert not cdist._any_exchange(diag, 3)
 
 
+from test_plan import plan  # noqa: E402,F401  (the fixture: tools/plan_check.cpp, built for the host)
+
+
+def test_segment_words_agree_with_exchange_plan(plan):  # noqa: F811
+    """The segment rule is stated once, in exchange_plan (csrc/ctg_plan.h);
+    dist.segment_words / _any_exchange restate it in Python for speed.  On
+    every matrix of tests/exchange_plans.py and every rank: the same send and
+    receive words in total, a nonzero entry exactly where the plan has a
+    segment with words, and the same "anything to exchange" decision."""
+    import exchange_plans as XP
+    assert cdist.ROW_WORDS == XP.ROW and cdist.MAX_WORLD == XP.MAX_WORLD
+    for name, (world, counts) in XP.MATRICES.items():
+        c = np.array(counts, dtype=np.int64)
+        flat = XP.flat(counts)
+        q = []
+        for r in range(world):
+            q += ['xchg %d %d %d 0 %s' % (world, r, XP.ROW, flat), 'xchg %d %d %d 1 %s' % (world, r, XP.ROW, flat),
+                  'xplan %d %d %s' % (world, r, flat)]
+        got = plan(q)
+        for r in range(world):
+            send, recv = cdist.segment_words(c, world, r)
+            assert len(send) == len(recv) == world and send[r] == 0 and recv[r] == 0
+            assert sum(send) == int(got[3 * r].split()[2]) and sum(recv) == int(got[3 * r + 1].split()[2]), (name, r)
+            tables = XP.prefixes(got[3 * r + 2])
+            for words, (n, w_off) in ((send, tables[2]), (recv, tables[5])):
+                assert [w for w in words if w] == [b - a for a, b in zip(w_off, w_off[1:])], (name, r)
+            assert cdist._any_exchange(c, world) == bool(int(got[3 * r + 2].split()[6])), (name, r)
+
+
 def test_exchange_in_one_process_matches_whole_volume():
     """The four exchange steps of every rank simulated in one process (the
     collectives replaced by stacking / slicing; tests/exchange_sim.py): the

@@ -394,6 +394,104 @@ def test_exchange_counts(plan):
     assert plan(['xchg 1 0 28 0 5 9', 'xchg 1 0 28 1 5 9']) == ['5 9 0', '5 9 0']     # one rank: nothing moves
 
 
+import exchange_plans as XP  # noqa: E402
+
+
+def _xplan(plan, name, ranks=None):
+    world, counts = XP.MATRICES[name]
+    ranks = range(world) if ranks is None else ranks
+    got = plan(['xplan %d %d %s' % (world, r, XP.flat(counts)) for r in ranks])
+    return [[int(x) for x in g.split()] for g in got], got
+
+
+def test_exchange_plan_matches_restatement(plan):
+    """exchange_plan of every rank of every matrix of tests/exchange_plans.py,
+    field by field against the restatement in Python integers."""
+    for name, (world, counts) in XP.MATRICES.items():
+        got, _ = _xplan(plan, name)
+        for r in range(world):
+            assert got[r] == XP.restate(counts, world, r)[0], (name, r)
+
+
+def test_exchange_plan_by_hand(plan):
+    (w1,), _ = _xplan(plan, 'world1')
+    assert w1 == [0, 5, 0, 9, 5, 9, 0, 0] + [0, 0, 0, 0] * 2            # one rank: own range only, no segment
+    # world 3, counts[s][d] = (10s + d + 1, 100s + 7d), rank 0: keeps (1, 0); sends (2, 7) to 1 and (3, 14) to 2,
+    # which start at row 1 / node 0 and row 3 / node 7 of its table; receives (11, 100) from 1 and (21, 200) from 2
+    (r0,), _ = _xplan(plan, 'world3', [0])
+    assert r0 == [0, 1, 0, 0, 6, 21, 1, 0,
+                  2, 0, 0, 0, 2, 7, 63, 5, 21, 161, 1, 0, 3, 7,
+                  2, 0, 0, 0, 11, 100, 408, 32, 300, 1196, 0, 0, 0, 0]
+    for name in ('diagonal',):                                           # nothing to exchange, on every rank
+        got, _ = _xplan(plan, name)
+        assert all(g[6] == 0 and g[8:] == [0, 0, 0, 0] * 2 for g in got)
+    got, _ = _xplan(plan, 'only_to_last')
+    assert [g[6] for g in got] == [1] * 5                                # the same answer on every rank
+    assert got[1][8:13] == [1, 0, 0, 0, 7] and got[4][-9:] == [1, 0, 0, 0, 7, 1, 7 * 28 + 1, 0, 0]
+    assert all(g[8] == 0 for i, g in enumerate(got) if i != 1)           # nobody else sends
+    # a destination with nodes and no rows keeps its segment; one with neither has none
+    assert _xplan(plan, 'nodes_only_between', [0])[0][0][8:20] == [3, 0, 0, 0, 3, 2, 86, 3, 6, 90, 8, 7]
+    assert _xplan(plan, 'empty_between', [0])[0][0][8:17] == [2, 0, 0, 0, 3, 2, 86, 8, 3]
+    assert _xplan(plan, 'empty_own', [1])[0][0][:4] == [2, 0, 2, 0]
+    got, _ = _xplan(plan, 'world32_full', [0, 31])
+    assert got[0][8] == 31 and got[1][8] == 31                           # 31 segments each way
+
+
+def test_exchange_plan_thresholds(plan):
+    """M, e_cnt + M and NM against 2^32, at the bound and one below."""
+    for what in ('rows', 'slots', 'nodes'):
+        assert _xplan(plan, what + '_at_bound', [0])[0][0][7] == 1
+        assert _xplan(plan, what + '_below_bound', [0])[0][0][7] == 0
+    assert _xplan(plan, 'slots_at_bound', [1])[0][0][7] == 0             # the other rank receives nothing
+
+
+def _segof(prefix, i):
+    return 'segof %d %d %s' % (i, len(prefix) - 1, ' '.join(map(str, prefix)))
+
+
+def test_seg_of(plan):
+    """seg_of at the first and last element of every non-empty segment of
+    every prefix table of the matrices, and on tables made by hand: one
+    segment, 32 segments, and equal consecutive prefixes (empty segments)."""
+    tables = [[0, 5], [0, 1], list(range(33)), [3 * i * i for i in range(33)],
+              [0, 3, 3, 3, 7], [0, 0, 4], [0, 4, 4], [0, 0, 0, 1], [0, 2, 2, 5, 5, 5, 6, 6]]
+    for name, (world, counts) in XP.MATRICES.items():
+        if name.endswith('bound'):
+            continue
+        for line in _xplan(plan, name)[1]:
+            tables += [p for n, p in XP.prefixes(line) if n and p[-1]]
+    q, exp = [], []
+    for p in tables:
+        n = len(p) - 1
+        for s in range(n):
+            if p[s] < p[s + 1]:
+                q += [_segof(p, p[s]), _segof(p, p[s + 1] - 1)]
+                exp += [s, s]
+        q += [_segof(p, 0), _segof(p, p[-1] - 1)]
+        exp += [min(s for s in range(n) if p[s + 1] > 0), max(s for s in range(n) if p[s] < p[-1])]
+    assert any(len(p) == 2 for p in tables) and any(len(p) == 33 for p in tables)
+    assert len(q) > 1000
+    assert [int(g) for g in plan(q)] == exp
+
+
+def test_slab_range(plan):
+    """slab_range on the cases of test_dist_cpu.py::test_mgpu_slab_plan_c_abi:
+    owned ranges tile [0, Z) in rank order, the halo below reaches as far as
+    the faces / offsets (clipped at plane 0), and the reach above is reported."""
+    nn = [[-1, 0, 0], [0, -1, 0], [0, 0, -1]]
+    lr = nn + [[-2, 0, 0], [0, -3, 0], [0, 0, -3], [-3, 0, 0], [0, -9, 0], [0, 0, -9], [-4, 0, 0], [0, -27, 0], [0, 0, -27]]
+    for Z, world in [(1024, 1), (2048, 8), (101, 4), (7, 7)]:
+        for offs, down in [([], 1), (nn, 1), (lr, 4)]:
+            tail = '%d %s' % (len(offs), ' '.join(str(v) for o in offs for v in o))
+            got = [[int(x) for x in g.split()] for g in plan(['slab %d %d %d %s' % (Z, world, r, tail) for r in range(world)])]
+            assert got[0][2:4] == [0, 0] and got[-1][4] == Z
+            for r, (dn, up, rd, own, end) in enumerate(got):
+                assert (dn, up) == (down, 0)
+                assert own == Z * r // world and end == Z * (r + 1) // world and end > own
+                assert own - rd == (min(down, own) if r else 0)
+    assert plan(['slab 64 2 0 1 1 0 0', 'slab 64 1 0 2 5 0 0 -2 0 0']) == ['1 1 0 0 32', '2 5 0 0 64']
+
+
 # ---------------------------------------------------------------------------
 # bucket geometry of the group sort and of the packed-key bucket sort
 # (plan_group_sort, plan_bucket_keys, gs_bucket_of, gs_bucket_key) against

@@ -24,7 +24,12 @@
 //   adj N_CHANNELS SKIP_MARKS ADJ_FILTER HAVE_BLOOM -> need_adj of a whole-array call
 //   adjblocks N_CHANNELS                     -> need_adj of a batched call
 //   fold r[NREG]                             -> total fullest off[NREG + 1]
-//   xchg WORLD RANK ROW_WORDS RECEIVE counts[WORLD * WORLD * 2] -> rows nodes words
+//   xchg WORLD RANK ROW_WORDS RECEIVE counts[WORLD * WORLD * 2] -> rows nodes words   (of exchange_plan)
+//   xplan WORLD RANK counts[WORLD * WORLD * 2]
+//        -> e_lo e_cnt n_lo n_cnt rows nodes any too_large, then for the send and the receive table:
+//           n  (row0 node0 w_off)[n + 1]  (e_start n_start)[n]
+//   segof I N prefix[N + 1]                  -> seg_of
+//   slab Z WORLD RANK N  z y x ...   (N offsets) -> down up read_begin z0 z1
 //   gsort N NB UB IB MIN_LABEL MAX_LABEL     -> why shift nbk bk0 min_pk max_pk   (why: GroupSortPlan::Why; shift -1,
 //                                               the rest 0 where it declined before choosing)
 //   gskey PK SHIFT BK0                       -> gs_bucket_of(pk)  gs_bucket_key(that bucket)
@@ -172,8 +177,37 @@ int main() {
             in >> world >> rank >> row_words >> receive;
             std::vector<int64_t> c((size_t)world * world * 2);
             for (int64_t& v : c) in >> v;
-            const ExchangeCounts x = exchange_counts(c.data(), world, rank, row_words, receive);
-            printf("%" PRId64 " %" PRId64 " %" PRId64 "\n", x.rows, x.nodes, x.words);
+            const ExchangePlan x = exchange_plan(c.data(), world, rank, row_words);
+            printf("%" PRId64 " %" PRId64 " %" PRId64 "\n", x.rows, x.nodes, (receive ? x.recv : x.send).words());
+        } else if (cmd == "xplan") {
+            int world, rank;
+            in >> world >> rank;
+            std::vector<int64_t> c((size_t)world * world * 2);
+            for (int64_t& v : c) in >> v;
+            const ExchangePlan x = exchange_plan(c.data(), world, rank);
+            printf("%" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %d %d", x.e_lo, x.e_cnt,
+                   x.n_lo, x.n_cnt, x.rows, x.nodes, (int)x.any, (int)x.too_large());
+            for (const ExchangeSegs* S : {&x.send, &x.recv}) {
+                printf(" %d", S->n);
+                for (int i = 0; i <= S->n; ++i) printf(" %" PRId64 " %" PRId64 " %" PRId64, S->row0[i], S->node0[i], S->w_off[i]);
+                for (int i = 0; i < S->n; ++i) printf(" %" PRId64 " %" PRId64, S->e_start[i], S->n_start[i]);
+            }
+            printf("\n");
+        } else if (cmd == "segof") {
+            int n;
+            int64_t i;
+            in >> i >> n;
+            std::vector<int64_t> prefix(n + 1);
+            for (int64_t& v : prefix) in >> v;
+            printf("%d\n", seg_of(prefix.data(), n, i));
+        } else if (cmd == "slab") {
+            int64_t Z;
+            int world, rank, n;
+            in >> Z >> world >> rank >> n;
+            std::vector<int64_t> off(3 * (size_t)n + 1);
+            for (int i = 0; i < 3 * n; ++i) in >> off[i];
+            const SlabRange r = slab_range(Z, world, rank, off.data(), n);
+            printf("%" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 "\n", r.down, r.up, r.read_begin, r.z0, r.z1);
         } else if (cmd == "gsort") {
             int64_t n;
             int nb, ub, ib;
