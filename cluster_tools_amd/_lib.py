@@ -31,6 +31,12 @@ CTG_ASSIGN_SPARSE = 1
 CTG_CC_GREATER = 0
 CTG_CC_LESS = 1
 CTG_CC_EQUAL = 2
+CTG_EDT_SRC_NONZERO = 0
+CTG_EDT_SRC_GREATER = 1
+CTG_EDT_SRC_EQUAL = 2
+CTG_EDT_TO_BACKGROUND = 1
+CTG_EDT_2D = 2
+CTG_EDT_OUT_D2 = 4
 CTG_MAX_CHANNELS = 24
 CTG_N_FEATURES = 10
 CTG_NBINS = 40
@@ -116,6 +122,8 @@ PROTOTYPES = {
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp,
                                                 c_u64p]),
     'ctg_merge_assignments': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_uint64, c_vp, ctypes.c_int, c_vp, c_u64p]),
+    'ctg_distance_transform': (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_double,
+                                              ctypes.c_uint64, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

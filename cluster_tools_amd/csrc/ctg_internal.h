@@ -690,6 +690,38 @@ hipError_t launch_uf_scan(uint32_t* seg, int64_t n_seg, uint32_t* words, hipStre
 hipError_t launch_uf_write(const uint32_t* parent, const uint32_t* rank, const uint32_t* seg, int64_t n,
                            uint64_t plus, uint64_t* out, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// exact Euclidean distance transform (ctg_edt.hip).  Call-sized pool buffers
+// only, as the label overlaps.
+// ---------------------------------------------------------------------------
+struct EdtSrc {                 // the box of a call and its seed predicate
+    const void* src;            // the array (uint8, float32, uint32 or uint64)
+    int64_t s_z, s_y;           // the array's strides in elements
+    int64_t base;               // element offset of the box's first voxel
+    uint32_t n[3];              // the box (z, y, x)
+    float threshold;            // CTG_EDT_SRC_GREATER
+    uint64_t label;             // CTG_EDT_SRC_EQUAL
+    int invert;                 // CTG_EDT_TO_BACKGROUND: the seeds are where the predicate fails
+};
+constexpr int EDT_PART_WORDS = 3;   // a workgroup's partial of the last pass: D2 bits, its first index, voxels without a seed
+struct EdtLineArgs {            // one envelope pass (y or z)
+    const void* in;             // box-shaped u16 |dx| (x pass) or u32 (|dy|, |dx| << 16) (y pass)
+    void* out;                  // box-shaped u32 pairs, or with final_pass the float32 result (out_d2: float64 D2)
+    int in32, final_pass, out_d2;
+    int axis;                   // the line's axis: 1 y, 0 z
+    uint32_t n[3];
+    double p[3];                // the pitch (z, y, x)
+    double diag2;               // edt_diag2: D2 of a voxel without a seed in its domain
+    uint64_t* stack;            // the stack buffer of edt_line_plan, or null (LDS)
+    unsigned long long* part;   // final_pass: EDT_PART_WORDS words per workgroup
+};
+// kind: 0 uint8 != 0, 1 float32 > threshold, 2 uint32 == label, 3 uint64 == label; |dx| of every voxel into out,
+// the seeds added to *info (zeroed before)
+hipError_t launch_edt_x(const EdtSrc& A, int kind, uint16_t* out, unsigned long long* info, hipStream_t s);
+hipError_t launch_edt_line(const EdtLineArgs& A, const EdtLinePlan& P, hipStream_t s);
+// n partials -> info[1 .. 3]
+hipError_t launch_edt_fold(const unsigned long long* part, int64_t n, unsigned long long* info, hipStream_t s);
+
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,
                       int world, uint64_t* spl, int64_t* counts, hipStream_t s);

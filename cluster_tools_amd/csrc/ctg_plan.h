@@ -418,6 +418,63 @@ constexpr bool cc_seam_partner(int c, int64_t z, int64_t y, int64_t x, int dz, i
 }
 
 // ---------------------------------------------------------------------------
+// the exact Euclidean distance transform (ctg_edt.hip)
+// ---------------------------------------------------------------------------
+// offsets travel as u16 and 0xFFFF marks "no seed": an axis stays below 2^15
+constexpr int64_t EDT_MAX_AXIS = 32768;
+constexpr int64_t EDT_MAX_VOXELS = 1ll << 32;
+constexpr int EDT_ROW_WORDS = (int)(EDT_MAX_AXIS / 64);   // 64-bit seed words of the longest row
+constexpr int EDT_ROW_SUPER = EDT_ROW_WORDS / 64;         // one bit per word above them
+constexpr int EDT_X_WAVES = 4;                            // rows a workgroup of the x pass takes at a time
+constexpr int64_t EDT_X_MAX_GRID = 8192;
+// Envelope passes: a workgroup is one wave, a lane per column, and each lane
+// keeps a stack of up to `line` 8-byte entries (ctg_edt.h).  Up to
+// EDT_LDS_LINE entries the stack lives in LDS: 64 lanes x 32 x 8 B = 16 KiB a
+// wave, ten waves in a CU's 160 KiB (with 64 entries and five waves the z pass
+// of a sparse 64 x 1024 x 1024 box took 0.61 ms against 0.26 ms one line
+// longer, in the buffer: DESIGN.md 5).  Longer lines keep it in a call-sized
+// buffer laid out [depth][workgroup][lane], so lanes at equal depth coalesce;
+// the grid shrinks until the buffer fits EDT_STACK_BYTES (the workgroups then
+// stride over the column groups).
+constexpr int EDT_LDS_LINE = 32;
+constexpr int64_t EDT_LINE_MAX_GRID = 8192;
+constexpr int64_t EDT_STACK_BYTES = 1ll << 30;
+struct EdtLinePlan {
+    int lds;              // 1: the stack in LDS; 0: in the workspace buffer
+    int64_t groups;       // groups of 64 columns
+    int64_t grid;         // workgroups, each striding over the groups
+    int64_t stack_bytes;  // the workspace buffer (0 with lds)
+};
+// line: the line's length; outer: rows of columns (z for the y pass, y for the
+// z pass); nx: columns per row
+inline EdtLinePlan edt_line_plan(int64_t line, int64_t outer, int64_t nx) {
+    EdtLinePlan p{};
+    p.lds = line <= EDT_LDS_LINE;
+    p.groups = outer * ((nx + TILE_X - 1) / TILE_X);
+    const int64_t per_wg = line * TILE_X * 8;
+    const int64_t cap = p.lds ? EDT_LINE_MAX_GRID
+                              : std::max<int64_t>(1, std::min(EDT_LINE_MAX_GRID, EDT_STACK_BYTES / std::max<int64_t>(per_wg, 1)));
+    p.grid = std::min(p.groups, cap);
+    p.stack_bytes = p.lds ? 0 : p.grid * per_wg;
+    return p;
+}
+// workgroups of the x pass over `rows` rows
+inline int64_t edt_x_grid(int64_t rows) {
+    return std::min<int64_t>((rows + EDT_X_WAVES - 1) / EDT_X_WAVES, EDT_X_MAX_GRID);
+}
+// Which passes a box of n (z, y, x) runs after the x pass, which always runs
+// (it reads the source): the y pass writes offsets for a z pass to follow, or,
+// with no z pass (2-D mode, or one slice), the result; a z pass over a box of
+// one row per slice reads the x pass's output directly.
+struct EdtPasses {
+    bool y, z;   // y: the y pass runs (it always does unless the z pass reads the rows directly)
+};
+inline EdtPasses edt_passes(const int64_t* n, bool two_d) {
+    const bool z = !two_d && n[0] > 1;
+    return {!(z && n[1] == 1), z};
+}
+
+// ---------------------------------------------------------------------------
 // the multi-GPU exchange's count matrix: counts_all[(src * world + dst) * 2]
 // rows and [.. + 1] nodes of src's table that dst owns
 // ---------------------------------------------------------------------------

@@ -7,6 +7,7 @@ calls after reading blocks from N5.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import sys
 import threading
@@ -1247,6 +1248,125 @@ def merge_assignments(pairs, n_labels, stream=None):
                                    L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(max_id))
     L.check(rc, 'ctg_merge_assignments')
     return table, int(max_id.value)
+
+
+EdtInfo = collections.namedtuple('EdtInfo', 'n_seeds n_unseeded argmax max_d2')
+
+
+def _edt_source(src, threshold, label):
+    """The source of a distance transform -> (array, CTG_EDT_SRC_*, bits)."""
+    if threshold is not None and label is not None:
+        raise ValueError('give a threshold (a float32 source) or a label (a label source), not both')
+    on_dev = _is_torch(src)
+    if on_dev:
+        import torch
+        if not (src.is_cuda and src.is_contiguous()):
+            raise ValueError('src must be a contiguous CUDA tensor')
+        kind = 'f' if src.dtype == torch.float32 else 'b' if src.dtype in (torch.uint8, torch.bool) else \
+            'i' if not src.is_floating_point() and src.element_size() in (4, 8) else None
+        if src.dtype == torch.bool:
+            src = src.view(torch.uint8)
+        bits = src.element_size() * 8
+    else:
+        src = np.asarray(src)
+        kind = 'f' if src.dtype == np.float32 else 'b' if src.dtype in (np.uint8, np.bool_) else \
+            'i' if src.dtype in (np.uint32, np.int32, np.uint64, np.int64) else None
+        src = np.ascontiguousarray(src)
+        if src.dtype == np.bool_:
+            src = src.view(np.uint8)
+        bits = src.dtype.itemsize * 8
+    if label is not None:
+        if kind != 'i':
+            raise ValueError('a label needs a source of 32- or 64-bit integers, got %s' % src.dtype)
+        if not 0 <= int(label) < 1 << 64:
+            raise ValueError('label must be a uint64 value, got %r' % (label,))
+        return src, L.CTG_EDT_SRC_EQUAL, bits
+    if threshold is not None:
+        if kind != 'f':
+            raise ValueError('a threshold needs a float32 source, got %s (a label source takes label=)' % src.dtype)
+        return src, L.CTG_EDT_SRC_GREATER, bits
+    if kind != 'b':
+        raise ValueError('a source without threshold or label must be uint8 or bool, got %s' % src.dtype)
+    return src, L.CTG_EDT_SRC_NONZERO, bits
+
+
+def _edt_pitch(pitch):
+    if pitch is None:
+        return None
+    p = [float(v) for v in pitch]
+    if len(p) != 3:
+        raise ValueError('pitch must have 3 entries (z, y, x), got %d' % len(p))
+    if not all(np.isfinite(v) and v > 0 for v in p):
+        raise ValueError('every pitch must be finite and positive, got %r' % (tuple(p),))
+    return p
+
+
+def distance_transform(src, pitch=None, threshold=None, label=None, to_background=False, two_d=False, begin=None,
+                       end=None, out=None, stream=None, squared=False):
+    """ctg_distance_transform: the exact Euclidean distance transform of the
+    box [begin, end) of ``src`` -> (dist, info).
+
+    ``src``: a (Z,Y,X) numpy array or contiguous CUDA tensor.  The predicate P
+    is ``x != 0`` for a uint8 / bool source, ``x > threshold`` (in float32; a
+    NaN is not greater) for a float32 source with ``threshold``, ``x == label``
+    for a 32- or 64-bit integer source with ``label``.  The seeds are the
+    voxels where P holds -- vigra's distanceTransform(background=True): every
+    other voxel's distance to the nearest of them -- or, with
+    ``to_background``, those where it fails (scipy's distance_transform_edt).
+    ``pitch``: the voxel size (z, y, x); ``two_d``: every z-slice on its own.
+    ``dist``: box-shaped float32 (``out`` to write into an existing one),
+    float32(sqrt(D2)) with D2 = (dz*pz)^2 + (dy*py)^2 + (dx*px)^2 in float64;
+    a voxel whose box (slice, with ``two_d``) holds no seed gets that domain's
+    diagonal.  With ``squared`` dist is float64 and holds D2 itself (the square
+    of scipy's float64 result).  ``info``: (n_seeds, n_unseeded, argmax, max_d2) -- the seeds of
+    the box, the voxels written with the diagonal, the flat index in the box of
+    the first voxel with the largest D2, and that D2."""
+    src, kind, bits = _edt_source(src, threshold, label)
+    on_dev = _is_torch(src)
+    shape = tuple(src.shape)
+    if len(shape) != 3:
+        raise ValueError('src must be 3-D, got shape %s' % (shape,))
+    p = _edt_pitch(pitch)
+    for box in (begin, end):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end must have 3 entries')
+    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
+    e = list(shape) if end is None else [int(v) for v in end]
+    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
+        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
+    oshape = tuple(hi - lo for lo, hi in zip(b, e))
+    if out is None:
+        if on_dev:
+            import torch
+            out = torch.empty(oshape, dtype=torch.float64 if squared else torch.float32, device=src.device)
+        else:
+            out = np.empty(oshape, dtype=np.float64 if squared else np.float32)
+    else:
+        if _is_torch(out) != on_dev:
+            raise ValueError('out must be of the same kind as src (numpy array or CUDA tensor)')
+        if on_dev:
+            import torch
+            ok = out.is_cuda and out.is_contiguous() and out.dtype == (torch.float64 if squared else torch.float32)
+        else:
+            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and \
+                out.dtype == (np.float64 if squared else np.float32)
+        if not ok or tuple(out.shape) != oshape:
+            raise ValueError('out must be a contiguous %s array of the shape of the box %s'
+                             % ('float64' if squared else 'float32', oshape))
+    lib = L.load()
+    L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    info = (ctypes.c_uint64 * 4)()
+    flags = (L.CTG_EDT_TO_BACKGROUND if to_background else 0) | (L.CTG_EDT_2D if two_d else 0) | \
+        (L.CTG_EDT_OUT_D2 if squared else 0)
+    rc = lib.ctg_distance_transform(_ptr(src), kind, bits, _shape_arr(shape), _shape_arr(b), _shape_arr(e),
+                                    float(threshold or 0.0), int(label or 0),
+                                    (ctypes.c_double * 3)(*p) if p is not None else None, flags, _ptr(out),
+                                    L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, info)
+    L.check(rc, 'ctg_distance_transform')
+    return out, EdtInfo(int(info[0]), int(info[1]), int(info[2]),
+                        float(np.array([info[3]], dtype=np.uint64).view(np.float64)[0]))
 
 
 def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_offset=0, noise_amp=0.1,

@@ -804,3 +804,82 @@ def thresholded_components_workflow(input_path, input_key, output_path, output_k
     write_workflow(output_path, output_key, output_path, output_key, output_path, assignment_key, block_shape,
                    offset_path=offset_path, max_jobs=max_jobs, timer=timer, mode=mode)
     return timer
+
+
+# ------------------------------------------------------------------ region centers, object distances
+def _morphology_boxes(morphology_path, morphology_key, stop_plus):
+    """Columns 5:8 and 8:11 of the morphology table as uint64 (region_centers.py:161-166,
+    object_distances.py:217-221, which adds 1 to the stop)."""
+    with ndist._open(morphology_path, 'r') as f:
+        morphology = f[morphology_key][:]
+    return morphology[:, 5:8].astype('uint64'), morphology[:, 8:11].astype('uint64') + np.uint64(stop_plus)
+
+
+def _region_centers_job(input_path, input_key, morphology_path, morphology_key, output_path, output_key, n_labels,
+                        id_chunks, ignore_label, resolution, blocks):
+    """morphology/region_centers.py:136-176."""
+    from cluster_tools_amd.region_centers import region_centers_for_label_range
+    blk = blocking([0], [n_labels], [id_chunks])
+    bb_start, bb_stop = _morphology_boxes(morphology_path, morphology_key, 0)
+    with ndist._open(input_path, 'r') as f_in, ndist._open(output_path) as f_out:
+        ds_in, ds_out = f_in[input_key], f_out[output_key]
+        for b in blocks:
+            block = blk.getBlock(b)
+            region_centers_for_label_range(ds_in, ds_out, bb_start, bb_stop, block.begin[0], block.end[0],
+                                           ignore_label, resolution)
+
+
+def region_centers_workflow(input_path, input_key, morphology_path, morphology_key, output_path, output_key, max_id,
+                            ignore_label=None, resolution=(1, 1, 1), id_chunks=2000, max_jobs=1, timer=None,
+                            mode='threads'):
+    """RegionCenters (morphology/region_centers.py:26-133) over the
+    (max_id + 1, 11) table of morphology_workflow: the (n_labels, 3) float32
+    dataset ``output_key`` with chunks (id_chunks, 3) (:57-63), one job per
+    ranges of ``id_chunks`` labels (2000 in the reference)."""
+    timer = timer or Timer()
+    n_labels = int(max_id) + 1
+    with timer.stage('region_centers'):
+        with ndist._open(output_path) as f:
+            f.require_dataset(output_key, shape=(n_labels, 3), chunks=(min(int(id_chunks), n_labels), 3),
+                              dtype='float32', compression='gzip')
+        job = functools.partial(_region_centers_job, input_path, input_key, morphology_path, morphology_key,
+                                output_path, output_key, n_labels, int(id_chunks), ignore_label, list(resolution))
+        _run_jobs(job, _jobs(blocks_in_volume([n_labels], [int(id_chunks)]), max_jobs), mode)
+    return timer
+
+
+def _object_distances_job(input_path, input_key, morphology_path, morphology_key, n_labels, id_chunks, max_distance,
+                          resolution, blocks):
+    """distances/object_distances.py:198-241: the job's dict (returned instead
+    of pickled as object_distances_<job>.pkl)."""
+    from cluster_tools_amd.object_distances import distances_id_chunks
+    blk = blocking([0], [n_labels], [id_chunks])
+    bb_start, bb_stop = _morphology_boxes(morphology_path, morphology_key, 1)
+    res = {}
+    with ndist._open(input_path, 'r') as f:
+        ds_in = f[input_key]
+        for b in blocks:
+            res.update(distances_id_chunks(blk, b, ds_in, bb_start, bb_stop, max_distance, resolution))
+    return res
+
+
+def object_distances_workflow(input_path, input_key, morphology_path, morphology_key, output_path, max_id,
+                              max_distance, resolution=(1, 1, 1), id_chunks=2000, max_jobs=1, timer=None,
+                              mode='threads'):
+    """PairwiseDistanceWorkflow (distances/distance_workflow.py): ObjectDistances
+    over ranges of ``id_chunks`` labels, then MergePairwiseDistances: the jobs'
+    dicts merged into one, pickled to ``output_path`` (:19-29)."""
+    import pickle
+    timer = timer or Timer()
+    n_labels = int(max_id) + 1
+    with timer.stage('object_distances'):
+        job = functools.partial(_object_distances_job, input_path, input_key, morphology_path, morphology_key,
+                                n_labels, int(id_chunks), max_distance, list(resolution))
+        parts = _run_jobs(job, _jobs(blocks_in_volume([n_labels], [int(id_chunks)]), max_jobs), mode)
+    with timer.stage('merge_pairwise_distances'):
+        res = {}
+        for part in parts:
+            res.update(part)
+        with open(output_path, 'wb') as f:
+            pickle.dump(res, f)
+    return timer

@@ -45,6 +45,11 @@
  *                                        thresholded_components/block_components.py:161-182
  *   ctg_merge_assignments             <- nufd.boost_ufd and relabelConsecutive,
  *                                        thresholded_components/merge_assignments.py:125-132
+ *   ctg_distance_transform            <- vigra.filters.distanceTransform and
+ *                                        scipy.ndimage.distance_transform_edt,
+ *                                        watershed/watershed.py:140-161,
+ *                                        distances/object_distances.py:109-113,
+ *                                        morphology/region_centers.py:122
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -523,6 +528,75 @@ int ctg_threshold_components(const void* data, int data_kind, const void* mask, 
                              int connectivity, uint64_t* out, int mem, void* stream, uint64_t* n_components);
 int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, uint64_t* table, int mem,
                           void* stream, uint64_t* max_id);
+
+/*
+ * The exact Euclidean distance transform of a box.
+ *
+ * ctg_distance_transform <- vigra.filters.distanceTransform of _apply_dt
+ *                           (watershed/watershed.py:140-161), of fit_to_hmap
+ *                           (utils/volume_utils.py:296-325) and of
+ *                           upsample_skeletons.py:121;
+ *                           scipy.ndimage.distance_transform_edt of
+ *                           _labels_and_distances (distances/object_distances.py:109-113)
+ *                           and of region_centers_for_label_range
+ *                           (morphology/region_centers.py:106-133)
+ *   src, src_kind, src_bits  the (Z,Y,X) array and the predicate P on it:
+ *               CTG_EDT_SRC_NONZERO  uint8 / bool (src_bits 8), P = x != 0
+ *               CTG_EDT_SRC_GREATER  float32 (src_bits 32), P = x > (float)threshold in
+ *                                    float32; a NaN is not greater (watershed.py:143
+ *                                    without the cast)
+ *               CTG_EDT_SRC_EQUAL    uint32 or uint64 labels (src_bits 32 / 64),
+ *                                    P = x == label; label may be 2^32 or above
+ *                                    (object_distances.py:111, region_centers.py:118
+ *                                    without the host-side mask)
+ *               shape / begin / end as ctg_label_overlaps (NULL: the whole array)
+ *   pitch       NULL (1, 1, 1), or the voxel size (z, y, x), each finite and > 0
+ *               (pixel_pitch, sampling)
+ *   flags       CTG_EDT_TO_BACKGROUND  the seeds are the voxels where P fails (scipy's
+ *                                      distance_transform_edt, vigra's background=False);
+ *                                      without it they are those where P holds (vigra's
+ *                                      background=True)
+ *               CTG_EDT_2D             every z-slice of the box on its own
+ *                                      (watershed.py:151-155)
+ *               CTG_EDT_OUT_D2         out is box-shaped float64 and receives D2 itself (the
+ *                                      square of scipy's float64 result)
+ *   out         box-shaped float32.  For a voxel p whose nearest seed of the box is q,
+ *               d = p - q in index units:
+ *                 D2  = (dz*pz)*(dz*pz) + (dy*py)*(dy*py) + (dx*px)*(dx*px)   float64, this order
+ *                 out = (float)sqrt(D2)                       sqrt correctly rounded in float64
+ *               Nothing outside the box is a seed.  A voxel whose domain (the box; with
+ *               CTG_EDT_2D its slice) holds no seed gets the domain's diagonal,
+ *               (float)sqrt((nz*pz)^2 + (ny*py)^2 + (nx*px)^2) -- without the z term in
+ *               2-D mode --, a finite strict upper bound of every distance there.
+ *   info        NULL, or 4 host words: [0] the seeds in the box, [1] the voxels written
+ *               with the diagonal, [2] the flat C-order index in the box of the first voxel
+ *               with the largest D2 (the diagonal's square for voxels without a seed; ties go
+ *               to the smallest index), [3] that D2 as float64 bits.  The arg-max is taken
+ *               on D2, not on the float32 output, as np.argmax of scipy's float64 result
+ *               (region_centers.py:125).
+ * With integer-valued pitches and (nz*pz)^2 + (ny*py)^2 + (nx*px)^2 < 2^53 every
+ * term is exact and the result equals
+ * distance_transform_edt(~seeds, sampling=pitch).astype(float32) bit for bit; with
+ * other pitches a different choice among near-equal seeds moves it by at most 1
+ * float32 ulp.
+ * Argument errors, found before any GPU work: a null src / shape / out, a box
+ * outside the array, a bad src_kind, src_bits, flag or mem, a pitch that is not
+ * finite and positive: CTG_ERR_ARG.  A box of 2^32 voxels or more, or an axis of
+ * the box of 32768 or more: CTG_ERR_UNSUPPORTED.  An empty box writes nothing
+ * (info is zeroed) and succeeds.  The call uses call-sized buffers only: a
+ * CTG_DEFER_STATS handle of the same device stays valid across it.
+ * ctg_last_timings of a profiled call: [0] x pass, [1] y pass, [2] z pass,
+ * [6] total.
+ */
+#define CTG_EDT_SRC_NONZERO 0
+#define CTG_EDT_SRC_GREATER 1
+#define CTG_EDT_SRC_EQUAL 2
+#define CTG_EDT_TO_BACKGROUND 1
+#define CTG_EDT_2D 2
+#define CTG_EDT_OUT_D2 4
+int ctg_distance_transform(const void* src, int src_kind, int src_bits, const int64_t* shape, const int64_t* begin,
+                           const int64_t* end, double threshold, uint64_t label, const double* pitch, int flags,
+                           void* out, int mem, void* stream, uint64_t* info);
 
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
