@@ -1209,13 +1209,15 @@ def threshold_components(data, threshold, mode='greater', mask=None, normalize=T
     return out, int(n.value)
 
 
-def merge_assignments(pairs, n_labels, stream=None):
+def merge_assignments(pairs, n_labels, stream=None, out=None):
     """ctg_merge_assignments: the union-find over the ids 0 .. n_labels - 1 with
     the (n, 2) ``pairs`` united -> (table, max_id): table[0] = 0, every other
     id maps to 1 + the rank of its set's smallest member (merge_assignments.py:
     125-132, the consecutive table).  ``pairs``: a numpy array (the table comes
     back as a uint64 array) or a contiguous 64-bit integer CUDA tensor (an int64
-    tensor).  A pair member that is 0 or not below ``n_labels`` raises."""
+    tensor; ``out`` to write into an existing array of the same kind with
+    n_labels 64-bit integers).  A pair member that is 0 or not below
+    ``n_labels`` raises."""
     on_dev = _is_torch(pairs)
     if on_dev:
         if not (pairs.is_cuda and pairs.is_contiguous()) or pairs.element_size() != 8 or pairs.is_floating_point():
@@ -1231,14 +1233,23 @@ def merge_assignments(pairs, n_labels, stream=None):
     n_labels = int(n_labels)
     if n_labels >= 1 << 32:
         raise ValueError('n_labels must stay below 2^32, got %d' % n_labels)
+    if out is not None:
+        if _is_torch(out) != on_dev:
+            raise ValueError('out must be of the same kind as pairs (numpy array or CUDA tensor)')
+        if on_dev:
+            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
+        else:
+            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
+        if not ok or tuple(out.shape) != (n_labels,):
+            raise ValueError('out must be a contiguous 64-bit integer array of n_labels = %d entries' % n_labels)
     if on_dev:
         import torch
-        table = torch.empty(n_labels, dtype=torch.int64, device=pairs.device)
+        table = torch.empty(n_labels, dtype=torch.int64, device=pairs.device) if out is None else out
     else:
         if pairs.dtype.kind == 'i' and pairs.size and int(pairs.min()) < 0:
             raise ValueError('pairs holds negative values')
         pairs = np.ascontiguousarray(pairs, dtype=np.uint64)
-        table = np.empty(n_labels, dtype=np.uint64)
+        table = np.empty(n_labels, dtype=np.uint64) if out is None else out
     lib = L.load()
     L.init_device()
     if stream is None:

@@ -83,6 +83,44 @@ def merge_table(pairs, n_labels):
     return table, int(table.max()) if n_labels else 0
 
 
+def merge_table_fast(pairs, n_labels):
+    """merge_table for millions of ids: scipy's connected components of the pair
+    graph give the sets; each id maps to the rank of its set's smallest member
+    ({0} is the set of rank 0, so the others count from 1).
+    tests/test_cc_host.py asserts it equal to merge_table."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    graph = coo_matrix((np.ones(len(pairs), dtype=np.int8), (pairs[:, 0], pairs[:, 1])), shape=(n_labels, n_labels))
+    n_sets, which = connected_components(graph, directed=False)
+    smallest = np.full(n_sets, n_labels, dtype=np.int64)
+    np.minimum.at(smallest, which, np.arange(n_labels, dtype=np.int64))
+    rank = np.empty(n_sets, dtype=np.int64)
+    rank[np.argsort(smallest)] = np.arange(n_sets)
+    table = rank[which].astype(np.uint64)
+    return table, int(table.max()) if n_labels else 0
+
+
+# The caps past which a loop of ctg_cc.hip takes a second step or turn, mirrored here once;
+# tests/test_cc_host.py (test_cap_mirrors) pins each against the plan function or the launch's own text.
+SEG = 2048               # csrc/ctg_plan.h: CC_SEG, nodes a numbering segment (cc_segments)
+SCAN_STEP = 1024         # csrc/ctg_cc.hip: k_uf_scan, segments a step of its one workgroup (`base += 1024`)
+RANGE_ROWS = 4 * 2048    # csrc/ctg_cc.hip: launch_cc_range, 2048 workgroups of 4 waves, a row a wave and turn
+BIG = (129, 128, 128)    # 2 113 536 voxels: 1032 segments (two scan steps), 16512 rows (three range turns), 288 tiles
+
+
+def scan_steps(nodes):
+    """Steps of k_uf_scan's loop over the numbering segments of ``nodes`` nodes."""
+    return -(-(-(-nodes // SEG)) // SCAN_STEP)
+
+
+def comb(shape=BIG):
+    """The serpentine over the whole box: one path along x on every other row
+    of every other plane -- it crosses every x seam on every row it takes and
+    climbs through every y and z tile border."""
+    return serpentine(shape)
+
+
 def first_occurrence(labels):
     """The labelling renumbered 1 .. N by first occurrence in raster order, 0 kept."""
     flat = np.asarray(labels).ravel()

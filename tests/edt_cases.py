@@ -24,6 +24,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 LDS_LINE = 32   # csrc/ctg_plan.h: EDT_LDS_LINE (test_edt_host.py checks the plan function at it)
+# The caps past which a kernel's grid-stride loop takes a second turn, mirrored here once;
+# test_edt_host.py (test_cap_mirrors) pins each against the plan functions through tools/edt_check.cpp.
+X_WAVES = 4             # csrc/ctg_plan.h: EDT_X_WAVES, rows a workgroup of k_edt_x takes a turn
+X_MAX_GRID = 8192       # csrc/ctg_plan.h: EDT_X_MAX_GRID, the most workgroups of k_edt_x
+LINE_MAX_GRID = 8192    # csrc/ctg_plan.h: EDT_LINE_MAX_GRID, the most workgroups of k_edt_line
+FOLD_THREADS = 256      # csrc/ctg_edt.hip: k_edt_fold's one workgroup (`i += 256`), a partial per k_edt_line workgroup
+ROW_TOP = 4096          # csrc/ctg_edt.h: voxels under one top ("super") word of a row, 64 words x 64 bits
 
 # the smallest shapes at which each thing can go wrong: one voxel; one row of three ballot words with a ragged
 # tail; single columns; one past the tile and wave multiples on every axis; a y line and a z line just past the
@@ -31,6 +38,36 @@ LDS_LINE = 32   # csrc/ctg_plan.h: EDT_LDS_LINE (test_edt_host.py checks the pla
 SHAPES = [(1, 1, 1), (1, 1, 130), (1, 70, 1), (70, 1, 1), (17, 9, 65), (33, 17, 129),
           (3, LDS_LINE + 1, 66), (LDS_LINE + 1, 3, 66)]
 PITCHES = [None, (40, 4, 4), (10, 1, 3), (0.025, 0.01, 0.01), (1.7, 0.3, 1.1)]
+
+
+# the shapes that drive the grid-stride loops of k_edt_x and k_edt_line past their first turn (see the functions
+# below for which loop of which pass)
+TURN_SHAPES = [(8193, 33, 3), (33, 8193, 3), (8193, 2, 3), (2, 8193, 3)]
+TURN_PATTERNS = ['random_0.002', 'random_0.02', 'random_0.3', 'none', 'all', 'last_slice', 'plane_z']
+TURN_PITCHES = [None, (10, 1, 3), (1.7, 0.3, 1.1)]
+
+
+def x_turns(shape):
+    """Turns of k_edt_x's `for g += gridDim.x` loop: groups of X_WAVES rows over the grid."""
+    groups = -(-shape[0] * shape[1] // X_WAVES)
+    return groups / min(groups, X_MAX_GRID)
+
+
+def line_pass(shape, axis, two_d=False):
+    """(runs, lds, groups, grid) of k_edt_line along ``axis`` (1: y, 0: z), as
+    csrc/ctg_plan.h plans it (edt_passes, edt_line_plan; the grid before any
+    shrinking to EDT_STACK_BYTES, which test_edt_host.py checks stays out of play)."""
+    nz, ny, nx = shape
+    z = not two_d and nz > 1
+    runs = z if axis == 0 else not (z and ny == 1)
+    groups = (nz if axis == 1 else ny) * -(-nx // 64)
+    return runs, shape[axis] <= LDS_LINE, groups, min(groups, LINE_MAX_GRID)
+
+
+def final_partials(shape, two_d=False):
+    """Partials k_edt_fold reads: one per workgroup of the call's last pass."""
+    z = line_pass(shape, 0, two_d)
+    return z[3] if z[0] else line_pass(shape, 1, two_d)[3]
 
 
 def is_exact(pitch):
@@ -89,6 +126,30 @@ def via_scipy(seeds, pitch=None, two_d=False):
                                          return_indices=True)
         g = np.indices(s.shape)
         out[dom] = d2_of(np.abs(g[0] - idx[0]), np.abs(g[1] - idx[1]), np.abs(g[2] - idx[2]), pitch)
+    return out
+
+
+def via_scipy_2d(seeds, pitch=None):
+    """via_scipy(two_d=True) in one scipy call, for boxes of thousands of slices:
+    a z pitch so large that a seed of another slice never wins -- 2^40 times the
+    slice's diagonal, so a step in z outweighs any in-slice distance by 2^80 and
+    no rounding of scipy's own arithmetic can change a comparison between two
+    seeds of one slice, whose z terms are both exactly 0 -- names the nearest
+    seed of the slice wherever the slice has one; D2 is evaluated on the
+    in-slice offsets.  test_edt_host.py asserts it equal to via_scipy."""
+    from scipy import ndimage as ndi
+    seeds = np.asarray(seeds, dtype=bool)
+    p = pitch3(pitch)
+    far = float(np.hypot(seeds.shape[1] * p[1], seeds.shape[2] * p[2]) * 2.0 ** 40)
+    has = seeds.any(axis=(1, 2))
+    out = np.full(seeds.shape, diag2(seeds.shape, pitch, True), dtype=np.float64)
+    if has.any():
+        idx = ndi.distance_transform_edt(~seeds, sampling=(far, p[1], p[2]), return_distances=False,
+                                         return_indices=True)
+        g = np.indices(seeds.shape)
+        d2 = d2_of(np.zeros_like(g[1]), np.abs(g[1] - idx[1]), np.abs(g[2] - idx[2]), pitch)
+        assert np.array_equal(idx[0][has], g[0][has])
+        out[has] = d2[has]
     return out
 
 
@@ -169,6 +230,168 @@ def case(shape, name, pitch, two_d=False):
 
 def pattern_names(shape):
     return list(patterns(shape))
+
+
+# --------------------------------------------------------------------------- past the first turn
+def turn_pattern_names(shape):
+    """TURN_PATTERNS and the far corner seed: the arg-max is then voxel 0."""
+    return TURN_PATTERNS + ['corner_%d_%d_%d' % tuple(n - 1 for n in shape)]
+
+
+def turn_case(shape, name, pitch, two_d=False):
+    """(seeds, D2) of a pattern of a TURN_SHAPES box; not kept (6.5 MB a case)."""
+    seeds = patterns(shape)[name]
+    return seeds, (via_scipy_2d(seeds, pitch) if two_d else via_scipy(seeds, pitch, False))
+
+
+# --------------------------------------------------------------------------- long rows
+LONG_ROWS = [4097, 8193, 32767]
+
+
+def row_seed_sets(nx):
+    """Seed positions of a row of nx > ROW_TOP voxels: the row's two ends, the
+    two sides of the first top-word border, the last bit of the first word and
+    the first bit of the last full one, one seed in the second top word (or,
+    where the row ends before it, at its image in the first), the middle, five
+    random ones."""
+    rng = np.random.default_rng(nx)
+    sets = [[0], [nx - 1], [0, nx - 1], [ROW_TOP - 1, ROW_TOP], [63, nx - 64], [4160 % nx], [nx // 2],
+            sorted(rng.choice(nx, size=5, replace=False).tolist())]
+    return sets
+
+
+def long_row_cases(nx):
+    """[(seeds, D2)]: two (3,2,nx) boxes with a different seed set in each row
+    (the eight sets, the second box in another order) and the plain (1,1,nx)
+    row with one seed in the second top word's range or its image.  The oracle
+    knows each row's |dx| = min |x - seed| and takes the minimum over the rows
+    of |dx|^2 + dy^2 + dz^2 (unit pitch: every term exact)."""
+    sets = row_seed_sets(nx)
+    x = np.arange(nx)
+    out = []
+    for shape, order in (((3, 2, nx), [0, 1, 2, 3, 4, 5]), ((3, 2, nx), [7, 6, 3, 5, 4, 1]), ((1, 1, nx), [5])):
+        seeds = np.zeros(shape, dtype=bool)
+        rowd = np.empty(shape, dtype=np.float64)
+        for r, k in enumerate(order):
+            z, y = divmod(r, shape[1])
+            seeds[z, y, sets[k]] = True
+            rowd[z, y] = np.abs(x[:, None] - np.array(sets[k])[None, :]).min(axis=1)
+        d2 = np.full(shape, np.inf)
+        for z in range(shape[0]):
+            for y in range(shape[1]):
+                for zz in range(shape[0]):
+                    for yy in range(shape[1]):
+                        d2[z, y] = np.minimum(d2[z, y], rowd[zz, yy] ** 2 + float((y - yy) ** 2 + (z - zz) ** 2))
+        out.append((seeds, d2))
+    return out
+
+
+# --------------------------------------------------------------------------- deep stacks
+DEEP_SHAPES = [(4099, 1, 3), (1, 4099, 3), (300, 2, 70)]
+DEEP_PITCHES = [None, (3, 1000, 7)]
+DEEP_PATTERNS = ['diagonal', 'random_0.3']
+
+
+# --------------------------------------------------------------------------- one seed: the D2 expression itself
+SINGLE_SHAPES = [(17, 9, 65), (3, 33, 66)]
+SINGLE_PITCHES = [(0.025, 0.01, 0.01), (1.7, 0.3, 1.1)]
+
+
+def corner_names(shape):
+    return [n for n in pattern_names(shape) if n.startswith('corner_')]
+
+
+def one_per_slice(shape):
+    """One seed in every slice, at another (y, x) in each."""
+    nz, ny, nx = shape
+    s = np.zeros(shape, dtype=bool)
+    z = np.arange(nz)
+    s[z, (7 * z + 3) % ny, (13 * z + 5) % nx] = True
+    return s
+
+
+def single_seed_d2(seeds, pitch, two_d=False):
+    """D2 of a box whose every domain holds exactly one seed: the contract's
+    expression on the offsets to it -- nothing to choose between."""
+    seeds = np.asarray(seeds, dtype=bool)
+    out = np.empty(seeds.shape, dtype=np.float64)
+    for dom in _domains(seeds, two_d):
+        s = seeds[dom]
+        (q,) = np.argwhere(s)
+        g = np.indices(s.shape)
+        out[dom] = d2_of(np.abs(g[0] - q[0]), np.abs(g[1] - q[1]), np.abs(g[2] - q[2]), pitch)
+    return out
+
+
+def check_single_seed(seeds, pitch, two_d, dist, info, d2=None):
+    """The answer for one seed a domain, bit for bit, whatever the pitch:
+    ``d2`` (the call's squared=True result, where the caller has it) equals
+    d2_of as float64 bit patterns, ``dist`` equals float32(sqrt(that)) and
+    ``info`` names the first voxel of the largest D2 and that D2 exactly."""
+    want = single_seed_d2(seeds, pitch, two_d)
+    if d2 is not None:
+        assert d2.dtype == np.float64 and d2.shape == want.shape
+        np.testing.assert_array_equal(d2.view(np.uint64), want.view(np.uint64))
+    assert dist.dtype == np.float32 and dist.shape == want.shape
+    np.testing.assert_array_equal(dist.view(np.uint32), np.sqrt(want).astype(np.float32).view(np.uint32))
+    k = int(np.argmax(want))
+    assert tuple(info) == (int(seeds.sum()), 0, k, float(want.ravel()[k]))
+    assert info[3] == want.max()
+
+
+def contracted_d2(seeds, pitch, two_d=False):
+    """What the D2 of single_seed_d2 would be were the sum contracted into fused
+    multiply-adds, in the two ways a compiler can do it: fma(c,c, fma(b,b, a*a))
+    and fma(c,c, fma(a,a, b*b)) -- by exact rationals rounded once a step."""
+    from fractions import Fraction
+    seeds = np.asarray(seeds, dtype=bool)
+    p = pitch3(pitch)
+    outs = [np.empty(seeds.shape, dtype=np.float64) for _ in range(2)]
+    for dom in _domains(seeds, two_d):
+        s = seeds[dom]
+        (q,) = np.argwhere(s)
+        g = np.indices(s.shape)
+        off = [np.abs(g[k] - q[k]).astype(np.float64) * p[k] for k in range(3)]     # (one rounding each, as in d2_of)
+        memo = {}
+        res = [np.empty(s.shape), np.empty(s.shape)]
+        for i in np.ndindex(s.shape):
+            a, b, c = (float(off[k][i]) for k in range(3))
+            if (a, b, c) not in memo:
+                fa, fb, fc = Fraction(a), Fraction(b), Fraction(c)
+                first = float(fb * fb + Fraction(a * a))
+                second = float(fa * fa + Fraction(b * b))
+                memo[a, b, c] = (float(fc * fc + Fraction(first)), float(fc * fc + Fraction(second)))
+            res[0][i], res[1][i] = memo[a, b, c]
+        outs[0][dom], outs[1][dom] = res
+    return outs
+
+
+# --------------------------------------------------------------------------- integer pitches up to the bound
+BOUND = 2.0 ** 53
+BOUND_SHAPES = [(1, 200, 3), (200, 1, 3), (40, 40, 5), (9, 130, 2)]
+BOUND_DENSITIES = [0.01, 0.1, 0.5]
+
+
+def bound_pitches(shape):
+    """Three fixed integer pitches and the largest isotropic one: floor(sqrt(2^53))
+    = 94906265 over the longest axis where that keeps the box's diagonal below
+    2^53, else the largest integer that does (the other axes count too)."""
+    import math
+    n2 = sum(int(n) ** 2 for n in shape)
+    p = min(94906265 // max(shape), math.isqrt((2 ** 53 - 1) // n2))     # p^2 n2 <= 2^53 - 1
+    return [(262145, 262147, 3), (3, 262147, 262145), (1, 1, 333333), (p, p, p)]
+
+
+@functools.lru_cache(maxsize=None)
+def bound_case(shape, pitch, density):
+    """(seeds, D2) by brute force, the box's diagonal below 2^53 (asserted by the tests)."""
+    rng = np.random.default_rng([shape[0], shape[1], shape[2], int(density * 100)])
+    seeds = rng.random(shape) < density
+    seeds[tuple(rng.integers(0, n) for n in shape)] = True
+    d2 = brute(seeds, pitch)
+    seeds.setflags(write=False)
+    d2.setflags(write=False)
+    return seeds, d2
 
 
 def golden():

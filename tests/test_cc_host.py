@@ -73,6 +73,25 @@ def test_grid(cc):
     assert got[5] == [1, 1, 3, 2, 0, 0, 1]
 
 
+def test_cap_mirrors(cc):
+    """The caps mirrored in tests/cc_cases.py: CC_SEG through the grid's segment
+    count (cc_segments), the scan step and the range launch through the text of
+    csrc/ctg_cc.hip, which holds them as literals.  A change fails here instead
+    of taking the second step or turn out of tests/test_gpu_cc.py."""
+    got = [[int(t) for t in line.split()] for line in
+           cc(['grid 1 1 %d' % C.SEG, 'grid 1 1 %d' % (C.SEG + 1), 'grid 128 128 128', 'grid %d %d %d' % C.BIG])]
+    assert [g[6] for g in got] == [1, 2, C.SCAN_STEP, 1032]
+    assert got[3][0] * got[3][1] * got[3][2] == 9 * 16 * 2 == 288
+    assert C.scan_steps(C.SEG * C.SCAN_STEP) == 1 and C.scan_steps(C.SEG * C.SCAN_STEP + 1) == 2
+    assert C.scan_steps(int(np.prod(C.BIG))) == 2 and C.BIG[0] * C.BIG[1] > 2 * C.RANGE_ROWS
+    with open(os.path.join(ROOT, 'cluster_tools_amd', 'csrc', 'ctg_cc.hip')) as f:
+        src = f.read()
+    scan = src[src.index('void k_uf_scan('):src.index('uf_id(')]
+    assert '__launch_bounds__(%d) void k_uf_scan(' % C.SCAN_STEP in src
+    assert 'base += %d)' % C.SCAN_STEP in scan and 'k_uf_scan, dim3(1), dim3(%d)' % C.SCAN_STEP in src
+    assert 'std::min<int64_t>((rows + 3) / 4, %d)' % (C.RANGE_ROWS // 4) in src
+
+
 # --------------------------------------------------------------------------- the labelling
 SHAPES = [(1, 1, 1), (1, 1, 130), (16, 8, 64), (17, 9, 65), (5, 9, 70), (33, 17, 129)]
 
@@ -150,6 +169,9 @@ def test_host_merge_against_a_dict(cc):
         want, max_id = C.merge_table(pairs, n_labels)
         assert int(t[0]) == max_id
         assert_array_equal(np.array(t[1:], dtype=np.uint64), want)
+        fast, fast_max = C.merge_table_fast(pairs, n_labels)               # the oracle of the large cases
+        assert fast.dtype == want.dtype and fast_max == max_id
+        assert_array_equal(fast, want)
     t = host_merge(cc, cases[-1], n_labels)
     assert_array_equal(np.array(t[1:], dtype=np.uint64), np.arange(n_labels, dtype=np.uint64))   # no pairs: the identity
 
@@ -219,3 +241,6 @@ def test_argument_rules(monkeypatch):
         rag.merge_assignments(np.array([[1, -2]]), 10)
     with pytest.raises(ValueError, match='2\\^32'):
         rag.merge_assignments(np.zeros((0, 2), dtype=np.uint64), 1 << 32)
+    for bad in (np.zeros(9, dtype=np.uint64), np.zeros(10, dtype=np.uint32), np.zeros((10, 1), dtype=np.uint64)):
+        with pytest.raises(ValueError, match='out must'):
+            rag.merge_assignments(np.array([[1, 2]]), 10, out=bad)

@@ -72,6 +72,61 @@ def test_passes(edt):
     assert got == ['1 1', '1 0', '1 0', '0 1', '1 0', '1 0', '0 1']
 
 
+def test_cap_mirrors(edt):
+    """The caps mirrored in tests/edt_cases.py against the plan functions: a
+    change of EDT_X_WAVES, EDT_X_MAX_GRID or EDT_LINE_MAX_GRID fails here, not
+    by quietly taking the second turn out of the GPU tests."""
+    W, G, LG = E.X_WAVES, E.X_MAX_GRID, E.LINE_MAX_GRID
+    rows = [1, W, W + 1, W * (G - 1), W * (G - 1) + 1, W * G, W * G + 1, 100 * W * G]
+    got = [int(t) for t in edt(['xgrid %d' % r for r in rows])]
+    assert got == [1, 1, 2, G - 1, G, G, G, G]
+    L = E.LDS_LINE
+    got = [[int(t) for t in line.split()] for line in
+           edt(['plan 2 %d 64' % LG, 'plan 2 %d 64' % (LG + 1), 'plan 2 %d 65' % LG,
+                'plan %d %d 64' % (L + 1, LG), 'plan %d %d 64' % (L + 1, LG + 1)])]
+    assert got[0] == [1, LG, LG, 0] and got[1] == [1, LG + 1, LG, 0] and got[2] == [1, 2 * LG, LG, 0]
+    assert got[3] == [0, LG, LG, LG * (L + 1) * 64 * 8] and got[4] == [0, LG + 1, LG, LG * (L + 1) * 64 * 8]
+    with open(os.path.join(ROOT, 'cluster_tools_amd', 'csrc', 'ctg_edt.hip')) as f:
+        src = f.read()
+    fold = src[src.index('void k_edt_fold('):src.index('void launch_line(')]
+    assert 'i += %d)' % E.FOLD_THREADS in fold and 'dim3(%d), 0, s, part, n, info' % E.FOLD_THREADS in src
+
+
+@pytest.mark.parametrize('shape', E.TURN_SHAPES, ids=lambda s: '%dx%dx%d' % s)
+def test_turn_shapes_cross_the_caps(edt, shape):
+    """E.line_pass is the plan the library makes for the TURN_SHAPES boxes (no
+    grid shrinks to fit the stack buffer, which stays under 150 MB), and each
+    box takes the loops it is there for past their first turn."""
+    nz, ny, nx = shape
+    for two_d in (False, True):
+        y, z = [bool(int(t)) for t in edt(['passes %d %d %d %d' % (shape + (int(two_d),))])[0].split()]
+        for axis, runs in ((1, y), (0, z)):
+            want = E.line_pass(shape, axis, two_d)
+            assert want[0] == runs
+            lds, groups, grid, nbytes = [int(t) for t in
+                                         edt(['plan %d %d %d' % (shape[axis], nz if axis == 1 else ny, nx)])[0].split()]
+            assert (bool(lds), groups, grid) == want[1:]
+            assert nbytes == (0 if lds else grid * shape[axis] * 64 * 8) <= 150 << 20
+    assert int(edt(['xgrid %d' % (nz * ny)])[0]) == min(-(-nz * ny // E.X_WAVES), E.X_MAX_GRID)
+    crossed = {(8193, 33, 3): [E.x_turns(shape) > 8, E.line_pass(shape, 1)[1:] == (False, 8193, 8192)],
+               (33, 8193, 3): [E.x_turns(shape) > 8, E.line_pass(shape, 0)[1:] == (False, 8193, 8192),
+                               E.final_partials(shape) > E.FOLD_THREADS],
+               (8193, 2, 3): [E.line_pass(shape, 1)[1:] == (True, 8193, 8192)],
+               (2, 8193, 3): [E.line_pass(shape, 0)[1:] == (True, 8193, 8192),
+                              E.final_partials(shape) > E.FOLD_THREADS]}[shape]
+    assert all(crossed)
+
+
+def test_two_d_oracle_in_one_call():
+    """via_scipy_2d (one scipy call with a far z pitch) names the seeds via_scipy
+    names slice by slice: equal D2, bit for bit, whatever the pitch."""
+    for shape in ((40, 33, 3), (33, 50, 3), (50, 2, 3), (17, 9, 65)):
+        for name in E.turn_pattern_names(shape) + ['diagonal', 'checkerboard']:
+            for pitch in E.TURN_PITCHES + [(40, 4, 4), (0.025, 0.01, 0.01)]:
+                seeds = E.patterns(shape)[name]
+                np.testing.assert_array_equal(E.via_scipy_2d(seeds, pitch), E.via_scipy(seeds, pitch, True))
+
+
 # --------------------------------------------------------------------------- the transform
 @pytest.mark.parametrize('shape', E.SHAPES, ids=lambda s: '%dx%dx%d' % s)
 def test_host_transform_matches_oracle(edt, shape):
@@ -105,6 +160,91 @@ def test_golden(edt):
         np.testing.assert_array_equal(dist, np.sqrt(c['d2']).astype(np.float32))
         assert list(info) == c['info']
         E.check(dist, info, seeds, pitch, c['two_d'], c['d2'])
+
+
+# --------------------------------------------------------------------------- long rows, deep stacks, the bound
+def ask_cases(edt, cases):
+    """[(seeds, pitch, two_d)] -> [(dist, info)] in one run of the tool."""
+    lines = edt([query(seeds, pitch, two_d) for seeds, pitch, two_d in cases])
+    return [parse(line, seeds.shape) for line, (seeds, _, _) in zip(lines, cases)]
+
+
+@pytest.mark.parametrize('nx', E.LONG_ROWS)
+def test_long_rows(edt, nx):
+    """edt_prev_seed / edt_next_seed (csrc/ctg_edt.h) past one top word, rows of
+    more than E.ROW_TOP = 4096 voxels: the walks over the top words in both
+    directions and the (w & 63) == 0 / == 63 edges, seeds at the row's ends, on
+    both sides of a top-word border and in the second top word.  The oracle is
+    min |x - seed| per row, combined across the rows by brute force; scipy
+    agrees with it."""
+    assert nx > E.ROW_TOP
+    cases = E.long_row_cases(nx)
+    for (seeds, d2), (dist, info) in zip(cases, ask_cases(edt, [(s, None, False) for s, _ in cases])):
+        np.testing.assert_array_equal(d2, E.via_scipy(seeds))
+        E.check(dist, info, seeds, None, False, d2)
+
+
+@pytest.mark.parametrize('shape', E.DEEP_SHAPES, ids=lambda s: '%dx%dx%d' % s)
+def test_deep_stacks(edt, shape):
+    """Lines of 4099 and 300 positions whose envelope keeps every parabola
+    ('diagonal') or pops often ('random_0.3'): stacks thousands of entries deep."""
+    cases = [(name, pitch) for name in E.DEEP_PATTERNS for pitch in E.DEEP_PITCHES]
+    answers = ask_cases(edt, [(E.case(shape, name, pitch)[0], pitch, False) for name, pitch in cases])
+    for (name, pitch), (dist, info) in zip(cases, answers):
+        seeds, d2 = E.case(shape, name, pitch)
+        E.check(dist, info, seeds, pitch, False, d2)
+
+
+@pytest.mark.parametrize('shape', E.BOUND_SHAPES, ids=lambda s: '%dx%dx%d' % s)
+def test_integer_pitches_up_to_the_bound(edt, shape):
+    """Integer pitches up to (nz pz)^2 + (ny py)^2 + (nx px)^2 < 2^53, where the
+    contract still promises bit-exactness and edt_takeover's floor is argued to
+    be the true one: against brute force (scipy's own arithmetic is no oracle
+    here).  The bound is asserted of every case -- a condition on the inputs."""
+    cases = [(pitch, density) for pitch in E.bound_pitches(shape) for density in E.BOUND_DENSITIES]
+    assert E.diag2(shape, cases[-1][0], False) > 0.97 * E.BOUND or cases[-1][0][0] == 94906265 // max(shape)
+    for pitch, _ in cases:
+        assert E.is_exact(pitch) and E.diag2(shape, pitch, False) < E.BOUND
+    answers = ask_cases(edt, [(E.bound_case(shape, pitch, density)[0], pitch, False) for pitch, density in cases])
+    for (pitch, density), (dist, info) in zip(cases, answers):
+        seeds, d2 = E.bound_case(shape, pitch, density)
+        E.check(dist, info, seeds, pitch, False, d2)
+
+
+# --------------------------------------------------------------------------- the D2 expression
+def single_seed_cases():
+    out = [(shape, name, E.patterns(shape)[name], pitch, False) for shape in E.SINGLE_SHAPES
+           for name in E.corner_names(shape) for pitch in E.SINGLE_PITCHES]
+    out += [(shape, 'one_per_slice', E.one_per_slice(shape), pitch, True) for shape in E.SINGLE_SHAPES
+            for pitch in E.SINGLE_PITCHES]
+    return out
+
+
+def test_single_seed_pins_the_expression(edt):
+    """One seed a domain: the host rendering gives float32(sqrt(D2)) and the
+    largest D2 of the contract's expression bit for bit under non-integer
+    pitches (E.check_single_seed; the GPU test also compares D2 itself)."""
+    cases = single_seed_cases()
+    assert len(cases) == 2 * 8 * 2 + 2 * 2
+    for (shape, name, seeds, pitch, two_d), (dist, info) in \
+            zip(cases, ask_cases(edt, [(seeds, pitch, two_d) for _, _, seeds, pitch, two_d in cases])):
+        E.check_single_seed(seeds, pitch, two_d, dist, info)
+
+
+def test_single_seed_cases_would_notice_a_contraction():
+    """Every single-seed case has voxels whose D2 differs when the sum is
+    contracted into fused multiply-adds, either way round: without that the
+    case would pin neither -ffp-contract=off nor the order of the additions.
+    A reordered sum (the x term first) differs somewhere too."""
+    for shape, name, seeds, pitch, two_d in single_seed_cases():
+        want = E.single_seed_d2(seeds, pitch, two_d)
+        for other in E.contracted_d2(seeds, pitch, two_d):
+            assert (other != want).sum() >= 10, (shape, name, pitch)
+        g = np.indices(shape)
+        p = E.pitch3(pitch)
+        far = np.abs(g - np.array([n - 1 for n in shape]).reshape(3, 1, 1, 1))      # reordering: any offsets will do
+        a, b, c = (far[k].astype(np.float64) * p[k] for k in range(3))
+        assert ((c * c + b * b + a * a) != (a * a + b * b + c * c)).any()
 
 
 # --------------------------------------------------------------------------- the oracle against itself

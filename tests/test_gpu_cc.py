@@ -285,6 +285,9 @@ def test_merge_assignments(gpu, merge_cases, name):
     n, cases = merge_cases
     pairs = cases[name].astype(U64)
     want, max_id = C.merge_table(pairs, n)
+    fast, fast_max = C.merge_table_fast(pairs, n)          # the oracle of the cases past one scan step
+    assert fast_max == max_id
+    assert_array_equal(fast, want)
     got, m = rag.merge_assignments(pairs, n)
     assert got.dtype == U64 and m == max_id
     assert_array_equal(got, want)
@@ -316,6 +319,143 @@ def test_merge_assignments_device(gpu, merge_cases):
     got, m = rag.merge_assignments(torch.from_numpy(pairs).cuda(), n)
     assert got.is_cuda and got.dtype == torch.int64 and m == max_id
     assert_array_equal(got.cpu().numpy().view(U64), want)
+
+
+# --------------------------------------------------------------------------- past one scan step, one range turn
+def scipy_label(fg, c):
+    from scipy import ndimage as ndi
+    lab, n = ndi.label(fg, structure=ndi.generate_binary_structure(3, c))
+    return lab.astype(U64), int(n)
+
+
+def label_dev(data, threshold, c, normalize, mode='greater'):
+    """threshold_components of a device volume into a device ``out`` prefilled
+    with -1 (no voxel may keep what an earlier call left in a pooled buffer)."""
+    import torch
+    out = torch.full(tuple(data.shape), -1, dtype=torch.int64, device='cuda')
+    got, n = rag.threshold_components(torch.from_numpy(data).cuda(), threshold, mode=mode, normalize=normalize,
+                                      connectivity=c, out=out)
+    assert got is out
+    return out.cpu().numpy().view(U64), n
+
+
+def big_box_asserted():
+    """C.BIG takes k_uf_scan past one step and k_cc_range past two turns
+    (tests/test_cc_host.py pins the mirrors these come from)."""
+    assert C.scan_steps(int(np.prod(C.BIG))) >= 2 and C.BIG[0] * C.BIG[1] > 2 * C.RANGE_ROWS
+
+
+def merge_pair_sets(n):
+    """name -> pairs over the ids 1 .. n - 1, n >= 2^21: nothing; 10^6 random
+    pairs; chains (k, k + 2^21) and (k, k + 2048) across the scan step's and the
+    segments' borders; the first id with the last."""
+    rng = np.random.default_rng(n)
+    step = C.SEG * C.SCAN_STEP
+    far = np.arange(1, max(n - step, 1), 3)
+    near = np.arange(1, n - C.SEG, 5)
+    near = near[(near // 7) % 3 != 0]                      # (chains of a few links, broken here and there)
+    return dict(none=np.zeros((0, 2), dtype=np.int64),
+                random=rng.integers(1, n, size=(10 ** 6, 2)),
+                chains=rng.permutation(np.concatenate([np.stack([far, far + step], 1),
+                                                       np.stack([near, near + C.SEG], 1)])),
+                ends=np.array([[1, n - 1]]))
+
+
+@pytest.mark.parametrize('n', [1 << 21, (1 << 21) + 1, (1 << 21) + 2049, 3 * (1 << 21) + 5])
+def test_merge_assignments_past_one_scan_step(gpu, n):
+    """k_uf_scan (csrc/ctg_cc.hip) past its first step of 1024 numbering
+    segments of CC_SEG = 2048 ids: `carry` and the reuse of `wsum`.  Without
+    pairs every segment holds 2048 roots and the table is the identity, so a slip
+    of the carry shifts everything behind it; the chains tie ids across the
+    step's and the segments' borders.  Host and device pairs, the device table
+    written over -1."""
+    import torch
+    assert C.scan_steps(n + 1) >= 2                        # (2^21 ids fill the first step to its last entry)
+    for name, pairs in merge_pair_sets(n).items():
+        want, max_id = C.merge_table_fast(pairs, n)
+        if name == 'none':
+            assert_array_equal(want, np.arange(n, dtype=U64))
+        if name == 'ends':
+            assert want[n - 1] == 1 and max_id == n - 2
+        got, m = rag.merge_assignments(pairs.astype(U64), n, out=np.full(n, (1 << 64) - 1, dtype=U64))
+        assert m == max_id, name
+        assert_array_equal(got, want)
+        out = torch.full((n,), -1, dtype=torch.int64, device='cuda')
+        got, m = rag.merge_assignments(torch.from_numpy(pairs.astype(np.int64)).cuda(), n, out=out)
+        assert got is out and m == max_id, name
+        assert_array_equal(out.cpu().numpy().view(U64), want)
+
+
+BIG_DENSITIES = {1: (0.2, 0.31, 0.5), 2: (0.08, 0.14, 0.3), 3: (0.05, 0.1, 0.2)}   # below, near, above percolation
+
+
+@pytest.mark.parametrize('c', [1, 2, 3])
+def test_big_box_random_maps(gpu, c):
+    """(129,128,128): 288 tiles, about a thousand seam workgroups on every XCD
+    uniting concurrently (k_cc_seams; the agent-scope argument of ctg_uf.h),
+    1032 numbering segments (k_uf_flatten, k_uf_scan's second step).  Densities
+    below, near and above the site-percolation point of each connectivity
+    (0.3116, 0.137, 0.0976): thousands of components at each, and above it one
+    that spans the box -- chains across hundreds of tile borders.  scipy's
+    numbering exactly (tests/test_cc_host.py judges scipy by oracle_label)."""
+    big_box_asserted()
+    for k, p in enumerate(BIG_DENSITIES[c]):
+        fg = C.random_fg(C.BIG, p, seed=c)
+        want, n = scipy_label(fg, c)
+        assert n > 1000
+        if k == 2:
+            assert np.bincount(want.ravel().astype(np.int64))[1:].max() > 0.1 * fg.sum()
+        got, m = label_dev(as_data(fg), 0.5, c, False)
+        assert m == n
+        assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize('c', [1, 2, 3])
+def test_big_box_comb(gpu, c):
+    """One path through every tile border of (129,128,128), then cut once."""
+    big_box_asserted()
+    fg = C.comb()
+    for cut in (None, (64, 64, 64)):
+        if cut:
+            fg[cut] = False
+        want, n = scipy_label(fg, c)
+        assert n == (2 if cut else 1)
+        got, m = label_dev(as_data(fg), 0.5, c, False)
+        assert m == n
+        assert_array_equal(got, want)
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.uint8])
+def test_big_box_range_past_one_turn(gpu, dtype):
+    """k_cc_range (csrc/ctg_cc.hip) past its first turn of 2048 x 4 = 8192 rows:
+    the box's minimum only in row 0 and its maximum only in the last row, row
+    16511, of the third turn; then swapped; then a NaN in the last row alone,
+    which must give the empty result.  A missed extreme changes the normalised
+    values, and with them the foreground."""
+    big_box_asserted()
+    rng = np.random.default_rng(31)
+    if dtype == np.uint8:
+        base, lo, hi = rng.integers(60, 200, size=C.BIG).astype(np.uint8), 0, 255
+    else:
+        base, lo, hi = (rng.random(C.BIG, dtype=np.float32) * np.float32(0.5) + np.float32(0.25)), -1.0, 2.0
+    for first, last in ((lo, hi), (hi, lo)):
+        data = base.copy()
+        data[0, 0, 77], data[-1, -1, 5] = first, last
+        assert (data == lo).sum() == 1 and (data == hi).sum() == 1
+        fg = C.foreground(data, 0.45, 'greater', True)
+        missed = C.foreground(np.clip(data, base.min(), base.max()), 0.45, 'greater', True)
+        assert (fg != missed).sum() > 1000                  # the extremes matter at this threshold
+        want, n = scipy_label(fg, 1)
+        got, m = label_dev(data, 0.45, 1, True)
+        assert_array_equal(got != 0, fg)
+        assert m == n
+        assert_array_equal(got, want)
+    if dtype == np.float32:
+        data = base.copy()
+        data[-1, -1, 100] = np.nan
+        for mode in ('greater', 'less'):
+            got, m = label_dev(data, 0.45, 3, True, mode=mode)
+            assert m == 0 and not got.any()
 
 
 def test_merge_assignments_refuses_bad_members(gpu):

@@ -55,6 +55,134 @@ def test_corner_seeds_pin_the_square_root(gpu):
     assert len(seen) > 5000
 
 
+# --------------------------------------------------------------------------- past the first grid turn
+def run_dev(seeds, pitch=None, two_d=False, squared=False):
+    """The transform of a device source into a device ``out`` prefilled with -1:
+    a voxel that no turn writes stays negative, whatever an earlier call left in
+    the pool's buffers."""
+    import torch
+    src = torch.from_numpy(np.array(seeds, dtype=np.uint8)).cuda()
+    out = torch.full(tuple(seeds.shape), -1.0, dtype=torch.float64 if squared else torch.float32, device='cuda')
+    got, info = rag.distance_transform(src, pitch=pitch, two_d=two_d, squared=squared, out=out)
+    assert got is out
+    return out.cpu().numpy(), tuple(info)
+
+
+def turns_asserted(shape, two_d):
+    """What the box takes past a first turn, from the mirrors of tests/edt_cases.py
+    (tests/test_edt_host.py pins them against the plan functions)."""
+    y, z = E.line_pass(shape, 1, two_d), E.line_pass(shape, 0, two_d)
+    if shape in ((8193, 33, 3), (33, 8193, 3)):
+        rows = shape[0] * shape[1]                               # k_edt_x: 8.25 turns, one live wave in the last group
+        assert E.x_turns(shape) >= 2 and rows % E.X_WAVES == 1 and rows > 2 * E.X_WAVES * E.X_MAX_GRID
+    if shape == (8193, 33, 3):                                   # y pass: buffer stacks, 8193 groups on 8192 workgroups
+        assert y[0] and not y[1] and y[2] > y[3] == E.LINE_MAX_GRID
+    if shape == (33, 8193, 3) and not two_d:                     # z pass: the same along z
+        assert z[0] and not z[1] and z[2] > z[3] == E.LINE_MAX_GRID
+    if shape == (8193, 2, 3):                                    # y pass: LDS stacks past the cap
+        assert y[0] and y[1] and y[2] > y[3] == E.LINE_MAX_GRID
+    if shape == (2, 8193, 3):                                    # z pass: LDS stacks past the cap
+        assert z[0] and z[1] and z[2] > z[3] == E.LINE_MAX_GRID
+    if (shape, two_d) in (((8193, 33, 3), True), ((33, 8193, 3), False), ((2, 8193, 3), False)):
+        assert E.final_partials(shape, two_d) >= 2 * E.FOLD_THREADS   # k_edt_fold: several partials a thread
+
+
+TURN_CASES = [(shape, pitch, two_d) for shape in E.TURN_SHAPES for two_d in (False, True) for pitch in E.TURN_PITCHES
+              if not two_d or shape in E.TURN_SHAPES[:2]]
+
+
+@pytest.mark.parametrize('shape,pitch,two_d', TURN_CASES,
+                         ids=['%dx%dx%d-%s-%s' % (s + (p, '2d' if t else '3d')) for s, p, t in TURN_CASES])
+def test_turn_shapes(gpu, shape, pitch, two_d):
+    """k_edt_x's and k_edt_line's `for (g = blockIdx.x; g < groups; g += gridDim.x)`
+    past their first turn, and k_edt_fold's `i += 256` (csrc/ctg_edt.hip):
+    boxes of more than EDT_X_WAVES x EDT_X_MAX_GRID = 32768 rows and of more
+    than EDT_LINE_MAX_GRID = 8192 groups of columns with lines of 33 (stacks in
+    the buffer, BufStack.stride = gridDim.x x 64) and of 2 (stacks in LDS) --
+    the LDS seed words rewritten behind three barriers a turn, a ragged last
+    group, k / top / j reset and best / unseeded carried from turn to turn.
+    Every output starts at -1.  In 2-D mode the sparse patterns leave thousands
+    of unseeded slices, info[1] a sum over all workgroups and turns; with the
+    far corner seed the arg-max is voxel 0; with 'all' every partial ties at 0
+    and the first voxel must win."""
+    turns_asserted(shape, two_d)
+    V = shape[0] * shape[1] * shape[2]
+    for name in E.turn_pattern_names(shape):
+        seeds, d2 = E.turn_case(shape, name, pitch, two_d)
+        dist, info = run_dev(seeds, pitch, two_d)
+        try:
+            E.check(dist, info, seeds, pitch, two_d, d2)
+            if name == 'all':
+                assert info == (V, 0, 0, 0.0)
+            if name.startswith('corner') and not two_d:
+                assert info[2] == 0
+            if two_d and name == 'random_0.002' and shape == (8193, 33, 3):
+                assert info[1] > 1000 * shape[1] * shape[2]
+        except AssertionError as err:
+            raise AssertionError('%s: %s' % (name, err)) from None
+
+
+# --------------------------------------------------------------------------- long rows, deep stacks, the bound
+@pytest.mark.parametrize('nx', E.LONG_ROWS)
+def test_long_rows(gpu, nx):
+    """edt_prev_seed / edt_next_seed (csrc/ctg_edt.h) in k_edt_x on rows of more
+    than E.ROW_TOP = 4096 voxels: both walks over the top words and their word
+    edges, a different seed set in each of a workgroup's four waves (their LDS
+    words differ), as tests/test_edt_host.py runs them on the host."""
+    assert nx > E.ROW_TOP
+    for seeds, d2 in E.long_row_cases(nx):
+        dist, info = run_dev(seeds)
+        E.check(dist, info, seeds, None, False, d2)
+
+
+@pytest.mark.parametrize('shape', E.DEEP_SHAPES, ids=lambda s: '%dx%dx%d' % s)
+def test_deep_stacks(gpu, shape):
+    """k_edt_line's buffer stacks thousands of entries deep: lines of 4099 and
+    300 whose envelope keeps every parabola or pops often."""
+    assert max(shape[0], shape[1]) > E.LDS_LINE
+    for name in E.DEEP_PATTERNS:
+        for pitch in E.DEEP_PITCHES:
+            seeds, d2 = E.case(shape, name, pitch)
+            dist, info = run_dev(seeds, pitch)
+            E.check(dist, info, seeds, pitch, False, d2)
+
+
+@pytest.mark.parametrize('shape', E.BOUND_SHAPES, ids=lambda s: '%dx%dx%d' % s)
+def test_integer_pitches_up_to_the_bound(gpu, shape):
+    """Bit-exact against brute force with integer pitches up to the documented
+    bound (nz pz)^2 + (ny py)^2 + (nx px)^2 < 2^53 (include/ctg.h), which is
+    asserted of every case: edt_takeover's floor near the bound."""
+    for pitch in E.bound_pitches(shape):
+        assert E.is_exact(pitch) and E.diag2(shape, pitch, False) < E.BOUND
+        for density in E.BOUND_DENSITIES:
+            seeds, d2 = E.bound_case(shape, pitch, density)
+            dist, info = run_dev(seeds, pitch)
+            E.check(dist, info, seeds, pitch, False, d2)
+            sq, info2 = run_dev(seeds, pitch, squared=True)
+            assert info2 == info
+            assert_array_equal(sq.view(np.uint64), np.asarray(d2).view(np.uint64))
+
+
+# --------------------------------------------------------------------------- the D2 expression
+def test_single_seed_pins_the_expression(gpu):
+    """The test that pins -ffp-contract=off (csrc/Makefile) and the order of the
+    three additions of edt_d2 (csrc/ctg_edt.h): with one seed a domain there is
+    nothing to choose between, so under any pitch D2 is the contract's
+    (dz pz)^2 + (dy py)^2 + (dx px)^2 in float64, added in this order and
+    uncontracted -- compared as bit patterns, with float32(sqrt(D2)) and info's
+    largest D2.  tests/test_edt_host.py shows that each case has voxels that
+    differ under a contraction or another order."""
+    for shape in E.SINGLE_SHAPES:
+        cases = [(E.patterns(shape)[name], False) for name in E.corner_names(shape)] + [(E.one_per_slice(shape), True)]
+        assert len(cases) == 9
+        for seeds, two_d in cases:
+            for pitch in E.SINGLE_PITCHES:
+                d2, info2 = run_dev(seeds, pitch, two_d, squared=True)
+                dist, info = run_dev(seeds, pitch, two_d)
+                assert info2 == info
+                E.check_single_seed(seeds, pitch, two_d, dist, info, d2)
+
+
 # --------------------------------------------------------------------------- 2-D mode
 @pytest.mark.parametrize('shape', [(17, 9, 65), (3, E.LDS_LINE + 1, 66), (1, 70, 1), (70, 1, 1)],
                          ids=lambda s: '%dx%dx%d' % s)

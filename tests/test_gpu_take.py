@@ -11,11 +11,12 @@ import pytest
 from numpy.testing import assert_array_equal
 
 from cluster_tools_amd import _lib, rag, tools
+from tests import take_cases as T
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CHUNK = 4096          # voxels per workgroup (ctg_plan.h: TAKE_CHUNK)
+CHUNK = T.CHUNK       # voxels per workgroup (ctg_plan.h: TAKE_CHUNK)
 U64 = np.uint64
 TOP = (1 << 64) - 1
 
@@ -200,6 +201,84 @@ def test_segments(both):
         check(a, labels, kw, segments=segments, allow_missing=True)
     with pytest.raises(KeyError if a.kind == 'sparse' else IndexError, match=r'%d: .*\(200 voxel' % ((1 << 40) + 1)):
         rag.apply_assignment(a, labels, segments=segments)
+
+
+# --------------------------------------------------------------------------- past the first turn, the slot plans
+def check_dev(a, labels, oracle_kw, segments=None, allow_missing=False):
+    """check() with the labels on the device and a device ``out`` prefilled with
+    -1: a voxel that no workgroup writes keeps it, whatever an earlier call left
+    in a pooled buffer.  With missing labels and no allow_missing the call must
+    raise, naming the smallest label and the count."""
+    import torch
+    want, nz, n_missing, first = oracle(labels, seg_begin=None if segments is None else segments[0],
+                                        seg_off=None if segments is None else segments[1], **oracle_kw)
+    t = torch.from_numpy(labels.view(np.int64 if labels.dtype == U64 else np.int32)).cuda()
+    out = torch.full((labels.size,), -1, dtype=torch.int64, device='cuda')
+    if n_missing and not allow_missing:
+        with pytest.raises(KeyError if a.kind == 'sparse' else IndexError, match=r'^.?%d: .*\(%d voxel' % (first, n_missing)):
+            rag.apply_assignment(a, t, segments=segments, out=out)
+        return
+    got, info = rag.apply_assignment(a, t, segments=segments, allow_missing=allow_missing, out=out)
+    assert got is out
+    assert_array_equal(out.cpu().numpy().view(U64), want)
+    assert_array_equal(info['nonzero'], nz)
+    assert (info['n_missing'], info['first_missing']) == (n_missing, first)
+
+
+@pytest.mark.parametrize('n', [(1 << 20) + 1, 3 * (1 << 20) + 7])
+def test_dense_max_past_one_turn(gpu, n):
+    """k_take_max (csrc/ctg_take.hip) past its first turn of 4096 x 256 = 2^20
+    entries: the table's only maximum at the last entry, at entry 2^20 (the
+    first of the second turn) and at entry 0; one lookup through each table."""
+    assert T.max_turns(n) >= 2 and T.max_turns(1 << 20) == 1
+    base = value_of(np.arange(n))                          # (below 2^40)
+    labels = np.random.default_rng(n).integers(0, n, size=3 * CHUNK + 5).astype(U64)
+    for at in (n - 1, 1 << 20, 0):
+        table = base.copy()
+        table[at] = U64((1 << 41) + at)
+        labels[7] = at
+        a = rag.assignment_dense(table)
+        assert (a.n, a.max_value, a.kind) == (n, (1 << 41) + at, 'dense')
+        check_dev(a, labels, dict(table=table))
+        a.free()
+
+
+def segment_plans():
+    """name -> (lengths, expected count slots): 4097 segments, one count slot
+    each; 4096, 64 slots each; three of which one holds 70 chunks, so that its
+    workgroups wrap around the 64 slots (`t & 63`).  The short segments' lengths
+    cycle 0 .. 5, with one of 2 CHUNK + 3 among them."""
+    def short(k):
+        lens = (np.arange(k) % 6).tolist()
+        lens[k // 2] = 2 * CHUNK + 3
+        return lens
+    return dict(one_slot=(short(T.SLOT_SEGMENTS + 1), 1), slots=(short(T.SLOT_SEGMENTS), T.SLOTS),
+                wrap=([5, 70 * CHUNK - 9, 300], T.SLOTS))
+
+
+@pytest.mark.parametrize('dtype', [np.uint64, np.uint32])
+@pytest.mark.parametrize('plan', ['one_slot', 'slots', 'wrap'])
+def test_segment_count_slots(both, plan, dtype):
+    """k_take's per-segment counters (csrc/ctg_take.hip; ctg_plan.h:
+    take_count_slots): one slot a segment past 4096 segments, 64 up to there,
+    and a segment of 70 chunks whose workgroups wrap around its 64 slots.
+    seg_nonzero per segment, the output, and the missing count and smallest
+    missing label with absent labels in the late segments, against numpy."""
+    a, kw = both
+    lens, slots = segment_plans()[plan]
+    assert T.count_slots(len(lens)) == slots
+    assert plan != 'wrap' or -(-max(lens) // CHUNK) > T.SLOTS
+    seg_begin = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    offs = (np.arange(len(lens)) % 7).astype(U64)
+    rng = np.random.default_rng(len(lens))
+    labels = rng.integers(0, 4990, size=int(seg_begin[-1])).astype(dtype)
+    labels[::5] = 0
+    check_dev(a, labels, kw, segments=(seg_begin, offs))
+    late = rng.integers(int(seg_begin[-1]) * 3 // 4, int(seg_begin[-1]), size=40)
+    labels[late] = (6000 + (late % 13)).astype(dtype)       # absent from the table, in the late segments only
+    check_dev(a, labels, kw, segments=(seg_begin, offs))    # refused, naming the smallest and the count
+    if a.kind == 'sparse':
+        check_dev(a, labels, kw, segments=(seg_begin, offs), allow_missing=True)
 
 
 # --------------------------------------------------------------------------- dense range

@@ -59,6 +59,24 @@ def test_count_slots(take):
     assert all(g & (g - 1) == 0 for g in got)        # the kernel masks the workgroup index with slots - 1
 
 
+def test_cap_mirrors(take):
+    """The caps mirrored in tests/take_cases.py against take_count_slots, the
+    chunk plan and the text of launch_take_max (csrc/ctg_take.hip), which holds
+    its grid as literals: a change fails here instead of un-pinning the second
+    turn and the slot wrap in tests/test_gpu_take.py."""
+    from tests import take_cases as T
+    ns = [1, T.SLOT_SEGMENTS, T.SLOT_SEGMENTS + 1]
+    assert [int(g) for g in take(['slots %d' % n for n in ns])] == [T.count_slots(n) for n in ns] == [T.SLOTS, T.SLOTS, 1]
+    assert T.CHUNK == CHUNK and chunks(take, (70 * T.CHUNK,), chunk=T.CHUNK)[-1] == 70 > T.SLOTS
+    with open(os.path.join(ROOT, 'cluster_tools_amd', 'csrc', 'ctg_plan.h')) as f:
+        assert 'constexpr int64_t TAKE_CHUNK = %d;' % T.CHUNK in f.read()
+    with open(os.path.join(ROOT, 'cluster_tools_amd', 'csrc', 'ctg_take.hip')) as f:
+        src = f.read()
+    assert 'std::min<int64_t>((n + 255) / 256, %d)' % (T.MAX_TURN // 256) in src
+    assert 'k_take_max, dim3((unsigned)blocks), dim3(256)' in src
+    assert T.max_turns(T.MAX_TURN) == 1 and T.max_turns(T.MAX_TURN + 1) == 2
+
+
 def test_build_and_lookup_against_a_dict(take):
     rng = np.random.default_rng(2024)
     keys = np.unique(rng.integers(0, 1 << 63, size=100000, dtype=np.uint64))

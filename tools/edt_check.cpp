@@ -7,6 +7,7 @@
 //
 //   plan LINE OUTER NX          -> lds groups grid stack_bytes
 //   passes NZ NY NX TWO_D       -> y z
+//   xgrid ROWS                  -> workgroups of the x pass (edt_x_grid)
 //   edt NZ NY NX PZ PY PX TWO_D BITS
 //                               BITS: NZ*NY*NX characters 0 / 1, 1 a seed; the pitches as
 //                               C hexadecimal floats.  -> n_seeds n_unseeded argmax d2
@@ -180,6 +181,10 @@ int main() {
             is >> n[0] >> n[1] >> n[2] >> two_d;
             const EdtPasses P = edt_passes(n, two_d != 0);
             std::printf("%d %d\n", (int)P.y, (int)P.z);
+        } else if (cmd == "xgrid") {
+            int64_t rows;
+            is >> rows;
+            std::printf("%lld\n", (long long)edt_x_grid(rows));
         } else if (cmd == "edt") {
             std::printf("%s\n", run_edt(is).c_str());
         } else {
