@@ -446,60 +446,76 @@ int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global, const uint6
 int64_t ctg_result_num_edges(const ctg_result* r) { return r ? r->n_edges : -1; }
 int64_t ctg_result_num_nodes(const ctg_result* r) { return r ? r->n_nodes : -1; }
 
-static int copy_out(void* dst, const void* src, size_t bytes, int mem) {
+// The accessors' copy, on the copy stream of the handle's device and waited
+// for: the calls that fill a handle end synchronised, so its tables are ready
+// on any stream, and the copy neither runs on the null stream nor waits for it.
+// (No device lock: a copy does not queue behind another thread's call.  The
+// call that made the handle made that device's workspace, copy stream included.)
+static int copy_out(const ctg_result* r, void* dst, const void* src, size_t bytes, int mem) {
     if (bytes == 0) return CTG_OK;
     if (!dst || !src) {
         set_error("copy: null pointer");
         return CTG_ERR_ARG;
     }
-    CTG_CHECK(hipMemcpy(dst, src, bytes, mem == CTG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+    const int cur = current_device(), dev = r->device >= 0 ? r->device : cur;
+    Workspace& w = ws(dev);
+    if (!w.ready) {
+        set_error("copy: the handle's device has no workspace");
+        return CTG_ERR_ARG;
+    }
+    if (dev != cur) CTG_CHECK(hipSetDevice(dev));
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, mem == CTG_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                  w.copy_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(w.copy_stream);
+    if (dev != cur) hipSetDevice(cur);
+    CTG_CHECK(e);
     return CTG_OK;
 }
 
 int ctg_result_copy_edges(const ctg_result* r, uint64_t* dst, int mem) {
-    return copy_out(dst, r->edges, (size_t)r->n_edges * 16, mem);
+    return copy_out(r, dst, r->edges, (size_t)r->n_edges * 16, mem);
 }
 int ctg_result_copy_nodes(const ctg_result* r, uint64_t* dst, int mem) {
-    return copy_out(dst, r->nodes, (size_t)r->n_nodes * 8, mem);
+    return copy_out(r, dst, r->nodes, (size_t)r->n_nodes * 8, mem);
 }
 int ctg_result_copy_features(const ctg_result* r, double* dst, int mem) {
     if (!r->features && r->n_edges) {
         set_error("result has no features (graph-only call)");
         return CTG_ERR_ARG;
     }
-    return copy_out(dst, r->features, (size_t)r->n_edges * N_FEATURES * 8, mem);
+    return copy_out(r, dst, r->features, (size_t)r->n_edges * N_FEATURES * 8, mem);
 }
 int ctg_result_copy_stats(const ctg_result* r, double* sums_dst, uint32_t* records_dst, int mem) {
     if (!r->stats && r->n_edges) {
         set_error("result has no statistics (call with keep_stats=1 and data)");
         return CTG_ERR_ARG;
     }
-    int rc = copy_out(sums_dst, r->stat_sums, (size_t)r->n_edges * 16, mem);
+    int rc = copy_out(r, sums_dst, r->stat_sums, (size_t)r->n_edges * 16, mem);
     if (rc) return rc;
-    return copy_out(records_dst, r->stats, (size_t)r->n_edges * WREC_WORDS * 4, mem);
+    return copy_out(r, records_dst, r->stats, (size_t)r->n_edges * WREC_WORDS * 4, mem);
 }
 int ctg_result_copy_counts(const ctg_result* r, uint64_t* dst, int mem) {
     if (!r->counts) {
         set_error("result has no counts (not an overlaps result)");
         return CTG_ERR_ARG;
     }
-    return copy_out(dst, r->counts, (size_t)r->n_edges * 8, mem);
+    return copy_out(r, dst, r->counts, (size_t)r->n_edges * 8, mem);
 }
 int ctg_result_copy_moments(const ctg_result* r, uint64_t* dst, int mem) {
     if (!r || !r->moments) {
         set_error("result has no moments (not a morphology result)");
         return CTG_ERR_ARG;
     }
-    return copy_out(dst, r->moments, (size_t)r->n_nodes * MORPH_WORDS * 8, mem);
+    return copy_out(r, dst, r->moments, (size_t)r->n_nodes * MORPH_WORDS * 8, mem);
 }
 int ctg_result_copy_region(const ctg_result* r, uint64_t* counts, double* sums, float* minmax, int mem) {
     if (!r || !r->reg_count) {
         set_error("result has no region moments (not a region-features result)");
         return CTG_ERR_ARG;
     }
-    int rc = counts ? copy_out(counts, r->reg_count, (size_t)r->n_nodes * 8, mem) : CTG_OK;
-    if (!rc && sums) rc = copy_out(sums, r->reg_sum, (size_t)r->n_nodes * 8, mem);
-    if (!rc && minmax) rc = copy_out(minmax, r->reg_minmax, (size_t)r->n_nodes * 8, mem);
+    int rc = counts ? copy_out(r, counts, r->reg_count, (size_t)r->n_nodes * 8, mem) : CTG_OK;
+    if (!rc && sums) rc = copy_out(r, sums, r->reg_sum, (size_t)r->n_nodes * 8, mem);
+    if (!rc && minmax) rc = copy_out(r, minmax, r->reg_minmax, (size_t)r->n_nodes * 8, mem);
     return rc;
 }
 const uint64_t* ctg_result_device_edges(const ctg_result* r) { return r ? r->edges : nullptr; }

@@ -11,6 +11,21 @@
 
 using namespace ctg;
 
+// The passes' scratch.  The pool knows nothing of streams, so the blocks go
+// back to it only once the stream is idle, on every return path (as AdjFilter,
+// BlockTables and MergeScratch do): a call on another stream could otherwise
+// draw them while the passes still write them.
+struct EdtScratch {
+    hipStream_t s;
+    DevBuf<uint16_t> dx;
+    DevBuf<uint32_t> dyx;
+    DevBuf<uint64_t> stack;
+    DevBuf<unsigned long long> words;   // info[4], then the last pass's partials
+    ~EdtScratch() {
+        if (dx) hipStreamSynchronize(s);
+    }
+};
+
 extern "C" {
 
 int ctg_distance_transform(const void* src, int src_kind, int src_bits, const int64_t* shape, const int64_t* begin,
@@ -66,12 +81,13 @@ int ctg_distance_transform(const void* src, int src_kind, int src_bits, const in
     const EdtLinePlan& last = passes.z ? pz : py;
     const size_t elems = (size_t)shape[0] * shape[1] * shape[2];
     DevInput<char> ds;
+    DenseOut<char> o;   // (both before the scratch: their blocks, too, are freed after its wait)
     if ((rc = ds.put((const char*)src, elems * (size_t)(src_bits / 8), mem, s, who)) != CTG_OK) return rc;
-    DevBuf<uint16_t> dx;
-    DevBuf<uint32_t> dyx;
-    DevBuf<uint64_t> stack;
-    DevBuf<unsigned long long> words;   // info[4], then the last pass's partials
-    DenseOut<char> o;
+    EdtScratch scratch{s};
+    DevBuf<uint16_t>& dx = scratch.dx;
+    DevBuf<uint32_t>& dyx = scratch.dyx;
+    DevBuf<uint64_t>& stack = scratch.stack;
+    DevBuf<unsigned long long>& words = scratch.words;
     const int64_t stack_bytes = std::max<int64_t>(passes.y ? py.stack_bytes : 0, passes.z ? pz.stack_bytes : 0);
     if (!dx.alloc((size_t)V * 2) || (passes.y && passes.z && !dyx.alloc((size_t)V * 4)) ||
         (stack_bytes && !stack.alloc((size_t)stack_bytes)) ||
@@ -124,8 +140,8 @@ int ctg_distance_transform(const void* src, int src_kind, int src_bits, const in
     ev.mark(6);
     CTG_CHECK(o.copy_back(s));
     if (info) CTG_CHECK(hipMemcpyAsync(info, words.p, 4 * 8, hipMemcpyDeviceToHost, s));
-    // (a device-resident call without info returns with its work queued on s)
-    if (info || mem == CTG_MEM_HOST) CTG_CHECK(hipStreamSynchronize(s));
+    // always waited for, a device-resident call without info too (EdtScratch)
+    CTG_CHECK(hipStreamSynchronize(s));
     if (c.w().profiling && (rc = read_phase_times(c.w(), s)) != CTG_OK) return rc;
     return CTG_OK;
 }

@@ -251,6 +251,9 @@ int ctg_mgpu_pack(const ctg_result* local, const int64_t* counts_all, int world_
                            "rows to send need a CTG_KEEP_STATS table and a send buffer");
     if (rc || (rc = c.begin(stream)) != CTG_OK) return rc;
     CTG_CHECK(mgpu_pack(local, p.send, send, c.s));
+    // a CTG_DEFER_STATS table is packed from the workspace's records, which the
+    // next scan on any stream overwrites: that pack is waited for
+    if (local->defer.on) CTG_CHECK(hipStreamSynchronize(c.s));
     return CTG_OK;
 }
 

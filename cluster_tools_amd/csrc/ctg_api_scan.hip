@@ -9,7 +9,9 @@
 // after the stream is synchronised (AdjFilter, BlockTables: their destructors
 // synchronise first, on every return path), or it goes back to the pool while
 // still in use and the pool's stream-ordered reuse keeps a later user behind
-// the kernel (ctg_buffers.h).
+// the kernel (ctg_buffers.h) -- a later user of this call, on this stream: both
+// entry points wait for the stream before they return, so no call on another
+// stream meets such a block (include/ctg.h, "Streams").
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -379,8 +381,9 @@ static hipError_t widen_single_label(const ScanParams& P, int64_t at, hipStream_
     uint32_t l32 = 0;
     hipError_t e = hipMemcpyAsync(&l32, (const uint32_t*)P.labels + at, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const uint64_t l64 = l32;
-    if (e == hipSuccess) e = hipMemcpy(r->nodes, &l64, 8, hipMemcpyHostToDevice);
+    const uint64_t l64 = l32;   // (on s like the rest of the call, and waited for: l64 is a local)
+    if (e == hipSuccess) e = hipMemcpyAsync(r->nodes, &l64, 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
     r->n_nodes = 1;
     return e;
 }

@@ -13,7 +13,13 @@ namespace ctg {
 // the library's caching device allocator (ctg_pool.h, ctg_workspace.hip).
 // dev_free only returns the block to the host-side pool: kernels already
 // queued on the stream still use it, and a later user of the block runs after
-// them ("stream-ordered reuse")
+// them ("stream-ordered reuse").  That holds for later users on the same
+// stream only, and the pool knows nothing of streams: a block may be freed
+// with work queued on it only inside a call that waits for its stream before
+// it returns (the device lock keeps other streams' calls out until then).
+// A CTG_CHECK return after work was queued does not wait: only the scratch
+// owners with a waiting destructor (EdtScratch, BlockTables, AdjFilter,
+// MergeScratch) cover every return path (include/ctg.h, "Streams")
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);
 

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstddef>
 #include <memory>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -318,7 +319,7 @@ static_assert(SLOT_RUNS >= 0 && SLOT_RUNS + 1 <= SLOT_EDGES && SLOT_EDGES + 1 <=
               "the scalar slots overlap or pass SMALL_WORDS");
 
 struct Workspace {
-    bool ready = false;   // ws_init made every fixed member (counters .. mgpu_spl, ev); set last
+    std::atomic<bool> ready{false};   // (read without the device lock by the accessors' copy) ws_init made every fixed member (counters .. mgpu_spl, ev); set last
     int device = -1;
     // bumped by every call that overwrites the records or the sort / run
     // buffers (a CTG_DEFER_STATS handle compares it)
@@ -336,6 +337,9 @@ struct Workspace {
     hipEvent_t mgpu_spl_ev = nullptr;    // recorded after the last split read mgpu_spl (a split on another
                                          // stream waits for it before overwriting the splitters)
     GrowBuf stage[2];   // host->device staging of volumes
+    // the result accessors' copies (ctg_result_copy_*): a non-blocking stream
+    // of the library's own, so they neither run on the null stream nor wait for it
+    hipStream_t copy_stream = nullptr;
     // timing
     hipEvent_t ev[7] = {};   // 0..6: the phase marks of a call
     double last_ms[8] = {0};   // scan, pack, sort, segment, reduce, nodes, total, narrow (always 0: no such pass)

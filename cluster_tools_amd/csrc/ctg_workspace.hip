@@ -46,6 +46,7 @@ static hipError_t ws_create(Workspace& w) {
     CTG_TRY(hipMalloc(&w.mgpu_spl, CTG_MGPU_MAX_WORLD * sizeof(uint64_t)));
     CTG_TRY(hipHostMalloc(&w.small_host, SMALL_WORDS * sizeof(unsigned int), hipHostMallocDefault));
     for (hipEvent_t& ev : w.ev) CTG_TRY(hipEventCreate(&ev));
+    CTG_TRY(hipStreamCreateWithFlags(&w.copy_stream, hipStreamNonBlocking));
     return hipSuccess;
 }
 
@@ -68,6 +69,7 @@ hipError_t ws_init(Workspace& w) {
     drop(w.mgpu_spl, hipFree);
     drop(w.small_host, hipHostFree);
     for (hipEvent_t& ev : w.ev) drop(ev, hipEventDestroy);
+    drop(w.copy_stream, hipStreamDestroy);
     return e;
 }
 

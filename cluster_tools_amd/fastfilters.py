@@ -132,8 +132,7 @@ def _eig(comps, dim):
 
 
 def _ret(t, host):
-    if host:
-        _torch().cuda.synchronize()
+    if host:   # (the copy runs on the current stream, after the filter's kernels, and is waited for)
         return t.cpu().numpy()
     return t
 

@@ -53,6 +53,18 @@ def _shape_arr(vals):
     return (ctypes.c_int64 * 3)(*[int(v) for v in vals])
 
 
+def _handle_stream(stream=None):
+    """The stream of a call that reads a device-resident handle: ``stream``,
+    else torch's current stream where torch runs on the GPU in this process
+    (the handle's call took the same), else the null stream."""
+    if stream is not None:
+        return stream
+    torch = sys.modules.get('torch')
+    if torch is None or not torch.cuda.is_initialized():
+        return None
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
 class Result:
     """Owning wrapper around a ``ctg_result*`` handle (device-resident)."""
 
@@ -116,10 +128,11 @@ class Result:
         L.check(L.load().ctg_result_copy_moments(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_moments')
         return out
 
-    def morph_rows(self):
+    def morph_rows(self, stream=None):
         """(N,11) float64 rows of a morphology result, ids ascending."""
         out = np.empty((self.n_nodes, MORPH_COLS), dtype=np.float64)
-        L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, _ptr(out), L.CTG_MEM_HOST, None),
+        L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, _ptr(out), L.CTG_MEM_HOST,
+                                             _handle_stream(stream)),
                 'ctg_morphology_rows')
         return out
 
@@ -132,22 +145,23 @@ class Result:
                 'copy_region')
         return c, s, m
 
-    def region_rows(self, form='sums', norm=1.0):
+    def region_rows(self, form='sums', norm=1.0, stream=None):
         """(N,5) float64 rows of a region-features result, ids ascending:
         [id, count, sum, min, max] (``form`` 'sums') or [id, count, mean,
         minimum, maximum] over ``norm`` ('features')."""
         out = np.empty((self.n_nodes, REGION_COLS), dtype=np.float64)
         L.check(L.load().ctg_region_rows(self.handle, 0, 0, _region_form(form), float(norm), None, _ptr(out),
-                                         L.CTG_MEM_HOST, None), 'ctg_region_rows')
+                                         L.CTG_MEM_HOST, _handle_stream(stream)), 'ctg_region_rows')
         return out
 
     # --- device copies (torch)
-    def region_rows_torch(self, form='sums', norm=1.0):
+    def region_rows_torch(self, form='sums', norm=1.0, stream=None):
         """(N,5) float64 tensor of the rows of a region-features result."""
         import torch
         t = torch.empty((self.n_nodes, REGION_COLS), dtype=torch.float64, device='cuda:%d' % self.device)
         L.check(L.load().ctg_region_rows(self.handle, 0, 0, _region_form(form), float(norm), None,
-                                         ctypes.c_void_p(t.data_ptr()), L.CTG_MEM_DEVICE, None), 'ctg_region_rows')
+                                         ctypes.c_void_p(t.data_ptr()), L.CTG_MEM_DEVICE, _handle_stream(stream)),
+                'ctg_region_rows')
         return t
 
     def moments_torch(self):
@@ -155,12 +169,12 @@ class Result:
         import torch
         return self._torch_copy((self.n_nodes, MORPH_WORDS), torch.int64, L.load().ctg_result_copy_moments)
 
-    def morph_rows_torch(self):
+    def morph_rows_torch(self, stream=None):
         """(N,11) float64 tensor of the rows of a morphology result."""
         import torch
         t = torch.empty((self.n_nodes, MORPH_COLS), dtype=torch.float64, device='cuda:%d' % self.device)
         L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, ctypes.c_void_p(t.data_ptr()),
-                                             L.CTG_MEM_DEVICE, None), 'ctg_morphology_rows')
+                                             L.CTG_MEM_DEVICE, _handle_stream(stream)), 'ctg_morphology_rows')
         return t
 
     def counts_torch(self):
@@ -171,8 +185,17 @@ class Result:
     def _torch_copy(self, shape, dtype, fn):
         import torch
         t = torch.empty(shape, dtype=dtype, device='cuda:%d' % self.device)
+        self._before_device_copy()
         L.check(fn(self.handle, ctypes.c_void_p(t.data_ptr()), L.CTG_MEM_DEVICE), 'device copy')
         return t
+
+    @staticmethod
+    def _before_device_copy():
+        """The accessors copy on a stream of the library's own, ordered after
+        nothing else: a fresh tensor may be a block of torch's allocator that
+        work queued on the current stream still uses, so that work ends first."""
+        import torch
+        torch.cuda.current_stream().synchronize()
 
     def edges_torch(self):
         import torch
@@ -196,6 +219,7 @@ class Result:
         import torch
         s = torch.empty((self.n_edges, 2), dtype=torch.float64, device='cuda:%d' % self.device)
         r = torch.empty((self.n_edges, WIDE_WORDS), dtype=torch.int32, device='cuda:%d' % self.device)
+        self._before_device_copy()
         L.check(L.load().ctg_result_copy_stats(self.handle, ctypes.c_void_p(s.data_ptr()),
                                                ctypes.c_void_p(r.data_ptr()), L.CTG_MEM_DEVICE), 'copy_stats')
         return s, r
@@ -391,7 +415,7 @@ def _desc(blocks):
 
 
 def rag_blocks_arena(labels, blocks, data=None, offsets=None, ignore_label=False, hist_range=(0.0, 1.0),
-                     keep_stats=False, nodes=True):
+                     keep_stats=False, nodes=True, stream=None):
     """ctg_rag_blocks over arenas that already hold the block arrays.
 
     labels: 1-D uint64/uint32 array (host, ideally a HostArena view);
@@ -440,8 +464,8 @@ def rag_blocks_arena(labels, blocks, data=None, offsets=None, ignore_label=False
     rc = lib.ctg_rag_blocks(_ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr,
                             ctypes.cast(desc, ctypes.c_void_p), len(blocks), n_lab, n_dat,
                             int(bool(ignore_label)), float(hist_range[0]), float(hist_range[1]), flags,
-                            L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, _current_stream(on_dev),
-                            ctypes.byref(h))
+                            L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
+                            _current_stream(on_dev) if stream is None else stream, ctypes.byref(h))
     L.check(rc, 'ctg_rag_blocks')
     r = Result(h, dev)
     nb = len(blocks)
@@ -467,7 +491,7 @@ def rag_blocks_arena(labels, blocks, data=None, offsets=None, ignore_label=False
 
 
 def rag_blocks(arrays, own, graph, data=None, offsets=None, ignore_label=False, hist_range=(0.0, 1.0),
-               keep_stats=False):
+               keep_stats=False, stream=None):
     """Convenience front end of rag_blocks_arena: per-block label arrays
     (and data arrays: (Z,Y,X) boundary maps or (C,Z,Y,X) affinities) with
     their own / graph boxes ((begin, end) in array coordinates)."""
@@ -485,10 +509,11 @@ def rag_blocks(arrays, own, graph, data=None, offsets=None, ignore_label=False, 
         lo += a.size
         if data is not None:
             do += data[i].size
-    return rag_blocks_arena(lab_arena, blocks, dat_arena, offsets, ignore_label, hist_range, keep_stats)
+    return rag_blocks_arena(lab_arena, blocks, dat_arena, offsets, ignore_label, hist_range, keep_stats,
+                            stream=stream)
 
 
-def unique_labels(labels, begin=None, end=None):
+def unique_labels(labels, begin=None, end=None, stream=None):
     """Sorted unique labels of labels[begin:end] (uint64 numpy array)."""
     lib = L.load()
     L.init_device()
@@ -501,7 +526,7 @@ def unique_labels(labels, begin=None, end=None):
                                _shape_arr(begin) if begin is not None else None,
                                _shape_arr(end) if end is not None else None,
                                L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
-                               _current_stream(on_dev), ctypes.byref(h))
+                               _current_stream(on_dev) if stream is None else stream, ctypes.byref(h))
     L.check(rc, 'ctg_unique_labels')
     r = Result(h, L.init_device())
     nodes = r.nodes()
@@ -566,7 +591,7 @@ def merge_stats(keys, sums, records, hist_range=(0.0, 1.0), keep_stats=False):
     return out
 
 
-def merge_feature_rows(ids, rows, id_begin, id_end):
+def merge_feature_rows(ids, rows, id_begin, id_end, stream=None):
     """Reference-layout (n,10) feature rows of global edge ids -> the merged
     (id_end - id_begin, 10) rows (ctg_merge_feature_rows)."""
     lib = L.load()
@@ -577,31 +602,31 @@ def merge_feature_rows(ids, rows, id_begin, id_end):
         raise ValueError('ids and rows differ in length')
     out = np.zeros((int(id_end) - int(id_begin), N_FEATURES), dtype=np.float64)
     L.check(lib.ctg_merge_feature_rows(_ptr(ids), _ptr(rows), ids.shape[0], int(id_begin), int(id_end), _ptr(out),
-                                       L.CTG_MEM_HOST, None), 'ctg_merge_feature_rows')
+                                       L.CTG_MEM_HOST, stream), 'ctg_merge_feature_rows')
     return out
 
 
-def unique_pairs(pairs):
+def unique_pairs(pairs, stream=None):
     """Sorted unique rows of an (n,2) uint64 pair list -> (edges, nodes)."""
     lib = L.load()
     dev = L.init_device()
     p = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
     h = ctypes.c_void_p()
-    L.check(lib.ctg_unique_pairs(_ptr(p), p.shape[0], L.CTG_MEM_HOST, None, ctypes.byref(h)), 'ctg_unique_pairs')
+    L.check(lib.ctg_unique_pairs(_ptr(p), p.shape[0], L.CTG_MEM_HOST, stream, ctypes.byref(h)), 'ctg_unique_pairs')
     r = Result(h, dev)
     out = r.edges(), r.nodes()
     r.free()
     return out
 
 
-def map_edge_ids(global_edges, query):
+def map_edge_ids(global_edges, query, stream=None):
     """Row of every query (u,v) in the sorted global edge table (-1 if absent)."""
     lib = L.load()
     L.init_device()
     g = np.ascontiguousarray(np.asarray(global_edges, dtype=np.uint64).reshape(-1, 2))
     q = np.ascontiguousarray(np.asarray(query, dtype=np.uint64).reshape(-1, 2))
     out = np.empty(q.shape[0], dtype=np.int64)
-    rc = lib.ctg_map_edge_ids(_ptr(g), g.shape[0], _ptr(q), q.shape[0], _ptr(out), L.CTG_MEM_HOST, None)
+    rc = lib.ctg_map_edge_ids(_ptr(g), g.shape[0], _ptr(q), q.shape[0], _ptr(out), L.CTG_MEM_HOST, stream)
     L.check(rc, 'ctg_map_edge_ids')
     return out
 
@@ -709,7 +734,7 @@ def merge_overlaps(pairs, counts):
     return out
 
 
-def max_overlaps(handle_or_tables, label_begin, label_end):
+def max_overlaps(handle_or_tables, label_begin, label_end, stream=None):
     """Per label in [label_begin, label_end) the value it overlaps most and
     that overlap: (labels, counts), uint64 arrays of label_end - label_begin
     entries, 0 / 0 for labels without a row; equal counts go to the smallest
@@ -719,12 +744,13 @@ def max_overlaps(handle_or_tables, label_begin, label_end):
     if lb < 0 or le < lb:
         raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
     own = not isinstance(handle_or_tables, Result)
-    r = merge_overlaps_handle(handle_or_tables['pairs'], handle_or_tables['counts']) if own else handle_or_tables
+    r = merge_overlaps_handle(handle_or_tables['pairs'], handle_or_tables['counts'], stream) if own \
+        else handle_or_tables
     out_l = np.zeros(le - lb, dtype=np.uint64)
     out_c = np.zeros(le - lb, dtype=np.uint64)
     try:
-        L.check(L.load().ctg_max_overlaps(r.handle, lb, le, _ptr(out_l), _ptr(out_c), L.CTG_MEM_HOST, None),
-                'ctg_max_overlaps')
+        L.check(L.load().ctg_max_overlaps(r.handle, lb, le, _ptr(out_l), _ptr(out_c), L.CTG_MEM_HOST,
+                                          _handle_stream(stream)), 'ctg_max_overlaps')
     finally:
         if own:
             r.free()
@@ -815,7 +841,7 @@ def merge_morphology(rows):
         r.free()
 
 
-def morphology_rows(handle_or_tables, label_begin, label_end):
+def morphology_rows(handle_or_tables, label_begin, label_end, stream=None):
     """The dense (label_end - label_begin, 11) float64 table of the labels in
     [label_begin, label_end): the row of label a at a - label_begin, zeros for
     absent labels.  ``handle_or_tables``: a ``Result`` of morphology_handle /
@@ -824,11 +850,11 @@ def morphology_rows(handle_or_tables, label_begin, label_end):
     if lb < 0 or le < lb:
         raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
     own = not isinstance(handle_or_tables, Result)
-    r = merge_morphology_handle(handle_or_tables['rows']) if own else handle_or_tables
+    r = merge_morphology_handle(handle_or_tables['rows'], stream) if own else handle_or_tables
     out = np.zeros((le - lb, MORPH_COLS), dtype=np.float64)
     try:
-        L.check(L.load().ctg_morphology_rows(r.handle, lb, le, _ptr(out), None, L.CTG_MEM_HOST, None),
-                'ctg_morphology_rows')
+        L.check(L.load().ctg_morphology_rows(r.handle, lb, le, _ptr(out), None, L.CTG_MEM_HOST,
+                                             _handle_stream(stream)), 'ctg_morphology_rows')
     finally:
         if own:
             r.free()
@@ -945,7 +971,7 @@ def merge_region_features(rows, norm=1.0):
         r.free()
 
 
-def region_feature_rows(handle_or_tables, label_begin, label_end, form='features', norm=1.0):
+def region_feature_rows(handle_or_tables, label_begin, label_end, form='features', norm=1.0, stream=None):
     """The dense (label_end - label_begin, 5) float64 table of the labels in
     [label_begin, label_end) in ``form`` ('features': [id, count, mean, minimum,
     maximum] over ``norm``; 'sums': [id, count, sum, min, max]): the row of
@@ -959,11 +985,11 @@ def region_feature_rows(handle_or_tables, label_begin, label_end, form='features
     if not (float(norm) > 0.0 and float(norm) < float('inf')):
         raise ValueError('norm must be finite and positive, got %r' % (norm,))
     own = not isinstance(handle_or_tables, Result)
-    r = merge_region_features_handle(handle_or_tables['rows']) if own else handle_or_tables
+    r = merge_region_features_handle(handle_or_tables['rows'], stream) if own else handle_or_tables
     out = np.zeros((le - lb, REGION_COLS), dtype=np.float64)
     try:
-        L.check(L.load().ctg_region_rows(r.handle, lb, le, code, float(norm), _ptr(out), None, L.CTG_MEM_HOST, None),
-                'ctg_region_rows')
+        L.check(L.load().ctg_region_rows(r.handle, lb, le, code, float(norm), _ptr(out), None, L.CTG_MEM_HOST,
+                                         _handle_stream(stream)), 'ctg_region_rows')
     finally:
         if own:
             r.free()

@@ -58,6 +58,63 @@
  * ctg_last_error() returns a thread-local message (the Python shim raises
  * RuntimeError with it, as pybind11 does for nifty's C++ exceptions).
  * Results are library-owned handles released with ctg_free().
+ *
+ * Streams (tests/test_gpu_streams.py holds every call below to this):
+ *   - Every GPU operation of a call -- kernels, memsets, copies, the sorts and
+ *     scans -- is issued on the call's ``stream``.  The library never issues
+ *     work on the null stream unless that is the stream it was given, and never
+ *     waits for it: a caller on a non-blocking stream is neither delayed by nor
+ *     ordered against unrelated work on the null stream.  The only device-wide
+ *     wait the library asks for is ctg_trim's (and ctg_diag_bounds' in CTG_DIAG
+ *     builds); ctg_init makes the device's workspace on its first call and
+ *     queues nothing.  What HIP itself does inside hipMalloc and hipFree is not
+ *     the library's to promise: a call whose buffers outgrow the cached ones
+ *     (the first call of a size, a call after ctg_trim, a purge of the pool on
+ *     an out-of-memory) allocates or frees device memory, and the runtime may
+ *     wait for the device there; steady-state calls reach neither.
+ *   - Calls that return synchronised -- every operation of the call has
+ *     completed when it returns (it has waited for ``stream``, unless it had
+ *     nothing to issue: an empty input or box), outputs in host or device
+ *     memory are complete, and the inputs may be reused or freed at once:
+ *     ctg_rag_features, ctg_rag_blocks,
+ *     ctg_unique_labels, ctg_unique_values, ctg_unique_pairs, ctg_merge_stats,
+ *     ctg_merge_feature_rows, ctg_map_edge_ids with CTG_MEM_HOST,
+ *     ctg_label_overlaps, ctg_merge_overlaps, ctg_max_overlaps, ctg_morphology,
+ *     ctg_merge_morphology, ctg_morphology_rows, ctg_region_features,
+ *     ctg_merge_region_features, ctg_region_rows, ctg_assignment_dense,
+ *     ctg_assignment_sparse, ctg_apply_assignment, ctg_threshold_components,
+ *     ctg_merge_assignments, ctg_distance_transform (with or without info, host
+ *     or device memory) and ctg_mgpu_merge.
+ *   - Calls that return with their work queued on ``stream`` (device memory
+ *     only, no scratch of the library's pool): ctg_map_edge_ids with
+ *     CTG_MEM_DEVICE, ctg_synth_volume, ctg_synth_affinities,
+ *     ctg_filter_conv_axis, ctg_filter_combine, ctg_sym_eigenvalues,
+ *     ctg_mgpu_sample, ctg_mgpu_split and ctg_mgpu_pack (a pack of a
+ *     CTG_DEFER_STATS table reads the workspace's records, which a later scan
+ *     on any stream overwrites: that pack alone is waited for).  Work queued on the
+ *     same stream afterwards sees their finished outputs.  Until that work
+ *     completes the caller must keep the inputs and outputs alive and
+ *     unchanged, must not read the outputs from the host or from another stream
+ *     without an event or a synchronisation, and (ctg_mgpu_*) must not free the
+ *     handle the call reads.  Small host arguments (shapes, offsets, taps,
+ *     counts_all) are consumed before the call returns.
+ *   - The result accessors (ctg_result_copy_*) are host-synchronous: the data is
+ *     at ``dst`` when they return.  They copy on a non-blocking stream of the
+ *     library's own, so they do not depend on the null stream; a handle's
+ *     tables are complete on every stream because the calls that fill them
+ *     return synchronised.  A device ``dst`` must not be in use by work that is
+ *     still queued.  ctg_morphology_rows, ctg_region_rows and ctg_max_overlaps
+ *     read a handle on the stream they are given.
+ *   - Calls on different streams of one device may follow one another freely
+ *     (they are serialised per device by a lock).  The library's block pool
+ *     knows nothing of streams, so a block returns to it while work that uses
+ *     it is queued only inside a call that waits for its stream before it
+ *     returns; every call that draws scratch from the pool is of that kind
+ *     where it succeeds.  A call that fails with CTG_ERR_HIP after it queued
+ *     work (a launch or copy that HIP refused) may return with that work queued
+ *     and its scratch back in the pool -- ctg_distance_transform,
+ *     ctg_rag_blocks, the adjacency filter and ctg_mgpu_merge wait even then;
+ *     after such an error synchronise the stream before the next call.
  */
 #ifndef CTG_H_
 #define CTG_H_

@@ -46,6 +46,20 @@ def test_size_classes(report):
     assert got[1 << 36] >= 1 << 36 and got[(1 << 32) + 1] < ((1 << 32) + 1) * 5 // 4
 
 
+def test_stream_cases_restates_the_size_classes(report):
+    """tests/stream_cases.py sizes the block that two calls on two streams
+    share (tests/test_gpu_streams.py) by its own pool_round_up and reuse rule:
+    the same classes as the library's, and the reuse bound of `reuse_bound`."""
+    import stream_cases as SC
+    got = {int(b): int(r) for _, b, r in (l.split() for l in report if l.startswith('class '))}
+    assert len(got) == 18 and all(SC.pool_round_up(b) == r for b, r in got.items())
+    assert SC.same_block_class(1000, 512) and SC.same_block_class(1000, 1024)   # up to twice the request's class
+    assert not SC.same_block_class(2048, 512) and not SC.same_block_class(512, 1000)
+    # the case of the test: V uint16 distances and V / 4 uint64 values, V = 5 * 33 * 70
+    V = 5 * 33 * 70
+    assert SC.pool_round_up(V * 2) == SC.pool_round_up((V // 4) * 8) == 32768
+
+
 CASES = ['reuse_bound', 'purge_and_retry', 'purge_and_retry_refused', 'freed_to_allocating_device',
          'purge_with_refused_free', 'dev_buf', 'grow_buf', 'sort_scratch_growth'] + \
         ['sort_scratch_refused_%d' % k for k in range(9)]
