@@ -37,6 +37,7 @@ CTG_EDT_SRC_EQUAL = 2
 CTG_EDT_TO_BACKGROUND = 1
 CTG_EDT_2D = 2
 CTG_EDT_OUT_D2 = 4
+CTG_WS_2D = 1
 CTG_MAX_CHANNELS = 24
 CTG_N_FEATURES = 10
 CTG_NBINS = 40
@@ -124,6 +125,8 @@ PROTOTYPES = {
     'ctg_merge_assignments': (ctypes.c_int, [c_vp, ctypes.c_int64, ctypes.c_uint64, c_vp, ctypes.c_int, c_vp, c_u64p]),
     'ctg_distance_transform': (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_double,
                                               ctypes.c_uint64, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp]),
+    'ctg_seeded_watershed': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_uint64,
+                                            c_vp, ctypes.c_int, c_vp, c_vp]),
     'ctg_map_edge_ids': (ctypes.c_int, [c_vp, ctypes.c_int64, c_vp, ctypes.c_int64, c_vp, ctypes.c_int, c_vp]),
     'ctg_result_num_edges': (ctypes.c_int64, [c_vp]),
     'ctg_result_num_nodes': (ctypes.c_int64, [c_vp]),

@@ -1,7 +1,8 @@
 // What the C-ABI entry points share (ctg_api.hip: handles, unique / merge /
 // map; ctg_api_scan.hip: the face scan; ctg_api_tables.hip: label overlaps
 // and morphology; ctg_api_cc.hip: the thresholded components;
-// ctg_api_mgpu.hip: the multi-GPU exchange): the call scaffold, the
+// ctg_api_edt.hip: the distance transform; ctg_api_ws.hip: the seeded
+// watershed; ctg_api_mgpu.hip: the multi-GPU exchange): the call scaffold, the
 // status of a HIP error, inputs and outputs that may live on the host, and the
 // dense relabelling of (u,v) pair lists.  No rocPRIM here: the two helpers
 // that sort (sort_unique_u64, and with it unique_candidates) are defined in

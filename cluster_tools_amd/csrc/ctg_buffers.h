@@ -18,8 +18,8 @@ namespace ctg {
 // with work queued on it only inside a call that waits for its stream before
 // it returns (the device lock keeps other streams' calls out until then).
 // A CTG_CHECK return after work was queued does not wait: only the scratch
-// owners with a waiting destructor (EdtScratch, BlockTables, AdjFilter,
-// MergeScratch) cover every return path (include/ctg.h, "Streams")
+// owners with a waiting destructor (EdtScratch, WsScratch, BlockTables,
+// AdjFilter, MergeScratch) cover every return path (include/ctg.h, "Streams")
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);
 

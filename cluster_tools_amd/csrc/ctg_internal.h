@@ -726,6 +726,48 @@ hipError_t launch_edt_line(const EdtLineArgs& A, const EdtLinePlan& P, hipStream
 // n partials -> info[1 .. 3]
 hipError_t launch_edt_fold(const unsigned long long* part, int64_t n, unsigned long long* info, hipStream_t s);
 
+// ---------------------------------------------------------------------------
+// seeded watershed (ctg_ws.hip).  Call-sized pool buffers only, as the label
+// overlaps.
+// ---------------------------------------------------------------------------
+// The u64 words of a call's small device block: the NaN flag and the seeded
+// voxels of the box, a round's hooks, whether a chase stopped short, the error
+// word (never raised by a sound launch: a pick without an edge), and the
+// result's largest label, its voxels left 0 and the labels the filter dropped
+enum WsWord : int {
+    WS_W_NAN = 0, WS_W_SEEDED = 1, WS_W_HOOKS = 2, WS_W_SHORT = 3, WS_W_ERR = 4, WS_W_MAX = 5, WS_W_ZERO = 6,
+    WS_W_DROPPED = 7, WS_WORDS = 8
+};
+struct WsArgs {                 // one flood
+    const float* hmap;          // the array's heights
+    const void* seeds;          // the array's seeds (seed_bits 32 or 64)
+    int seed_bits;
+    int64_t s_z, s_y;           // the strides of both arrays in elements
+    int64_t base;               // element offset of the box's first voxel
+    uint32_t n[3];              // the box (z, y, x)
+    int two_d;
+    uint32_t* parent;           // box-linear, as the three below (ctg_plan.h: ws_plan)
+    uint32_t* key;
+    unsigned long long* best;
+    uint32_t* pick;
+    unsigned long long* words;  // device: WsWord
+};
+// with_keys: the heights' keys and the NaN flag as well (a second flood of the same heights keeps them);
+// every voxel its own root, flagged where seeded; the seeded voxels counted
+hipError_t launch_ws_init(const WsArgs& A, int with_keys, hipStream_t s);
+// one round up to the hooks: both minima, then what every picking root hangs below, counted in WS_W_HOOKS
+hipError_t launch_ws_pick(const WsArgs& A, hipStream_t s);
+// the hooks into parent
+hipError_t launch_ws_apply(const WsArgs& A, hipStream_t s);
+// one chase launch; WS_W_SHORT is raised where an entry is not yet its root
+hipError_t launch_ws_chase(const WsArgs& A, hipStream_t s);
+// out[i] = the seed of i's root, 0 without one; the largest label and the voxels left 0 folded into words
+hipError_t launch_ws_write(const WsArgs& A, uint64_t* out, hipStream_t s);
+// The size filter over the slab [v0, v0 + n) of out, whose labels and voxel counts are (nodes, moments) of a
+// morphology table: labels with fewer than `size` voxels there become 0; the dropped labels added to WS_W_DROPPED
+hipError_t launch_ws_filter(uint64_t* out, int64_t n, const uint64_t* nodes, const uint64_t* moments, int64_t n_nodes,
+                            uint64_t size, unsigned long long* words, hipStream_t s);
+
 hipError_t mgpu_sample(const uint64_t* edges, int64_t E, int64_t* meta, hipStream_t s);
 hipError_t mgpu_split(const uint64_t* edges, int64_t E, const uint64_t* nodes, int64_t N, const int64_t* meta_all,
                       int world, uint64_t* spl, int64_t* counts, hipStream_t s);

@@ -475,6 +475,46 @@ inline EdtPasses edt_passes(const int64_t* n, bool two_d) {
 }
 
 // ---------------------------------------------------------------------------
+// the seeded watershed (ctg_ws.hip)
+// ---------------------------------------------------------------------------
+// an edge id is 3 * (box-linear index) + axis in 32 bits, and bit 31 of a parent
+// entry is a flag (ctg_ws.h): a box holds at most 2^30 voxels
+constexpr int64_t WS_MAX_VOXELS = 1ll << 30;
+constexpr int WS_THREADS = 256;
+// a thread per voxel up to this many workgroups, which then stride: a launch's
+// counters take one atomic per workgroup
+constexpr int64_t WS_MAX_GRID = 4096;
+inline int64_t ws_grid(int64_t n) { return std::min<int64_t>((n + WS_THREADS - 1) / WS_THREADS, WS_MAX_GRID); }
+// Rounds that suffice for U unseeded voxels: every round at least halves the
+// seedless components that still have an edge leaving them, at most U at the
+// start, so after ceil(log2(U + 1)) rounds none is left, and one more round
+// finds nothing to pick and ends the flood.
+inline int ws_round_cap(int64_t U) { return bits_u(U) + 1; }
+// Chase launches that suffice after a round's hooks: a chain is shorter than
+// 2^30 entries and a launch leaves every entry WS_CHASE_STEPS = 2^6 entries
+// further up its chain, or at the root: five launches reach it, the sixth
+// finds nothing short.
+constexpr int WS_CHASE_LAUNCHES = 6;
+struct WsPlan {
+    int64_t voxels;
+    int64_t grid;            // workgroups of every per-voxel launch
+    int64_t parent_bytes;    // u32 per voxel: the forest
+    int64_t key_bytes;       // u32 per voxel: k of the height
+    int64_t best_bytes;      // u64 per voxel: a root's smallest (max, min) this round, then what it hooks below
+    int64_t pick_bytes;      // u32 per voxel: a root's edge id
+    int64_t slices;          // domains: 1, or the z-slices in 2-D mode
+};
+inline WsPlan ws_plan(const int64_t* n, bool two_d) {
+    WsPlan p{};
+    p.voxels = n[0] * n[1] * n[2];
+    p.grid = ws_grid(p.voxels);
+    p.parent_bytes = p.key_bytes = p.pick_bytes = p.voxels * 4;
+    p.best_bytes = p.voxels * 8;
+    p.slices = two_d ? n[0] : 1;
+    return p;
+}
+
+// ---------------------------------------------------------------------------
 // the multi-GPU exchange's count matrix: counts_all[(src * world + dst) * 2]
 // rows and [.. + 1] nodes of src's table that dst owns
 // ---------------------------------------------------------------------------

@@ -1406,6 +1406,102 @@ def distance_transform(src, pitch=None, threshold=None, label=None, to_backgroun
                         float(np.array([info[3]], dtype=np.uint64).view(np.float64)[0]))
 
 
+WsInfo = collections.namedtuple('WsInfo', 'max_id n_zero rounds n_dropped')
+WS_MAX_VOXELS = 1 << 30
+
+
+def seeded_watershed(hmap, seeds, size_filter=0, two_d=False, begin=None, end=None, out=None, stream=None):
+    """ctg_seeded_watershed: the seeded watershed of the box [begin, end) of
+    ``hmap`` -> (labels, info).
+
+    ``hmap``: a (Z,Y,X) float32 numpy array or contiguous CUDA tensor; +-inf
+    are ordinary heights, a NaN in the box raises and writes nothing.
+    ``seeds``: of the same shape and kind, 32- or 64-bit integers, 0 = no seed.
+    The result is the minimum spanning forest of the box's 6-neighbour graph
+    (``two_d``: of every z-slice on its own) under the edge order of
+    include/ctg.h, the seeded voxels contracted into one root: every voxel gets
+    the label of the seed its tree hangs from, a label of minimal pass height;
+    a voxel whose domain holds no seed stays 0.  ``size_filter``: labels with
+    fewer voxels in a domain become 0 and the flood runs again from the
+    survivors (elf's apply_size_filter).  ``labels``: box-shaped uint64 (an
+    int64 tensor for tensors).  ``out`` writes into an existing one; it may be
+    ``seeds`` itself where they are 64-bit and the box is the whole array.
+    ``info``: (max_id, n_zero, rounds, n_dropped) -- the largest label written,
+    the voxels left 0, the rounds of the last flood, the labels dropped."""
+    on_dev = _is_torch(hmap)
+    if _is_torch(seeds) != on_dev:
+        raise ValueError('hmap and seeds must both be numpy arrays or both CUDA tensors')
+    if on_dev:
+        import torch
+        if not (hmap.is_cuda and hmap.is_contiguous()) or hmap.dtype != torch.float32:
+            raise ValueError('hmap must be a contiguous float32 CUDA tensor')
+        if not (seeds.is_cuda and seeds.is_contiguous()) or seeds.is_floating_point() or \
+                seeds.dtype == torch.bool or seeds.element_size() not in (4, 8):
+            raise ValueError('seeds must be a contiguous CUDA tensor of 32- or 64-bit integers')
+        bits = seeds.element_size() * 8
+    else:
+        hmap = np.asarray(hmap)
+        seeds = np.asarray(seeds)
+        if hmap.dtype != np.float32:
+            raise TypeError('hmap must be float32, got %s' % hmap.dtype)
+        if seeds.dtype not in (np.uint32, np.int32, np.uint64, np.int64):
+            raise TypeError('seeds must be 32- or 64-bit integers, got %s' % seeds.dtype)
+        bits = seeds.dtype.itemsize * 8
+    shape = tuple(hmap.shape)
+    if len(shape) != 3:
+        raise ValueError('hmap must be 3-D, got shape %s' % (shape,))
+    if tuple(seeds.shape) != shape:
+        raise ValueError('seeds shape %s != hmap shape %s' % (tuple(seeds.shape), shape))
+    if not 0 <= int(size_filter) < 1 << 64:
+        raise ValueError('size_filter must be a uint64 value, got %r' % (size_filter,))
+    for box in (begin, end):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end must have 3 entries')
+    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
+    e = list(shape) if end is None else [int(v) for v in end]
+    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
+        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
+    oshape = tuple(hi - lo for lo, hi in zip(b, e))
+    if oshape[0] * oshape[1] * oshape[2] > WS_MAX_VOXELS:
+        raise ValueError('a box holds at most 2^30 voxels, got %s' % (oshape,))
+    in_place = out is seeds
+    if in_place and (bits != 64 or oshape != shape):
+        raise ValueError('out may be the seeds only where they are 64-bit and the box is the whole array')
+    if not on_dev:
+        if np.isnan(hmap[b[0]:e[0], b[1]:e[1], b[2]:e[2]]).any():
+            raise ValueError('the heights of the box hold a NaN')
+        hmap = np.ascontiguousarray(hmap)
+        if in_place and not seeds.flags.c_contiguous:
+            raise ValueError('seeds written in place must be contiguous')
+        seeds = np.ascontiguousarray(seeds)
+        if in_place:
+            out = seeds
+    if out is None:
+        if on_dev:
+            out = torch.empty(oshape, dtype=torch.int64, device=hmap.device)
+        else:
+            out = np.empty(oshape, dtype=np.uint64)
+    else:
+        if _is_torch(out) != on_dev:
+            raise ValueError('out must be of the same kind as hmap (numpy array or CUDA tensor)')
+        if on_dev:
+            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
+        else:
+            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
+        if not ok or tuple(out.shape) != oshape:
+            raise ValueError('out must be a contiguous 64-bit integer array of the shape of the box %s' % (oshape,))
+    lib = L.load()
+    L.init_device()
+    if stream is None:
+        stream = _current_stream(on_dev)
+    info = (ctypes.c_uint64 * 4)()
+    rc = lib.ctg_seeded_watershed(_ptr(hmap), _ptr(seeds), bits, _shape_arr(shape), _shape_arr(b), _shape_arr(e),
+                                  L.CTG_WS_2D if two_d else 0, int(size_filter), _ptr(out),
+                                  L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, info)
+    L.check(rc, 'ctg_seeded_watershed')
+    return out, WsInfo(int(info[0]), int(info[1]), int(info[2]), int(info[3]))
+
+
 def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_offset=0, noise_amp=0.1,
                  with_boundary=True, device=None):
     """Generate the synthetic volume directly in HBM (torch tensors)."""

@@ -50,6 +50,9 @@
  *                                        watershed/watershed.py:140-161,
  *                                        distances/object_distances.py:109-113,
  *                                        morphology/region_centers.py:122
+ *   ctg_seeded_watershed              <- vigra.analysis.watershedsNew(hmap, seeds=...) and the
+ *                                        size filter of elf's watershed,
+ *                                        watershed/watershed_from_seeds.py:143-204
  *
  * Conventions: plain pointers and sizes; ``mem`` says whether array
  * arguments live in host memory (CTG_MEM_HOST) or in device memory of the
@@ -83,8 +86,8 @@
  *     ctg_merge_morphology, ctg_morphology_rows, ctg_region_features,
  *     ctg_merge_region_features, ctg_region_rows, ctg_assignment_dense,
  *     ctg_assignment_sparse, ctg_apply_assignment, ctg_threshold_components,
- *     ctg_merge_assignments, ctg_distance_transform (with or without info, host
- *     or device memory) and ctg_mgpu_merge.
+ *     ctg_merge_assignments, ctg_distance_transform and ctg_seeded_watershed
+ *     (with or without info, host or device memory) and ctg_mgpu_merge.
  *   - Calls that return with their work queued on ``stream`` (device memory
  *     only, no scratch of the library's pool): ctg_map_edge_ids with
  *     CTG_MEM_DEVICE, ctg_synth_volume, ctg_synth_affinities,
@@ -113,7 +116,7 @@
  *     where it succeeds.  A call that fails with CTG_ERR_HIP after it queued
  *     work (a launch or copy that HIP refused) may return with that work queued
  *     and its scratch back in the pool -- ctg_distance_transform,
- *     ctg_rag_blocks, the adjacency filter and ctg_mgpu_merge wait even then;
+ *     ctg_seeded_watershed, ctg_rag_blocks, the adjacency filter and ctg_mgpu_merge wait even then;
  *     after such an error synchronise the stream before the next call.
  */
 #ifndef CTG_H_
@@ -654,6 +657,74 @@ int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, u
 int ctg_distance_transform(const void* src, int src_kind, int src_bits, const int64_t* shape, const int64_t* begin,
                            const int64_t* end, double threshold, uint64_t label, const double* pitch, int flags,
                            void* out, int mem, void* stream, uint64_t* info);
+
+/*
+ * The seeded watershed of a box: every voxel takes the label of the seed it is
+ * flooded from.
+ *
+ * ctg_seeded_watershed <- vigra.analysis.watershedsNew(hmap, seeds=...) of
+ *                         _ws_block / _ws_block_masked
+ *                         (watershed/watershed_from_seeds.py:143-204), of
+ *                         watershed/watershed.py:227,246,
+ *                         two_pass_watershed.py:166,207, fit_to_hmap
+ *                         (utils/volume_utils.py:313,332) and
+ *                         postprocess/filling_size_filter.py:134, with the size
+ *                         filter of elf's watershed
+ *   hmap        the (Z,Y,X) float32 heights.  +-inf are ordinary values; a NaN in
+ *               the box is CTG_ERR_ARG, found before anything is written
+ *   seeds, seed_bits   the (Z,Y,X) uint32 or uint64 seeds (seed_bits 32 / 64), 0 =
+ *               no seed; a label may be 2^32 or above
+ *               shape / begin / end as ctg_label_overlaps (NULL: the whole array)
+ *   flags       CTG_WS_2D   only the y and x edges exist: every z-slice of the box
+ *                           floods on its own
+ *   size_filter 0 (none), or the voxels a label must have to stay (below)
+ *   out         box-shaped uint64.  It may be `seeds` itself where the seeds are
+ *               64-bit and the box is the whole array (vigra's out=labels, the
+ *               in-place dataset of watershed_from_seeds); it must not overlap
+ *               the seeds in any other way
+ *   info        NULL, or 4 host words: [0] the largest label written, [1] the
+ *               voxels left 0, [2] the rounds of the last flood, [3] the labels
+ *               the size filter dropped (counted per domain)
+ *
+ * The result is defined by a rule, not by an execution order.  The voxels of
+ * the box are the nodes of a graph whose edges join 6-neighbours (with
+ * CTG_WS_2D the y and x neighbours).  k(h) is the order-preserving u32 image of
+ * a float32: -0 is taken as +0, a value with the sign bit set maps to ~bits,
+ * any other to bits | 0x80000000.  lin is the C-order index inside the box; the
+ * id of an edge is 3 * lin(its lower voxel) + axis (z 0, y 1, x 2).  Edges are
+ * strictly ordered by the triple
+ *     ( max(k(h_u), k(h_v)), min(k(h_u), k(h_v)), id ).
+ * The result is the minimum spanning forest of the graph under that order with
+ * all seeded voxels contracted into one root: take the edges in ascending
+ * order and join the two sets unless they are one set already or both hold a
+ * seed (Kruskal).  A voxel takes the label of the seeded voxel its tree hangs
+ * from; a seeded voxel keeps its label; a voxel whose domain (the box, with
+ * CTG_WS_2D its slice) holds no seed stays 0.
+ * Every voxel so gets a label whose pass height -- the smallest, over the paths
+ * to a seed, of the largest height on the path -- is minimal over all seeds.
+ * vigra's priority flood with FIFO ties gives the same label wherever one
+ * label alone attains that minimum, and may differ only where two labels tie
+ * in it: there this rule splits by the lower end's height and then along
+ * raster order, not by arrival time.
+ * size_filter [UPSTREAM, unverified: elf's apply_size_filter restated]: after
+ * the flood every label with fewer than size_filter voxels in a domain becomes
+ * 0 there, its seeds included, and the flood runs again with the surviving
+ * segments, whole, as seeds; where nothing survives the domain is all 0.
+ *
+ * Argument errors, found before any GPU work: a null hmap / seeds / shape /
+ * out, a box outside the array, a box of more than 2^30 voxels (an edge id
+ * must fit 32 bits), a bad seed_bits, flag or mem, an `out` that is the seeds
+ * where that is not allowed: CTG_ERR_ARG.  An empty box writes nothing (info is
+ * zeroed) and succeeds.  The call uses call-sized buffers only (20 bytes per
+ * voxel): a CTG_DEFER_STATS handle of the same device stays valid across it.
+ * ctg_last_timings of a profiled call, summed over the rounds and both floods:
+ * [0] init, [1] pick and hook, [2] apply and chase, [3] size filter, [4] write,
+ * [6] first launch to last.
+ */
+#define CTG_WS_2D 1
+int ctg_seeded_watershed(const float* hmap, const void* seeds, int seed_bits, const int64_t* shape,
+                         const int64_t* begin, const int64_t* end, int flags, uint64_t size_filter, uint64_t* out,
+                         int mem, void* stream, uint64_t* info);
 
 /* position of each query (u,v) in the sorted global edge table, -1 if absent */
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global,
