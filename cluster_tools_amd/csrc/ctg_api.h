@@ -3,8 +3,11 @@
 // and morphology; ctg_api_cc.hip: the thresholded components;
 // ctg_api_edt.hip: the distance transform; ctg_api_ws.hip: the seeded
 // watershed; ctg_api_mgpu.hip: the multi-GPU exchange): the call scaffold, the
-// status of a HIP error, inputs and outputs that may live on the host, and the
-// dense relabelling of (u,v) pair lists.  No rocPRIM here: the two helpers
+// status of a HIP error, the mem check, inputs and outputs that may live on the
+// host, the prologue of a dense-volume call (DenseCall: box, extent, VolBox,
+// staging and output by element width), a call's device words read back, and
+// the dense relabelling of (u,v) pair lists.  Every scope that owns pool blocks
+// declares a StreamWait (ctg_buffers.h) after them.  No rocPRIM here: the two helpers
 // that sort (sort_unique_u64, and with it unique_candidates) are defined in
 // ctg_api.hip.
 #pragma once
@@ -25,8 +28,21 @@ int hip_status(hipError_t e, const char* who, int oom_status = CTG_ERR_NOMEM);
 int box_of(const char* who, const int64_t* shape, const int64_t* begin, const int64_t* end, int64_t max_voxels,
            CallBox* box);
 
+// mem is CTG_MEM_HOST or CTG_MEM_DEVICE, or the error is set
+inline bool mem_ok(const char* who, int mem) {
+    if (mem == CTG_MEM_HOST || mem == CTG_MEM_DEVICE) return true;
+    set_error(std::string(who) + ": mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
+    return false;
+}
+
 // a host volume into the workspace's staging slot; a device one as it is
 int stage_in(GrowBuf& stage, const void* src, size_t bytes, int mem, hipStream_t s, const void** dev);
+// `bytes` of a call's device words into host, after everything queued on s
+inline int read_words(const void* ptr, size_t bytes, hipStream_t s, void* host) {
+    CTG_CHECK(hipMemcpyAsync(host, ptr, bytes, hipMemcpyDeviceToHost, s));
+    CTG_CHECK(hipStreamSynchronize(s));
+    return CTG_OK;
+}
 // one u32 device word, after everything queued on s
 int read_word(Workspace& w, SmallSlot i, hipStream_t s, int64_t* v);
 // the phase times of a profiled call: scan, pack, sort, segment, reduce, nodes, total
@@ -132,6 +148,37 @@ struct DenseOut {
     }
 };
 
+// The prologue of a dense-volume call (components, distance transform,
+// watershed): open() is box_of plus what the entry points derive from the box;
+// in() stages an array-sized input and out() opens the box-sized output, each
+// of `width` bytes per element.  s is set once the call has begun.
+struct DenseCall {
+    const char* who;
+    int mem;
+    hipStream_t s = nullptr;
+    CallBox box{};
+    int64_t n[3] = {}, V = 0;   // the box's extent and voxels
+    size_t elems = 0;           // the array's elements
+    VolBox vol{};
+    int open(const int64_t* shape, const int64_t* begin, const int64_t* end, int64_t max_voxels) {
+        const int rc = box_of(who, shape, begin, end, max_voxels, &box);
+        if (rc) return rc;
+        for (int k = 0; k < 3; ++k) n[k] = box.e[k] - box.b[k];
+        V = box.voxels;
+        elems = (size_t)shape[0] * shape[1] * shape[2];
+        vol = vol_box(shape, box);
+        return CTG_OK;
+    }
+    template <class T>
+    int in(DevInput<T>& d, const void* src, size_t width) const {
+        return d.put((const T*)src, elems * width, mem, s, who);
+    }
+    template <class T>
+    int out(DenseOut<T>& o, void* dst, size_t width) const {
+        return hip_status(o.open((T*)dst, (size_t)V * width, mem, false, s), who);
+    }
+};
+
 // (u,v) pair lists with labels >= 2^32 (merge / union inputs): the sort packs
 // (u,v) into one 64-bit key, so the endpoints are replaced by their rank in
 // the sorted unique endpoint table (monotone) and mapped back afterwards.
@@ -164,6 +211,7 @@ int unique_candidates(Workspace& w, int64_t cap, int64_t bound, unsigned end_bit
                       int64_t* N) {
     for (int attempt = 0; attempt < 3; ++attempt) {
         DevBuf<uint64_t> cand(cap * 8);
+        StreamWait wait{s};
         if (!cand || !nodes.alloc(cap * 8)) {
             set_error(nomem_msg);
             return CTG_ERR_NOMEM;
@@ -174,12 +222,15 @@ int unique_candidates(Workspace& w, int64_t cap, int64_t bound, unsigned end_bit
         CTG_CHECK(hipStreamSynchronize(s));
         const int64_t m = (int64_t)w.counters_host->n_records;
         if (m > cap) {
+            wait.disarm();
             cap = candidate_cap_regrow(m, bound);
             nodes.reset();
             continue;
         }
         CTG_CHECK(sort_unique_u64(w, cand, m, nodes, w.small + SLOT_NODES, s, end_bit));
-        return read_word(w, SLOT_NODES, s, N);
+        const int rc = read_word(w, SLOT_NODES, s, N);
+        if (rc == CTG_OK) wait.disarm();
+        return rc;
     }
     set_error(overflow_msg);
     return CTG_ERR_NOMEM;

@@ -120,11 +120,12 @@ using namespace ctg;
 static int reduce_pairs(ApiCall& c, ReduceJob& J, const uint64_t* dk, const char* who, ctg_result** out) {
     Workspace& w = c.w();
     hipStream_t s = c.s;
+    DensePairs dp;
+    StreamWait wait{s};   // (for the caller's inputs too: its own guard covers only its staging)
     CTG_CHECK(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
     CTG_CHECK(launch_max_pairs(J.n, dk, &w.counters->max_v, s));
     CTG_CHECK(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
-    DensePairs dp;
     J.pairs = dk;
     J.max_v = w.counters_host->max_v;
     if (J.max_v >> 32) {
@@ -138,7 +139,9 @@ static int reduce_pairs(ApiCall& c, ReduceJob& J, const uint64_t* dk, const char
     if (e == hipSuccess) e = dp.map_back(c.r.get(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     const int rc = hip_status(e, who, CTG_ERR_HIP);
-    return rc ? rc : c.end(false, out);
+    if (rc) return rc;
+    wait.disarm();
+    return c.end(false, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -298,9 +301,11 @@ int ctg_unique_values(const uint64_t* values, int64_t n, int mem, void* stream, 
         return CTG_ERR_NOMEM;
     }
     DevInput<uint64_t> in;
+    StreamWait wait{s};
     if ((rc = in.put(values, (size_t)n * 8, mem, s, "ctg_unique_values")) != CTG_OK) return rc;
     CTG_CHECK(sort_unique_u64(w, in, n, r->nodes, w.small + SLOT_NODES, s));
     if ((rc = read_word(w, SLOT_NODES, s, &r->n_nodes)) != CTG_OK) return rc;
+    wait.disarm();
     return c.end(false, out);
 }
 
@@ -320,6 +325,7 @@ int ctg_merge_stats(const uint64_t* keys, const double* sums, const uint32_t* re
     DevInput<uint64_t> dk;
     DevInput<double> ds;
     DevInput<uint32_t> dr;
+    StreamWait wait{s};
     rc = dk.put(keys, (size_t)n * 16, mem, s, "ctg_merge_stats");
     if (!rc) rc = ds.put(sums, (size_t)n * 16, mem, s, "ctg_merge_stats");
     if (!rc) rc = dr.put(records, (size_t)n * WREC_WORDS * 4, mem, s, "ctg_merge_stats");
@@ -337,7 +343,8 @@ int ctg_merge_stats(const uint64_t* keys, const double* sums, const uint32_t* re
     J.keep_stats = keep_stats;
     J.scale = (double)NBINS / (hist_hi - hist_lo);
     J.offset = hist_lo;
-    return reduce_pairs(c, J, dk, "ctg_merge_stats", out);
+    if ((rc = reduce_pairs(c, J, dk, "ctg_merge_stats", out)) == CTG_OK) wait.disarm();
+    return rc;
 }
 
 int ctg_merge_feature_rows(const uint64_t* ids, const double* rows, int64_t n, int64_t id_begin, int64_t id_end,
@@ -361,6 +368,7 @@ int ctg_merge_feature_rows(const uint64_t* ids, const double* rows, int64_t n, i
     DevInput<uint64_t> di;
     DevInput<double> dr;
     DevBuf<double> own_o;
+    StreamWait wait{s};
     double* dout = out;
     rc = di.put(ids, (size_t)n * 8, mem, s, "ctg_merge_feature_rows");
     if (!rc) rc = dr.put(rows, (size_t)n * N_FEATURES * 8, mem, s, "ctg_merge_feature_rows");
@@ -387,6 +395,7 @@ int ctg_merge_feature_rows(const uint64_t* ids, const double* rows, int64_t n, i
     }
     if (host) CTG_CHECK(hipMemcpyAsync(out, dout, E * N_FEATURES * 8, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     if (n && w.small_host[SLOT_BAD_ID]) {
         set_error("ctg_merge_feature_rows: an edge id lies outside [id_begin, id_end)");
         return CTG_ERR_ARG;
@@ -405,6 +414,7 @@ int ctg_unique_pairs(const uint64_t* pairs, int64_t n, int mem, void* stream, ct
     if (rc) return rc;
     if (n == 0) return c.empty(empty_result, out);
     DevInput<uint64_t> dk;
+    StreamWait wait{c.s};
     if ((rc = dk.put(pairs, (size_t)n * 16, mem, c.s, "ctg_unique_pairs")) != CTG_OK) return rc;
     ReduceJob J{};
     J.n = n;
@@ -412,7 +422,8 @@ int ctg_unique_pairs(const uint64_t* pairs, int64_t n, int mem, void* stream, ct
     J.need_adj = 0;
     J.scale = 1.0;
     J.offset = 0.0;
-    return reduce_pairs(c, J, dk, "ctg_unique_pairs", out);
+    if ((rc = reduce_pairs(c, J, dk, "ctg_unique_pairs", out)) == CTG_OK) wait.disarm();
+    return rc;
 }
 
 int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global, const uint64_t* query, int64_t n_query,
@@ -430,6 +441,7 @@ int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global, const uint6
     }
     DevInput<uint64_t> g, q;
     DevBuf<int64_t> o(n_query * 8);
+    StreamWait wait{s};
     int rc = g.put(global_edges, (size_t)n_global * 16, CTG_MEM_HOST, s, "ctg_map_edge_ids");
     if (!rc) rc = q.put(query, (size_t)n_query * 16, CTG_MEM_HOST, s, "ctg_map_edge_ids");
     if (rc) return rc;
@@ -440,6 +452,7 @@ int ctg_map_edge_ids(const uint64_t* global_edges, int64_t n_global, const uint6
     CTG_CHECK(launch_find_edges(g, n_global, q, n_query, o, s));
     CTG_CHECK(hipMemcpyAsync(out_ids, o, n_query * 8, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     return CTG_OK;
 }
 

@@ -23,13 +23,6 @@ struct UfBuffers {
     }
 };
 
-// the call's words after everything queued on s
-int read_words(const UfBuffers& b, hipStream_t s, uint32_t* h) {
-    CTG_CHECK(hipMemcpyAsync(h, b.words.p, CC_WORDS * 4, hipMemcpyDeviceToHost, s));
-    CTG_CHECK(hipStreamSynchronize(s));
-    return CTG_OK;
-}
-
 int cap_error(const char* who) {
     set_error(std::string(who) + ": a union-find chain passed its step cap (the parent table is corrupt)");
     return CTG_ERR_HIP;
@@ -61,41 +54,32 @@ int ctg_threshold_components(const void* data, int data_kind, const void* mask, 
         set_error("ctg_threshold_components: connectivity must be 1, 2 or 3");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_threshold_components: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
-    CallBox box;
-    int rc = box_of(who, shape, begin, end, CC_MAX_NODES, &box);
+    if (!mem_ok(who, mem)) return CTG_ERR_ARG;
+    DenseCall D{who, mem};
+    int rc = D.open(shape, begin, end, CC_MAX_NODES);
     if (rc) return rc;
-    const int64_t V = box.voxels;
+    const int64_t V = D.V;
     if (V == 0) return CTG_OK;
     if ((rc = c.begin(stream)) != CTG_OK) return rc;
-    hipStream_t s = c.s;
-    const int64_t n[3] = {box.e[0] - box.b[0], box.e[1] - box.b[1], box.e[2] - box.b[2]};
-    const CcGrid G = cc_grid(n);
-    const size_t elems = (size_t)shape[0] * shape[1] * shape[2];
+    hipStream_t s = D.s = c.s;
+    const CcGrid G = cc_grid(D.n);
     DevInput<char> dd;
     DevInput<uint8_t> dm;
-    if ((rc = dd.put((const char*)data, elems * (data_kind == CTG_DATA_U8 ? 1 : 4), mem, s, who)) != CTG_OK) return rc;
-    if (mask && (rc = dm.put((const uint8_t*)mask, elems, mem, s, who)) != CTG_OK) return rc;
     UfBuffers b;
     DenseOut<uint64_t> o;
+    StreamWait wait{s};
+    if ((rc = D.in(dd, data, data_kind == CTG_DATA_U8 ? 1 : 4)) != CTG_OK) return rc;
+    if (mask && (rc = D.in(dm, mask, 1)) != CTG_OK) return rc;
     if (!b.alloc(V)) return hip_status(hipErrorOutOfMemory, who);
-    if ((rc = hip_status(o.open(out, (size_t)V * 8, mem, false, s), who)) != CTG_OK) return rc;
+    if ((rc = D.out(o, out, 8)) != CTG_OK) return rc;
     uint32_t h[CC_WORDS] = {};
     h[CC_W_MIN] = 0xFFFFFFFFu;   // (f2ord words: the minimum starts at the top, the maximum at 0)
     CTG_CHECK(hipMemcpyAsync(b.words.p, h, sizeof(h), hipMemcpyHostToDevice, s));
     CcArgs A{};
     A.data = dd.p;
     A.mask = mask ? dm.p : nullptr;
-    A.s_z = shape[1] * shape[2];
-    A.s_y = shape[2];
-    A.base = box.b[0] * A.s_z + box.b[1] * A.s_y + box.b[2];
-    for (int k = 0; k < 3; ++k) {
-        A.n[k] = (uint32_t)n[k];
-        A.nt[k] = (uint32_t)G.nt[k];
-    }
+    A.box = D.vol;
+    for (int k = 0; k < 3; ++k) A.nt[k] = (uint32_t)G.nt[k];
     A.threshold = threshold;
     A.mode = mode;
     A.words = b.words;
@@ -115,7 +99,8 @@ int ctg_threshold_components(const void* data, int data_kind, const void* mask, 
     CTG_CHECK(launch_uf_write(b.parent, b.rank, b.seg, V, 1, o.d, s));
     ev.mark(6);
     CTG_CHECK(o.copy_back(s));
-    if ((rc = read_words(b, s, h)) != CTG_OK) return rc;
+    if ((rc = read_words(b.words, sizeof(h), s, h)) != CTG_OK) return rc;
+    wait.disarm();
     if (c.w().profiling && (rc = read_phase_times(c.w(), s)) != CTG_OK) return rc;
     if (h[CC_W_ERR] & CC_ERR_CAP) return cap_error(who);
     *n_components = h[CC_W_TOTAL];
@@ -131,10 +116,7 @@ int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, u
         set_error("ctg_merge_assignments: bad arguments");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_merge_assignments: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
+    if (!mem_ok(who, mem)) return CTG_ERR_ARG;
     if (!cc_nodes_fit(n_labels) || n >= (1ll << 38)) {
         set_error("ctg_merge_assignments: 2^32 labels or more, or 2^38 pairs or more");
         return CTG_ERR_UNSUPPORTED;
@@ -149,12 +131,14 @@ int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, u
     hipStream_t s = c.s;
     const int64_t N = (int64_t)n_labels;
     DevInput<uint64_t> dp;
+    UfBuffers b;
+    DenseOut<uint64_t> o;
+    StreamWait wait{s};
     if ((rc = dp.put(pairs, (size_t)n * 16, mem, s, who)) != CTG_OK) return rc;
     if (n > 0 && ((uintptr_t)dp.p & 15u)) {
         set_error("ctg_merge_assignments: pairs must be aligned to 16 bytes");
         return CTG_ERR_ARG;
     }
-    UfBuffers b;
     if (!b.alloc(N)) return hip_status(hipErrorOutOfMemory, who);
     uint32_t h[CC_WORDS] = {};
     CTG_CHECK(hipMemsetAsync(b.words.p, 0, CC_WORDS * 4, s));
@@ -165,13 +149,12 @@ int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, u
     CTG_CHECK(launch_uf_pairs(dp, n, b.parent, (uint32_t)n_labels, b.words, s));
     ev.mark(2);
     // the pairs are checked before the table is touched
-    if ((rc = read_words(b, s, h)) != CTG_OK) return rc;
+    if ((rc = read_words(b.words, sizeof(h), s, h)) != CTG_OK) return rc;
     if (h[CC_W_ERR] & CC_ERR_PAIR) {
         set_error("ctg_merge_assignments: a pair member is 0 or not below n_labels (" + std::to_string(n_labels) + ")");
         return CTG_ERR_ARG;
     }
     if (h[CC_W_ERR] & CC_ERR_CAP) return cap_error(who);
-    DenseOut<uint64_t> o;
     if ((rc = hip_status(o.open(table, (size_t)N * 8, mem, false, s), who)) != CTG_OK) return rc;
     CTG_CHECK(launch_uf_flatten(b.parent, N, b.rank, b.seg, b.words, s));
     ev.mark(3);
@@ -182,7 +165,8 @@ int ctg_merge_assignments(const uint64_t* pairs, int64_t n, uint64_t n_labels, u
     ev.mark(5);
     ev.mark(6);
     CTG_CHECK(o.copy_back(s));
-    if ((rc = read_words(b, s, h)) != CTG_OK) return rc;
+    if ((rc = read_words(b.words, sizeof(h), s, h)) != CTG_OK) return rc;
+    wait.disarm();
     if (c.w().profiling && (rc = read_phase_times(c.w(), s)) != CTG_OK) return rc;
     if (h[CC_W_ERR] & CC_ERR_CAP) return cap_error(who);
     *max_id = (uint64_t)h[CC_W_TOTAL] - 1;

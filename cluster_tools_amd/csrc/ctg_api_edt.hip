@@ -11,21 +11,6 @@
 
 using namespace ctg;
 
-// The passes' scratch.  The pool knows nothing of streams, so the blocks go
-// back to it only once the stream is idle, on every return path (as AdjFilter,
-// BlockTables and MergeScratch do): a call on another stream could otherwise
-// draw them while the passes still write them.
-struct EdtScratch {
-    hipStream_t s;
-    DevBuf<uint16_t> dx;
-    DevBuf<uint32_t> dyx;
-    DevBuf<uint64_t> stack;
-    DevBuf<unsigned long long> words;   // info[4], then the last pass's partials
-    ~EdtScratch() {
-        if (dx) hipStreamSynchronize(s);
-    }
-};
-
 extern "C" {
 
 int ctg_distance_transform(const void* src, int src_kind, int src_bits, const int64_t* shape, const int64_t* begin,
@@ -50,10 +35,7 @@ int ctg_distance_transform(const void* src, int src_kind, int src_bits, const in
         set_error("ctg_distance_transform: unknown flag");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_distance_transform: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
+    if (!mem_ok(who, mem)) return CTG_ERR_ARG;
     double p[3] = {1.0, 1.0, 1.0};
     for (int k = 0; pitch && k < 3; ++k) {
         p[k] = pitch[k];
@@ -62,50 +44,47 @@ int ctg_distance_transform(const void* src, int src_kind, int src_bits, const in
             return CTG_ERR_ARG;
         }
     }
-    CallBox box;
-    int rc = box_of(who, shape, begin, end, EDT_MAX_VOXELS, &box);
+    DenseCall D{who, mem};
+    int rc = D.open(shape, begin, end, EDT_MAX_VOXELS);
     if (rc) return rc;
-    const int64_t n[3] = {box.e[0] - box.b[0], box.e[1] - box.b[1], box.e[2] - box.b[2]};
+    const int64_t* n = D.n;
     if (n[0] >= EDT_MAX_AXIS || n[1] >= EDT_MAX_AXIS || n[2] >= EDT_MAX_AXIS) {
         set_error("ctg_distance_transform: boxes with an axis of 32768 or more are not supported");
         return CTG_ERR_UNSUPPORTED;
     }
-    const int64_t V = box.voxels;
+    const int64_t V = D.V;
     if (V == 0) return CTG_OK;
     if ((rc = c.begin(stream)) != CTG_OK) return rc;
-    hipStream_t s = c.s;
+    hipStream_t s = D.s = c.s;
     const bool two_d = (flags & CTG_EDT_2D) != 0, out_d2 = (flags & CTG_EDT_OUT_D2) != 0;
     const EdtPasses passes = edt_passes(n, two_d);
     // the last pass writes the result: the z pass, or the y pass where there is none
     const EdtLinePlan py = edt_line_plan(n[1], n[0], n[2]), pz = edt_line_plan(n[0], n[1], n[2]);
     const EdtLinePlan& last = passes.z ? pz : py;
-    const size_t elems = (size_t)shape[0] * shape[1] * shape[2];
     DevInput<char> ds;
-    DenseOut<char> o;   // (both before the scratch: their blocks, too, are freed after its wait)
-    if ((rc = ds.put((const char*)src, elems * (size_t)(src_bits / 8), mem, s, who)) != CTG_OK) return rc;
-    EdtScratch scratch{s};
-    DevBuf<uint16_t>& dx = scratch.dx;
-    DevBuf<uint32_t>& dyx = scratch.dyx;
-    DevBuf<uint64_t>& stack = scratch.stack;
-    DevBuf<unsigned long long>& words = scratch.words;
+    DenseOut<char> o;
+    DevBuf<uint16_t> dx;
+    DevBuf<uint32_t> dyx;
+    DevBuf<uint64_t> stack;
+    DevBuf<unsigned long long> words;   // info[4], then the last pass's partials
+    StreamWait wait{s};
+    if ((rc = D.in(ds, src, (size_t)(src_bits / 8))) != CTG_OK) return rc;
     const int64_t stack_bytes = std::max<int64_t>(passes.y ? py.stack_bytes : 0, passes.z ? pz.stack_bytes : 0);
     if (!dx.alloc((size_t)V * 2) || (passes.y && passes.z && !dyx.alloc((size_t)V * 4)) ||
         (stack_bytes && !stack.alloc((size_t)stack_bytes)) ||
         !words.alloc((size_t)(4 + last.grid * EDT_PART_WORDS) * 8))
         return hip_status(hipErrorOutOfMemory, who);
-    if ((rc = hip_status(o.open((char*)out, (size_t)V * (out_d2 ? 8 : 4), mem, false, s), who)) != CTG_OK) return rc;
+    if ((rc = D.out(o, out, out_d2 ? 8 : 4)) != CTG_OK) return rc;
     CTG_CHECK(hipMemsetAsync(words.p, 0, 4 * 8, s));
     EdtSrc A{};
     A.src = ds.p;
-    A.s_z = shape[1] * shape[2];
-    A.s_y = shape[2];
-    A.base = box.b[0] * A.s_z + box.b[1] * A.s_y + box.b[2];
+    A.box = D.vol;
     A.threshold = (float)threshold;
     A.label = label;
     A.invert = (flags & CTG_EDT_TO_BACKGROUND) != 0;
     EdtLineArgs L{};
     for (int k = 0; k < 3; ++k) {
-        A.n[k] = L.n[k] = (uint32_t)n[k];
+        L.n[k] = A.box.n[k];
         L.p[k] = p[k];
     }
     L.diag2 = edt_diag2(n, p, two_d);
@@ -140,7 +119,7 @@ int ctg_distance_transform(const void* src, int src_kind, int src_bits, const in
     ev.mark(6);
     CTG_CHECK(o.copy_back(s));
     if (info) CTG_CHECK(hipMemcpyAsync(info, words.p, 4 * 8, hipMemcpyDeviceToHost, s));
-    // always waited for, a device-resident call without info too (EdtScratch)
+    // always waited for, a device-resident call without info too
     CTG_CHECK(hipStreamSynchronize(s));
     if (c.w().profiling && (rc = read_phase_times(c.w(), s)) != CTG_OK) return rc;
     return CTG_OK;

@@ -97,11 +97,10 @@ struct MergeScratch {
     DevBuf<uint32_t> touched;                      // e_cnt
     DevBuf<uint32_t> keep, fpos;                   // e_cnt + M
     size_t m = 0, own = 0, slots = 0;              // the three lengths, at least 1
+    StreamWait wait{s, false};                     // armed once alloc() ran
     explicit MergeScratch(hipStream_t stream) : s(stream) {}
-    ~MergeScratch() {
-        if (m) hipStreamSynchronize(s);
-    }
     bool alloc(const ExchangePlan& p) {
+        wait.arm();
         m = (size_t)std::max<int64_t>(p.recv.rows(), 1);
         own = (size_t)std::max<int64_t>(p.e_cnt, 1);
         slots = (size_t)std::max<int64_t>(p.e_cnt + p.recv.rows(), 1);

@@ -317,9 +317,7 @@ struct AdjFilter {
     hipStream_t s;
     ResultPtr graph;
     DevBuf<unsigned long long> bloom;
-    ~AdjFilter() {
-        if (bloom) hipStreamSynchronize(s);
-    }
+    StreamWait wait{s, false};   // armed once the filter exists
 };
 
 static int adjacency_filter(ScanParams& P, const int64_t* shape, const int64_t* own_begin, const int64_t* own_end,
@@ -344,6 +342,7 @@ static int adjacency_filter(ScanParams& P, const int64_t* shape, const int64_t* 
         set_error("ctg_rag_features: out of memory (adjacency filter)");
         return CTG_ERR_NOMEM;
     }
+    f.wait.arm();
     if ((rc = hip_status(launch_build_bloom(g->edges, g->n_edges, f.bloom, blocks - 1, s), "ctg_rag_features",
                          CTG_ERR_HIP)) != CTG_OK)
         return rc;
@@ -406,7 +405,7 @@ struct BlockTables {
     hipStream_t s;
     DevBuf<BlockGeom> geom;
     DevBuf<uint32_t> prefix;
-    ~BlockTables() { hipStreamSynchronize(s); }
+    StreamWait wait{s};
 };
 
 static int upload_block_tables(const BlockPlan& plan, int n_blocks, hipStream_t s, BlockTables& t, ScanParams& P) {

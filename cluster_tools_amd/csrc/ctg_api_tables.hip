@@ -40,7 +40,8 @@ using AssignmentPtr = std::unique_ptr<ctg_assignment, AssignmentFree>;
 
 // A label volume of ctg_label_overlaps / ctg_morphology / ctg_region_features whose labels reach
 // 2^32: the box's sorted unique labels U and the whole array as 32-bit ranks in
-// U (monotone; voxels outside the box get some rank and are never read).
+// U (monotone; voxels outside the box get some rank and are never read).  The
+// ids are read until the call is done: the entry point's StreamWait follows its sides.
 struct DenseSide {
     ResultPtr U;
     DevBuf<uint32_t> ids;
@@ -69,11 +70,13 @@ static int dense_ignore_rank(const DenseSide& side, int* has_ignore, uint64_t* i
                              const char* who) {
     if (!side.U || !*has_ignore) return CTG_OK;
     DevBuf<uint32_t> rank(4);
+    StreamWait wait{s};
     uint32_t h = 0;
     if (!rank) return hip_status(hipErrorOutOfMemory, who);
     CTG_CHECK(launch_overlap_find(side.U->nodes, side.U->n_nodes, *ignore_label, rank, s));
     CTG_CHECK(hipMemcpyAsync(&h, rank.p, 4, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     *has_ignore = h != 0xFFFFFFFFu;
     *ignore_label = h;
     return CTG_OK;
@@ -110,6 +113,13 @@ static int dense_reentry(const char* who, const void** vol, int* bits, int n, in
     return CTG_OK;
 }
 
+// The epilogue of a table scan (ApiCall::end, table): it ends synchronised, so the call's guard waits no more.
+static int end_table(ApiCall& c, bool timed, StreamWait& wait, ctg_result** out) {
+    const int rc = c.end(timed, out, true);
+    if (rc == CTG_OK) wait.disarm();
+    return rc;
+}
+
 // ctg_merge_morphology and ctg_merge_region_features: n float64 rows of `cols` columns -> a result of `empty`'s kind
 // by `merge`.  (clear_first: the region call clears *out before its argument check, the morphology call after it.)
 static int merge_rows_entry(const char* who, const double* rows, int64_t n, int cols, int mem, void* stream,
@@ -132,6 +142,7 @@ static int merge_rows_entry(const char* who, const double* rows, int64_t n, int 
     if (n == 0) return c.end(false, out);
     hipStream_t s = c.s;
     DevInput<double> dr;
+    StreamWait wait{s};
     if ((rc = dr.put(rows, (size_t)n * cols * 8, mem, s, who)) != CTG_OK) return rc;
     int bad = 0;
     if ((rc = hip_status(merge(c.w(), dr, n, s, c.r.get(), &bad), who)) != CTG_OK) return rc;
@@ -140,6 +151,7 @@ static int merge_rows_entry(const char* who, const double* rows, int64_t n, int 
         return CTG_ERR_ARG;
     }
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     return c.end(false, out);
 }
 
@@ -173,14 +185,17 @@ static int rows_entry(const char* who, const ctg_result* r, uint64_t label_begin
     if (!rc) rc = range_first ? top_label() : range();
     if (rc) return rc;
     DenseOut<double> od, orw;
+    StreamWait wait{s};
     rc = hip_status(od.open(out, (size_t)n * cols * 8, mem, true, s), who);
     if (!rc) rc = hip_status(orw.open(rows, (size_t)N * cols * 8, mem, false, s), who);
     if (rc) return rc;
-    if (!od.d && !orw.d) return CTG_OK;
-    CTG_CHECK(launch(od.d, orw.d));
-    CTG_CHECK(od.copy_back(s));
-    CTG_CHECK(orw.copy_back(s));
-    CTG_CHECK(hipStreamSynchronize(s));
+    if (od.d || orw.d) {
+        CTG_CHECK(launch(od.d, orw.d));
+        CTG_CHECK(od.copy_back(s));
+        CTG_CHECK(orw.copy_back(s));
+        CTG_CHECK(hipStreamSynchronize(s));
+    }
+    wait.disarm();
     return CTG_OK;
 }
 
@@ -216,6 +231,7 @@ int ctg_label_overlaps(const void* labels, int label_bits, const void* values, i
     const void* vol[2] = {dl, dv};
     int bits[2] = {label_bits, value_bits};
     DenseSide d[2];
+    StreamWait wait{s};
     rc = dense_reentry(who, vol, bits, 2, 1, &with_ignore, &ignore_label, shape, b, e, stream,
                        [&](unsigned* over) {
                            return overlap_tables(w, vol[0], bits[0], vol[1], bits[1], shape, b, e, with_ignore,
@@ -227,7 +243,7 @@ int ctg_label_overlaps(const void* labels, int label_bits, const void* values, i
     CTG_CHECK(launch_overlap_map_back(r->n_edges, r->edges, d[0].U ? d[0].U->nodes : nullptr,
                                       d[0].U ? d[0].U->n_nodes : 0, d[1].U ? d[1].U->nodes : nullptr,
                                       d[1].U ? d[1].U->n_nodes : 0, s));
-    return c.end(r->n_records > 0, out, true);
+    return end_table(c, r->n_records > 0, wait, out);
 }
 
 int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n, int mem, void* stream,
@@ -249,6 +265,9 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
     hipStream_t s = c.s;
     ResultPtr& r = c.r;
     DevInput<uint64_t> dp, dc;
+    DensePairs dense;
+    DevBuf<uint64_t> key;
+    StreamWait wait{s};
     rc = dp.put(pairs, (size_t)n * 16, mem, s, "ctg_merge_overlaps");
     if (!rc) rc = dc.put(counts, (size_t)n * 8, mem, s, "ctg_merge_overlaps");
     if (rc) return rc;
@@ -256,7 +275,6 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
     CTG_CHECK(launch_max_pairs(n, dp, &w.counters->max_v, s));
     CTG_CHECK(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
-    DensePairs dense;
     const uint64_t* src = dp;
     if (w.counters_host->max_v >> 32) {
         if ((rc = dense.build(dp, n, s)) != CTG_OK) return rc;
@@ -266,12 +284,12 @@ int ctg_merge_overlaps(const uint64_t* pairs, const uint64_t* counts, int64_t n,
         }
         src = dense.dense;
     }
-    DevBuf<uint64_t> key((size_t)n * 8);
-    if (!key) return hip_status(hipErrorOutOfMemory, "ctg_merge_overlaps");
+    if (!key.alloc((size_t)n * 8)) return hip_status(hipErrorOutOfMemory, "ctg_merge_overlaps");
     CTG_CHECK(launch_overlap_pack(n, src, key, s));
     if ((rc = hip_status(overlap_reduce(w, key, dc, n, s, r.get()), "ctg_merge_overlaps")) != CTG_OK) return rc;
     CTG_CHECK(dense.map_back(r.get(), s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     r->n_records = n;
     return c.end(false, out);
 }
@@ -291,6 +309,7 @@ int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_e
     if (n == 0) return CTG_OK;
     hipStream_t s = (hipStream_t)stream;
     DenseOut<uint64_t> ol, oc;
+    StreamWait wait{s};
     int rc = hip_status(ol.open(out_labels, n * 8, mem, true, s), "ctg_max_overlaps");
     if (!rc) rc = hip_status(oc.open(out_counts, n * 8, mem, true, s), "ctg_max_overlaps");
     if (rc) return rc;
@@ -298,6 +317,7 @@ int ctg_max_overlaps(const ctg_result* r, uint64_t label_begin, uint64_t label_e
     CTG_CHECK(ol.copy_back(s));
     CTG_CHECK(oc.copy_back(s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     return CTG_OK;
 }
 
@@ -336,11 +356,12 @@ int ctg_morphology(const void* labels, int label_bits, const int64_t* shape, con
     const void* dl = nullptr;
     if ((rc = stage_in(w.stage[0], labels, (size_t)V * (label_bits / 8), mem, s, &dl)) != CTG_OK) return rc;
     DenseSide d;
+    StreamWait wait{s};
     rc = dense_reentry(   // (2: no ignore label here)
         who, &dl, &label_bits, 1, -1, nullptr, nullptr, shape, b, e, stream,
         [&](unsigned* over) { return morph_tables(w, dl, label_bits, shape, b, e, o, s, r, over); }, &d, r);
     if (rc) return rc;
-    return c.end(true, out, true);
+    return end_table(c, true, wait, out);
 }
 
 int ctg_merge_morphology(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
@@ -385,10 +406,7 @@ int ctg_region_features(const void* labels, int label_bits, const void* data, in
         set_error("ctg_region_features: data_kind must be CTG_DATA_F32 or CTG_DATA_U8");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_region_features: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
+    if (!mem_ok("ctg_region_features", mem)) return CTG_ERR_ARG;
     CallBox box;
     int rc = box_of(who, shape, begin, end, RECORD_LIMIT, &box);
     if (rc || (rc = c.begin(stream, empty_region)) != CTG_OK) return rc;
@@ -403,6 +421,7 @@ int ctg_region_features(const void* labels, int label_bits, const void* data, in
     if (!rc) rc = stage_in(w.stage[1], data, (size_t)V * (data_kind == CTG_DATA_U8 ? 1 : 4), mem, s, &dd);
     if (rc) return rc;
     DenseSide d;
+    StreamWait wait{s};
     rc = dense_reentry(who, &dl, &label_bits, 1, 0, &has_ignore, &ignore_label, shape, b, e, stream,
                        [&](unsigned* over) {
                            return region_tables(w, dl, label_bits, dd, data_kind, shape, b, e, has_ignore,
@@ -410,7 +429,7 @@ int ctg_region_features(const void* labels, int label_bits, const void* data, in
                        },
                        &d, r);
     if (rc) return rc;
-    return c.end(r->n_records > 0, out, true);
+    return end_table(c, r->n_records > 0, wait, out);
 }
 
 int ctg_merge_region_features(const double* rows, int64_t n, int mem, void* stream, ctg_result** out) {
@@ -452,10 +471,7 @@ int ctg_assignment_dense(const uint64_t* table, int64_t n, int mem, void* stream
         set_error("ctg_assignment_dense: bad arguments");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_assignment_dense: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
+    if (!mem_ok("ctg_assignment_dense", mem)) return CTG_ERR_ARG;
     int rc = c.begin(stream);
     if (rc) return rc;
     hipStream_t s = c.s;
@@ -465,6 +481,7 @@ int ctg_assignment_dense(const uint64_t* table, int64_t n, int mem, void* stream
     a->n = n;
     a->size = (uint64_t)n;
     DevBuf<unsigned long long> stat(16);
+    StreamWait wait{s};
     if (!stat || !(a->table = (uint64_t*)dev_alloc(std::max<size_t>((size_t)n * 8, 8))))
         return hip_status(hipErrorOutOfMemory, "ctg_assignment_dense");
     CTG_CHECK(hipMemsetAsync(stat.p, 0, 16, s));
@@ -475,6 +492,7 @@ int ctg_assignment_dense(const uint64_t* table, int64_t n, int mem, void* stream
     unsigned long long h[2] = {0, 0};
     CTG_CHECK(hipMemcpyAsync(h, stat.p, 16, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     a->max_value = h[1];
     *out = a.release();
     return CTG_OK;
@@ -489,10 +507,7 @@ int ctg_assignment_sparse(const uint64_t* keys, const uint64_t* values, int64_t 
         set_error("ctg_assignment_sparse: bad arguments");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_assignment_sparse: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
+    if (!mem_ok("ctg_assignment_sparse", mem)) return CTG_ERR_ARG;
     if (n > (1ll << 40)) {
         set_error("ctg_assignment_sparse: more than 2^40 pairs");
         return CTG_ERR_UNSUPPORTED;
@@ -507,9 +522,10 @@ int ctg_assignment_sparse(const uint64_t* keys, const uint64_t* values, int64_t 
     a->size = take_capacity(n);
     const size_t slot_bytes = (size_t)a->size * 16;
     DevBuf<unsigned long long> stat(16);
+    DevInput<uint64_t> dk, dv;
+    StreamWait wait{s};
     if (!stat || !(a->table = (uint64_t*)dev_alloc((size_t)take_table_words(a->size) * 8)))
         return hip_status(hipErrorOutOfMemory, who);
-    DevInput<uint64_t> dk, dv;
     rc = dk.put(keys, (size_t)n * 8, mem, s, who);
     if (!rc) rc = dv.put(values, (size_t)n * 8, mem, s, who);
     if (rc) return rc;
@@ -520,6 +536,7 @@ int ctg_assignment_sparse(const uint64_t* keys, const uint64_t* values, int64_t 
     unsigned long long h[2] = {0, 0};
     CTG_CHECK(hipMemcpyAsync(h, stat.p, 16, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     if (h[0]) {
         set_error("ctg_assignment_sparse: " + std::to_string(h[0]) + " duplicate key(s)");
         return CTG_ERR_ARG;
@@ -562,10 +579,7 @@ int ctg_apply_assignment(const ctg_assignment* a, const void* labels, int label_
         set_error("ctg_apply_assignment: label_bits must be 32 or 64");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_apply_assignment: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
+    if (!mem_ok("ctg_apply_assignment", mem)) return CTG_ERR_ARG;
     if (n < 0 || (seg_begin && n_seg < 0)) {
         set_error("ctg_apply_assignment: negative n or n_seg");
         return CTG_ERR_ARG;
@@ -611,14 +625,14 @@ int ctg_apply_assignment(const ctg_assignment* a, const void* labels, int label_
     if (seg_begin) std::copy_n(seg_offset, ns, h.data() + ns + 1);
     h[2 * ns + 2] = ~0ull;   // the smallest missing label starts at all ones
     std::copy(chunks.prefix.begin(), chunks.prefix.end(), (uint32_t*)(h.data() + words));
-    DevBuf<uint64_t> seg(h.size() * 8);
+    DevBuf<uint64_t> seg(h.size() * 8), dout;
+    DevInput<char> dl;
+    StreamWait wait{s};
     if (!seg) return hip_status(hipErrorOutOfMemory, who);
     CTG_CHECK(hipMemcpyAsync(seg.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
     const bool host = mem == CTG_MEM_HOST;
     const size_t lbytes = (size_t)n * (label_bits / 8);
-    DevInput<char> dl;
     if ((rc = dl.put((const char*)labels, lbytes, mem, s, who)) != CTG_OK) return rc;
-    DevBuf<uint64_t> dout;
     uint64_t* o = out;
     if (host && out) {
         // (a host call in place: the copy of the labels is overwritten instead)
@@ -647,6 +661,7 @@ int ctg_apply_assignment(const ctg_assignment* a, const void* labels, int label_
     CTG_CHECK(hipMemcpyAsync(back.data(), seg.p + 2 * ns + 1, back.size() * 8, hipMemcpyDeviceToHost, s));
     if (host && out) CTG_CHECK(hipMemcpyAsync(out, o, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     CTG_CHECK(hipStreamSynchronize(s));
+    wait.disarm();
     if (c.w().profiling && (rc = read_phase_times(c.w(), s)) != CTG_OK) return rc;
     missing[0] = back[0];
     missing[1] = back[0] ? back[1] : 0;

@@ -14,19 +14,13 @@ using namespace ctg;
 
 namespace {
 
-// The call's scratch.  Declared after the call's inputs and outputs, so that
-// on every return path its wait comes before any of their blocks goes back to
-// the pool (ctg_buffers.h).
+// the call's scratch
 struct WsScratch {
-    hipStream_t s;
     DevBuf<uint32_t> parent, key, pick;
     DevBuf<unsigned long long> best, words;
     bool alloc(const WsPlan& P) {
         return parent.alloc((size_t)P.parent_bytes) && key.alloc((size_t)P.key_bytes) &&
                pick.alloc((size_t)P.pick_bytes) && best.alloc((size_t)P.best_bytes) && words.alloc(WS_WORDS * 8);
-    }
-    ~WsScratch() {
-        if (parent) hipStreamSynchronize(s);
     }
 };
 
@@ -61,9 +55,7 @@ struct WsClock {
 };
 
 int read_words(const WsArgs& A, hipStream_t s, unsigned long long* h) {
-    CTG_CHECK(hipMemcpyAsync(h, A.words, WS_WORDS * 8, hipMemcpyDeviceToHost, s));
-    CTG_CHECK(hipStreamSynchronize(s));
-    return CTG_OK;
+    return ctg::read_words(A.words, WS_WORDS * 8, s, h);
 }
 
 int zero_words(const WsArgs& A, int first, int n, hipStream_t s) {
@@ -81,7 +73,7 @@ int cap_error(const char* who, const char* what) {
 // h: the call's words as last read.
 int flood(const char* who, const WsArgs& A, int with_keys, uint64_t* out, WsClock& clk, hipStream_t s,
           unsigned long long* h, uint64_t* rounds, bool* nan) {
-    const int64_t V = (int64_t)A.n[0] * A.n[1] * A.n[2];
+    const int64_t V = (int64_t)A.box.n[0] * A.box.n[1] * A.box.n[2];
     int rc;
     *rounds = 0;
     if ((rc = zero_words(A, WS_W_SEEDED, 3, s)) != CTG_OK) return rc;
@@ -156,46 +148,39 @@ int ctg_seeded_watershed(const float* hmap, const void* seeds, int seed_bits, co
         set_error("ctg_seeded_watershed: unknown flag");
         return CTG_ERR_ARG;
     }
-    if (mem != CTG_MEM_HOST && mem != CTG_MEM_DEVICE) {
-        set_error("ctg_seeded_watershed: mem must be CTG_MEM_HOST or CTG_MEM_DEVICE");
-        return CTG_ERR_ARG;
-    }
-    CallBox box;
-    int rc = box_of(who, shape, begin, end, 0, &box);
+    if (!mem_ok(who, mem)) return CTG_ERR_ARG;
+    DenseCall D{who, mem};
+    int rc = D.open(shape, begin, end, 0);
     if (rc) return rc;
-    const int64_t V = box.voxels;
+    const int64_t V = D.V, *n = D.n;
     if (V > WS_MAX_VOXELS) {
         set_error("ctg_seeded_watershed: a box holds at most 2^30 voxels");
         return CTG_ERR_ARG;
     }
-    const int64_t elems = shape[0] * shape[1] * shape[2];
-    if ((const void*)out == seeds && (seed_bits != 64 || V != elems)) {
+    if ((const void*)out == seeds && (seed_bits != 64 || V != (int64_t)D.elems)) {
         set_error("ctg_seeded_watershed: out may be the seeds only where they are 64-bit and the box is the whole array");
         return CTG_ERR_ARG;
     }
     if (V == 0) return CTG_OK;
     if ((rc = c.begin(stream)) != CTG_OK) return rc;
-    hipStream_t s = c.s;
-    const int64_t n[3] = {box.e[0] - box.b[0], box.e[1] - box.b[1], box.e[2] - box.b[2]};
+    hipStream_t s = D.s = c.s;
     const bool two_d = (flags & CTG_WS_2D) != 0;
     const WsPlan P = ws_plan(n, two_d);
     DevInput<float> dh;
     DevInput<char> dsd;
     DenseOut<uint64_t> o;
-    if ((rc = dh.put(hmap, (size_t)elems * 4, mem, s, who)) != CTG_OK) return rc;
-    if ((rc = dsd.put((const char*)seeds, (size_t)elems * (size_t)(seed_bits / 8), mem, s, who)) != CTG_OK) return rc;
-    WsScratch b{s};
+    WsScratch b;
+    StreamWait wait{s};
+    if ((rc = D.in(dh, hmap, 4)) != CTG_OK) return rc;
+    if ((rc = D.in(dsd, seeds, (size_t)(seed_bits / 8))) != CTG_OK) return rc;
     if (!b.alloc(P)) return hip_status(hipErrorOutOfMemory, who);
-    if ((rc = hip_status(o.open(out, (size_t)V * 8, mem, false, s), who)) != CTG_OK) return rc;
+    if ((rc = D.out(o, out, 8)) != CTG_OK) return rc;
     CTG_CHECK(hipMemsetAsync(b.words.p, 0, WS_WORDS * 8, s));
     WsArgs A{};
     A.hmap = dh.p;
     A.seeds = dsd.p;
     A.seed_bits = seed_bits;
-    A.s_z = shape[1] * shape[2];
-    A.s_y = shape[2];
-    A.base = box.b[0] * A.s_z + box.b[1] * A.s_y + box.b[2];
-    for (int k = 0; k < 3; ++k) A.n[k] = (uint32_t)n[k];
+    A.box = D.vol;
     A.two_d = two_d;
     A.parent = b.parent;
     A.key = b.key;
@@ -230,9 +215,7 @@ int ctg_seeded_watershed(const float* hmap, const void* seeds, int seed_bits, co
             // the survivors, whole, are the seeds of the second flood
             A.seeds = o.d;
             A.seed_bits = 64;
-            A.s_z = n[1] * n[2];
-            A.s_y = n[2];
-            A.base = 0;
+            A.box = vol_box(n, call_box(n, nullptr, nullptr, 0));
             if ((rc = flood(who, A, 0, o.d, clk, s, h, &rounds, &nan)) != CTG_OK) return rc;
         }
     }

@@ -17,11 +17,29 @@ namespace ctg {
 // stream only, and the pool knows nothing of streams: a block may be freed
 // with work queued on it only inside a call that waits for its stream before
 // it returns (the device lock keeps other streams' calls out until then).
-// A CTG_CHECK return after work was queued does not wait: only the scratch
-// owners with a waiting destructor (EdtScratch, WsScratch, BlockTables,
-// AdjFilter, MergeScratch) cover every return path (include/ctg.h, "Streams")
+// Every return path does: a scope that frees blocks with work queued on them
+// holds a StreamWait below its buffers (include/ctg.h, "Streams").
 void* dev_alloc(size_t bytes);
 void dev_free(void* p);
+// blocks until everything queued on the stream (a hipStream_t) is done
+void stream_wait(void* stream);
+
+// Waits for the stream when its scope ends.  Declared after every pool-drawing
+// object of the scope (as a member: the last one), so it is destroyed first
+// and every return path, a failed one included, waits before a block goes
+// back to the pool.  disarm(): the success path has just waited itself.
+// on = false with arm(): a scope that queues work only once a buffer exists.
+struct StreamWait {
+    void* stream;
+    bool armed;
+    explicit StreamWait(void* s, bool on = true) : stream(s), armed(on) {}
+    StreamWait(const StreamWait&) = delete;
+    ~StreamWait() {
+        if (armed) stream_wait(stream);
+    }
+    void arm() { armed = true; }
+    void disarm() { armed = false; }
+};
 
 // A block of the caching allocator that goes back to the pool when its scope
 // ends (every early return included); reset() returns it sooner, release()

@@ -70,16 +70,16 @@ struct AtomicMin {
 
 template <typename DataT>
 __global__ __launch_bounds__(256) void k_cc_range(const CcArgs A) {
-    const DataT* D = (const DataT*)A.data + A.base;
-    const int64_t rows = (int64_t)A.n[0] * A.n[1];
+    const DataT* D = (const DataT*)A.data + A.box.base;
+    const int64_t rows = (int64_t)A.box.n[0] * A.box.n[1];
     const int lane = threadIdx.x & (WAVE - 1);
     float lo = INFINITY, hi = -INFINITY;
     bool nan = false;
     // a wave per row of the box
     for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE; r < rows;
          r += (int64_t)gridDim.x * blockDim.x / WAVE) {
-        const DataT* row = D + (r / A.n[1]) * A.s_z + (r % A.n[1]) * A.s_y;
-        for (uint32_t x = lane; x < A.n[2]; x += WAVE) {
+        const DataT* row = D + (r / A.box.n[1]) * A.box.s_z + (r % A.box.n[1]) * A.box.s_y;
+        for (uint32_t x = lane; x < A.box.n[2]; x += WAVE) {
             const float v = (float)row[x];
             nan |= v != v;
             lo = fminf(lo, v);   // (fminf / fmaxf skip a NaN: the flag carries it)
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_tile(const CcArgs A) {
     t /= A.nt[2];
     const uint32_t ty = t % A.nt[1], tz = t / A.nt[1];
     const uint32_t gx = tx * TILE_X + lane, gy = ty * CC_TILE_Y + w;
-    const bool inxy = gx < A.n[2] && gy < A.n[1];
+    const bool inxy = gx < A.box.n[2] && gy < A.box.n[1];
     float mn = 0.f, mx = 0.f;
     bool divide = false, dead = false;
     if constexpr (NORM) {
@@ -138,14 +138,14 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_tile(const CcArgs A) {
         // (a box that holds -inf: x - mn is NaN there, so numpy's max is NaN and nothing is divided)
         divide = mx > 0.f && mn != -INFINITY;
     }
-    const int64_t col = A.base + (int64_t)gy * A.s_y + gx;
+    const int64_t col = A.box.base + (int64_t)gy * A.box.s_y + gx;
     const DataT* D = (const DataT*)A.data;
 #pragma unroll
     for (int z = 0; z < CC_TILE_Z; ++z) {
         const uint32_t gz = tz * CC_TILE_Z + z;
         bool f = false;
-        if (inxy && gz < A.n[0] && !dead) {
-            const int64_t i = col + (int64_t)gz * A.s_z;
+        if (inxy && gz < A.box.n[0] && !dead) {
+            const int64_t i = col + (int64_t)gz * A.box.s_z;
             float v = (float)D[i];
             if constexpr (NORM) {
                 v = v - mn;
@@ -190,17 +190,17 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_tile(const CcArgs A) {
     __syncthreads();
     for (int z = 0; z < CC_TILE_Z; ++z) {
         const uint32_t gz = tz * CC_TILE_Z + z;
-        if (!inxy || gz >= A.n[0]) continue;
+        if (!inxy || gz >= A.box.n[0]) continue;
         const int r = z * CC_TILE_Y + w;
         const uint64_t m = bits[r];
         uint32_t val = UF_NONE;
         if ((m >> lane) & 1) {
             const uint32_t root = uf_find(par, (uint32_t)(r * TILE_X + run_head(m, lane)), CAP, LdsLoad(), &over);
             const uint32_t lz = root / (CC_TILE_Y * TILE_X), ly = (root / TILE_X) % CC_TILE_Y, lx = root % TILE_X;
-            val = (uint32_t)(((uint64_t)(tz * CC_TILE_Z + lz) * A.n[1] + (ty * CC_TILE_Y + ly)) * A.n[2] +
+            val = (uint32_t)(((uint64_t)(tz * CC_TILE_Z + lz) * A.box.n[1] + (ty * CC_TILE_Y + ly)) * A.box.n[2] +
                              (tx * TILE_X + lx));
         }
-        A.parent[((uint64_t)gz * A.n[1] + gy) * A.n[2] + gx] = val;
+        A.parent[((uint64_t)gz * A.box.n[1] + gy) * A.box.n[2] + gx] = val;
     }
     if (over) atomicOr(&A.words[CC_W_ERR], CC_ERR_CAP);
 }
@@ -214,7 +214,7 @@ template <int CONN>
 __global__ __launch_bounds__(256) void k_cc_seams(const CcArgs A, const CcGrid G) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= G.seam_threads) return;
-    const int64_t n0 = A.n[0], n1 = A.n[1], n2 = A.n[2];
+    const int64_t n0 = A.box.n[0], n1 = A.box.n[1], n2 = A.box.n[2];
     const CcSeamVoxel v = cc_seam_voxel(G, n1, n2, i);
     if (!v.take) return;
     const AgentLoad load{};
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) void k_uf_write(const uint32_t* __restrict__ p
 static unsigned blocks_for(int64_t threads, int per_block) { return (unsigned)((threads + per_block - 1) / per_block); }
 
 hipError_t launch_cc_range(const CcArgs& A, int data_kind, hipStream_t s) {
-    const int64_t rows = (int64_t)A.n[0] * A.n[1];
+    const int64_t rows = (int64_t)A.box.n[0] * A.box.n[1];
     const unsigned blocks = (unsigned)std::min<int64_t>((rows + 3) / 4, 2048);
     if (data_kind == CTG_DATA_U8) hipLaunchKernelGGL(k_cc_range<uint8_t>, dim3(blocks), dim3(256), 0, s, A);
     else hipLaunchKernelGGL(k_cc_range<float>, dim3(blocks), dim3(256), 0, s, A);

@@ -67,8 +67,8 @@ __global__ __launch_bounds__(EDT_X_WAVES * WAVE) void k_edt_x(const EdtSrc A, ui
     __shared__ uint64_t words[EDT_X_WAVES][EDT_ROW_WORDS + EDT_ROW_SUPER];
     __shared__ unsigned long long wave_seeds[EDT_X_WAVES];
     const int wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
-    const int nx = (int)A.n[2], nw = (nx + 63) >> 6, ns = (nw + 63) >> 6;
-    const int64_t rows = (int64_t)A.n[0] * A.n[1];
+    const int nx = (int)A.box.n[2], nw = (nx + 63) >> 6, ns = (nw + 63) >> 6;
+    const int64_t rows = (int64_t)A.box.n[0] * A.box.n[1];
     const int64_t groups = (rows + EDT_X_WAVES - 1) / EDT_X_WAVES;
     uint64_t* W = words[wave];
     uint64_t* S = W + EDT_ROW_WORDS;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(EDT_X_WAVES * WAVE) void k_edt_x(const EdtSrc A, ui
         const int64_t row = g * EDT_X_WAVES + wave;
         const bool live = row < rows;
         if (live) {
-            const int64_t off = A.base + (row / A.n[1]) * A.s_z + (row % A.n[1]) * A.s_y;
+            const int64_t off = A.box.base + (row / A.box.n[1]) * A.box.s_z + (row % A.box.n[1]) * A.box.s_y;
             for (int w = 0; w < nw; ++w) {
                 const int x = (w << 6) + lane;
                 const bool p = x < nx && (EdtSource<KIND>::test(A, off + x) != (A.invert != 0));
@@ -267,7 +267,7 @@ void launch_line(const EdtLineArgs& A, const EdtLinePlan& P, hipStream_t s) {
 }  // namespace
 
 hipError_t launch_edt_x(const EdtSrc& A, int kind, uint16_t* out, unsigned long long* info, hipStream_t s) {
-    const unsigned grid = (unsigned)edt_x_grid((int64_t)A.n[0] * A.n[1]);
+    const unsigned grid = (unsigned)edt_x_grid((int64_t)A.box.n[0] * A.box.n[1]);
     const dim3 block(EDT_X_WAVES * WAVE);
     if (kind == 0) hipLaunchKernelGGL(k_edt_x<0>, dim3(grid), block, 0, s, A, out, info);
     else if (kind == 1) hipLaunchKernelGGL(k_edt_x<1>, dim3(grid), block, 0, s, A, out, info);

@@ -664,9 +664,7 @@ constexpr uint32_t CC_ERR_CAP = 1u, CC_ERR_PAIR = 2u;
 struct CcArgs {                 // the box of a labelling call
     const void* data;           // the array's samples (float32 or uint8)
     const uint8_t* mask;        // the array's mask, or null
-    int64_t s_z, s_y;           // the array's strides in elements
-    int64_t base;               // element offset of the box's first voxel
-    uint32_t n[3];              // the box (z, y, x)
+    VolBox box;                 // the box in the array (ctg_plan.h: vol_box)
     uint32_t nt[3];             // its tiles (ctg_plan.h: cc_grid)
     float threshold;
     int mode;                   // CTG_CC_*
@@ -700,9 +698,7 @@ hipError_t launch_uf_write(const uint32_t* parent, const uint32_t* rank, const u
 // ---------------------------------------------------------------------------
 struct EdtSrc {                 // the box of a call and its seed predicate
     const void* src;            // the array (uint8, float32, uint32 or uint64)
-    int64_t s_z, s_y;           // the array's strides in elements
-    int64_t base;               // element offset of the box's first voxel
-    uint32_t n[3];              // the box (z, y, x)
+    VolBox box;                 // the box in the array (ctg_plan.h: vol_box)
     float threshold;            // CTG_EDT_SRC_GREATER
     uint64_t label;             // CTG_EDT_SRC_EQUAL
     int invert;                 // CTG_EDT_TO_BACKGROUND: the seeds are where the predicate fails
@@ -742,9 +738,7 @@ struct WsArgs {                 // one flood
     const float* hmap;          // the array's heights
     const void* seeds;          // the array's seeds (seed_bits 32 or 64)
     int seed_bits;
-    int64_t s_z, s_y;           // the strides of both arrays in elements
-    int64_t base;               // element offset of the box's first voxel
-    uint32_t n[3];              // the box (z, y, x)
+    VolBox box;                 // the box in both arrays (ctg_plan.h: vol_box)
     int two_d;
     uint32_t* parent;           // box-linear, as the three below (ctg_plan.h: ws_plan)
     uint32_t* key;

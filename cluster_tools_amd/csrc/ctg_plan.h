@@ -65,6 +65,25 @@ inline CallBox call_box(const int64_t* shape, const int64_t* begin, const int64_
     return c;
 }
 
+// What a dense-volume kernel reads of its box (thresholded components, the
+// distance transform, the watershed): voxel (z, y, x) of the box is element
+// base + z * s_z + y * s_y + x of the array.
+struct VolBox {
+    int64_t s_z, s_y;           // the array's strides in elements
+    int64_t base;               // element offset of the box's first voxel
+    uint32_t n[3];              // the box (z, y, x)
+};
+
+// c: a box of call_box on `shape` without error (an axis below 2^32)
+inline VolBox vol_box(const int64_t* shape, const CallBox& c) {
+    VolBox v{};
+    v.s_z = shape[1] * shape[2];
+    v.s_y = shape[2];
+    v.base = c.b[0] * v.s_z + c.b[1] * v.s_y + c.b[2];
+    for (int k = 0; k < 3; ++k) v.n[k] = (uint32_t)(c.e[k] - c.b[k]);
+    return v;
+}
+
 // ---------------------------------------------------------------------------
 // face-scan tile depths (whole arrays)
 // ---------------------------------------------------------------------------

@@ -27,6 +27,7 @@ int current_device() {
 
 void* dev_alloc(size_t bytes) { return g_pool.alloc(current_device(), bytes); }
 void dev_free(void* p) { g_pool.free(p); }
+void stream_wait(void* stream) { hipStreamSynchronize((hipStream_t)stream); }
 
 static Workspace g_ws[64];
 Workspace& ws(int device) { return g_ws[device & 63]; }

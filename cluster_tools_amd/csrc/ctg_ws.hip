@@ -37,12 +37,14 @@ struct AgentLoad {
     }
 };
 
-__device__ __forceinline__ WsBox box_of_args(const WsArgs& A) { return WsBox{{A.n[0], A.n[1], A.n[2]}, A.two_d}; }
-__device__ __forceinline__ int64_t voxels_of(const WsArgs& A) { return (int64_t)A.n[0] * A.n[1] * A.n[2]; }
+__device__ __forceinline__ WsBox box_of_args(const WsArgs& A) {
+    return WsBox{{A.box.n[0], A.box.n[1], A.box.n[2]}, A.two_d};
+}
+__device__ __forceinline__ int64_t voxels_of(const WsArgs& A) { return (int64_t)A.box.n[0] * A.box.n[1] * A.box.n[2]; }
 // the array element of box voxel i
 __device__ __forceinline__ int64_t element_of(const WsArgs& A, uint32_t i) {
-    const uint32_t x = i % A.n[2], y = (i / A.n[2]) % A.n[1], z = i / (A.n[1] * A.n[2]);
-    return A.base + (int64_t)z * A.s_z + (int64_t)y * A.s_y + x;
+    const uint32_t x = i % A.box.n[2], y = (i / A.box.n[2]) % A.box.n[1], z = i / (A.box.n[1] * A.box.n[2]);
+    return A.box.base + (int64_t)z * A.box.s_z + (int64_t)y * A.box.s_y + x;
 }
 __device__ __forceinline__ uint64_t seed_at(const WsArgs& A, int64_t e) {
     return A.seed_bits == 32 ? (uint64_t)((const uint32_t*)A.seeds)[e] : ((const uint64_t*)A.seeds)[e];
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_ws_dropped(const uint64_t* __res
     if (threadIdx.x == 0 && dropped) atomicAdd(&words[WS_W_DROPPED], dropped);
 }
 
-static unsigned ws_grid(const WsArgs& A) { return (unsigned)ws_grid((int64_t)A.n[0] * A.n[1] * A.n[2]); }
+static unsigned ws_grid(const WsArgs& A) { return (unsigned)ws_grid((int64_t)A.box.n[0] * A.box.n[1] * A.box.n[2]); }
 
 hipError_t launch_ws_init(const WsArgs& A, int with_keys, hipStream_t s) {
     if (with_keys) hipLaunchKernelGGL(k_ws_init<1>, dim3(ws_grid(A)), dim3(WS_THREADS), 0, s, A);

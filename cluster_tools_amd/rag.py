@@ -232,6 +232,58 @@ def _current_stream(tensor_input):
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _stream(stream, on_dev):
+    """The stream of a call: ``stream``, else torch's current one for tensor inputs, else the null stream."""
+    return _current_stream(on_dev) if stream is None else stream
+
+
+def _mem(on_dev):
+    return L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST
+
+
+def _box(shape, begin, end):
+    """The box [begin, end) of a dense-volume call on an array of ``shape`` -> (b, e, oshape)."""
+    for box in (begin, end):
+        if box is not None and len(box) != 3:
+            raise ValueError('begin / end must have 3 entries')
+    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
+    e = list(shape) if end is None else [int(v) for v in end]
+    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
+        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
+    return b, e, tuple(hi - lo for lo, hi in zip(b, e))
+
+
+def _dense_out(out, oshape, on_dev, like, kind, name, what=None):
+    """The output of a dense call: a new array of ``oshape`` of the kind of ``like`` (numpy, or a tensor on
+    its device), or ``out`` checked against it.  ``kind``: 'int64' (uint64 arrays, int64 tensors; either
+    64-bit integer type passes), 'float32' or 'float64'; ``name``: what the messages call ``like``;
+    ``oshape``: a shape, or an int where only the size counts; ``what``: that shape in the last message
+    (default: the shape of the box)."""
+    if out is None:
+        if on_dev:
+            import torch
+            return torch.empty(oshape, dtype=getattr(torch, kind), device=like.device)
+        return np.empty(oshape, dtype=np.uint64 if kind == 'int64' else kind)
+    if _is_torch(out) != on_dev:
+        raise ValueError('out must be of the same kind as %s (numpy array or CUDA tensor)' % name)
+    if on_dev:
+        import torch
+        ok = out.is_cuda and out.is_contiguous() and (
+            out.element_size() == 8 and not out.is_floating_point() if kind == 'int64'
+            else out.dtype == getattr(torch, kind))
+    else:
+        ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and \
+            out.dtype in ((np.uint64, np.int64) if kind == 'int64' else (np.dtype(kind),))
+    if ok and isinstance(oshape, int):
+        ok = int(out.numel() if on_dev else out.size) == oshape
+    elif ok:
+        ok = tuple(out.shape) == tuple(oshape)
+    if not ok:
+        raise ValueError('out must be a contiguous %s array of %s' % (
+            '64-bit integer' if kind == 'int64' else kind, what or 'the shape of the box %s' % (oshape,)))
+    return out
+
+
 def _check_offsets(offsets):
     off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1, 3))
     if off.shape[0] > L.CTG_MAX_CHANNELS:
@@ -303,13 +355,10 @@ def rag_features_handle(labels, data=None, offsets=None, own_begin=None, own_end
     sh = _shape_arr(shape)
     ob = _shape_arr(own_begin) if own_begin is not None else None
     oe = _shape_arr(own_end) if own_end is not None else None
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_rag_features(_ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr, sh, ob, oe,
                               int(bool(ignore_label)), float(hist_range[0]), float(hist_range[1]),
-                              flags, L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
-                              stream, ctypes.byref(h))
+                              flags, _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_rag_features')
     return Result(h, dev)
 
@@ -464,8 +513,8 @@ def rag_blocks_arena(labels, blocks, data=None, offsets=None, ignore_label=False
     rc = lib.ctg_rag_blocks(_ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr,
                             ctypes.cast(desc, ctypes.c_void_p), len(blocks), n_lab, n_dat,
                             int(bool(ignore_label)), float(hist_range[0]), float(hist_range[1]), flags,
-                            L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
-                            _current_stream(on_dev) if stream is None else stream, ctypes.byref(h))
+                            _mem(on_dev),
+                            _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_rag_blocks')
     r = Result(h, dev)
     nb = len(blocks)
@@ -525,8 +574,8 @@ def unique_labels(labels, begin=None, end=None, stream=None):
     rc = lib.ctg_unique_labels(_ptr(labels), _shape_arr(shape),
                                _shape_arr(begin) if begin is not None else None,
                                _shape_arr(end) if end is not None else None,
-                               L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
-                               _current_stream(on_dev) if stream is None else stream, ctypes.byref(h))
+                               _mem(on_dev),
+                               _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_unique_labels')
     r = Result(h, L.init_device())
     nodes = r.nodes()
@@ -553,12 +602,10 @@ def merge_stats_handle(keys, sums, records, hist_range=(0.0, 1.0), keep_stats=Fa
         records = np.ascontiguousarray(np.asarray(records, dtype=np.uint32).reshape(-1, WIDE_WORDS))
         n = keys.shape[0]
         assert sums.shape[0] == n and records.shape[0] == n
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_merge_stats(_ptr(keys), _ptr(sums), _ptr(records), n, float(hist_range[0]),
                              float(hist_range[1]), int(bool(keep_stats)),
-                             L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+                             _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_merge_stats')
     return Result(h, dev)
 
@@ -572,11 +619,9 @@ def unique_values_handle(values, stream=None):
         values = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1))
     else:
         assert values.is_cuda and values.is_contiguous() and values.element_size() == 8
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     L.check(lib.ctg_unique_values(_ptr(values), int(values.shape[0]),
-                                  L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h)),
+                                  _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h)),
             'ctg_unique_values')
     return Result(h, dev)
 
@@ -670,14 +715,12 @@ def label_overlaps_handle(labels, values, begin=None, end=None, ignore_label=Non
     lib = L.load()
     dev = L.init_device()
     on_dev = _is_torch(labels)
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_label_overlaps(_ptr(labels), lbits, _ptr(values), vbits, _shape_arr(shape),
                                 _shape_arr(begin) if begin is not None else None,
                                 _shape_arr(end) if end is not None else None,
                                 int(ignore_label is not None), int(ignore_label or 0),
-                                L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+                                _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_label_overlaps')
     return Result(h, dev)
 
@@ -717,10 +760,8 @@ def merge_overlaps_handle(pairs, counts, stream=None):
             raise ValueError('%d pairs for %d counts' % (pairs.shape[0], n))
     lib = L.load()
     dev = L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
-    rc = lib.ctg_merge_overlaps(_ptr(pairs), _ptr(counts), n, L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream,
+    rc = lib.ctg_merge_overlaps(_ptr(pairs), _ptr(counts), n, _mem(on_dev), _stream(stream, on_dev),
                                 ctypes.byref(h))
     L.check(rc, 'ctg_merge_overlaps')
     return Result(h, dev)
@@ -775,14 +816,12 @@ def morphology_handle(labels, begin=None, end=None, origin=None, stream=None):
     lib = L.load()
     dev = L.init_device()
     on_dev = _is_torch(labels)
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_morphology(_ptr(labels), bits, _shape_arr(shape),
                             _shape_arr(begin) if begin is not None else None,
                             _shape_arr(end) if end is not None else None,
                             _shape_arr(origin) if origin is not None else None,
-                            L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+                            _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_morphology')
     return Result(h, dev)
 
@@ -823,11 +862,9 @@ def merge_morphology_handle(rows, stream=None):
         raise ValueError('morphology rows have %d columns, got %s' % (MORPH_COLS, tuple(rows.shape)))
     lib = L.load()
     dev = L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
-    rc = lib.ctg_merge_morphology(_ptr(rows), size // MORPH_COLS, L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
-                                  stream, ctypes.byref(h))
+    rc = lib.ctg_merge_morphology(_ptr(rows), size // MORPH_COLS, _mem(on_dev),
+                                  _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_merge_morphology')
     return Result(h, dev)
 
@@ -900,14 +937,12 @@ def region_features_handle(labels, data, begin=None, end=None, ignore_label=None
         raise ValueError('ignore_label must be a uint64 value or None, got %r' % (ignore_label,))
     lib = L.load()
     dev = L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_region_features(_ptr(labels), bits, _ptr(data), kind, _shape_arr(shape),
                                  _shape_arr(begin) if begin is not None else None,
                                  _shape_arr(end) if end is not None else None,
                                  int(ignore_label is not None), int(ignore_label or 0),
-                                 L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+                                 _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_region_features')
     return Result(h, dev)
 
@@ -953,11 +988,9 @@ def merge_region_features_handle(rows, stream=None):
         raise ValueError('region-feature rows have %d columns, got %s' % (REGION_COLS, tuple(rows.shape)))
     lib = L.load()
     dev = L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_merge_region_features(_ptr(rows), size // REGION_COLS,
-                                       L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+                                       _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_merge_region_features')
     return Result(h, dev)
 
@@ -1043,11 +1076,9 @@ def assignment_dense(table, stream=None):
     table, on_dev = _u64_vector(table, 'table')
     lib = L.load()
     dev = L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
-    rc = lib.ctg_assignment_dense(_ptr(table), int(table.shape[0]), L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST,
-                                  stream, ctypes.byref(h))
+    rc = lib.ctg_assignment_dense(_ptr(table), int(table.shape[0]), _mem(on_dev),
+                                  _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_assignment_dense')
     return Assignment(h, dev)
 
@@ -1064,11 +1095,9 @@ def assignment_sparse(keys, values, stream=None):
         raise ValueError('%d keys for %d values' % (keys.shape[0], values.shape[0]))
     lib = L.load()
     dev = L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     h = ctypes.c_void_p()
     rc = lib.ctg_assignment_sparse(_ptr(keys), _ptr(values), int(keys.shape[0]),
-                                   L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(h))
+                                   _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
     L.check(rc, 'ctg_assignment_sparse')
     return Assignment(h, dev)
 
@@ -1116,33 +1145,18 @@ def apply_assignment(a, labels, offset=0, segments=None, allow_missing=False, ou
         if out is not None:
             raise ValueError('check_only writes nothing: out must be None')
     elif out is None:
-        if on_dev:
-            import torch
-            out = torch.empty(tuple(labels.shape), dtype=torch.int64, device=labels.device)
-        else:
-            out = np.empty(labels.shape, dtype=np.uint64)
+        out = _dense_out(None, tuple(labels.shape), on_dev, labels, 'int64', 'labels')
     else:
-        if _is_torch(out) != on_dev:
-            raise ValueError('out must be of the same kind as labels (numpy array or CUDA tensor)')
-        if on_dev:
-            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
-            size = int(out.numel())
-        else:
-            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
-            size = int(out.size) if ok else -1
-        if not ok or size != n:
-            raise ValueError('out must be a contiguous 64-bit integer array of the size of labels')
+        _dense_out(out, n, on_dev, labels, 'int64', 'labels', 'the size of labels')
         if bits != 64 and _ptr(out).value == _ptr(labels).value and n:
             raise ValueError('in place needs 64-bit labels')
     lib = L.load()
     L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     nonzero = np.zeros(max(n_seg, 1), dtype=np.uint64)
     missing = np.zeros(2, dtype=np.uint64)
     rc = lib.ctg_apply_assignment(a.handle, _ptr(labels), bits, n, _ptr(seg_begin), _ptr(seg_off), n_seg,
                                   int(bool(allow_missing)), _ptr(out), _ptr(nonzero), _ptr(missing),
-                                  L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream)
+                                  _mem(on_dev), _stream(stream, on_dev))
     if rc == L.CTG_ERR_MISSING:
         msg = '%d: the smallest of the labels without an entry (%d voxel(s))' % (int(missing[1]), int(missing[0]))
         if a.kind == 'sparse':
@@ -1199,37 +1213,14 @@ def threshold_components(data, threshold, mode='greater', mask=None, normalize=T
             if mask.dtype not in (np.bool_, np.uint8):
                 raise TypeError('mask must be bool or uint8, got %s' % mask.dtype)
             mask = np.ascontiguousarray(mask).view(np.uint8)
-    for box in (begin, end):
-        if box is not None and len(box) != 3:
-            raise ValueError('begin / end must have 3 entries')
-    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
-    e = list(shape) if end is None else [int(v) for v in end]
-    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
-        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
-    oshape = tuple(hi - lo for lo, hi in zip(b, e))
-    if out is None:
-        if on_dev:
-            import torch
-            out = torch.empty(oshape, dtype=torch.int64, device=data.device)
-        else:
-            out = np.empty(oshape, dtype=np.uint64)
-    else:
-        if _is_torch(out) != on_dev:
-            raise ValueError('out must be of the same kind as data (numpy array or CUDA tensor)')
-        if on_dev:
-            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
-        else:
-            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
-        if not ok or tuple(out.shape) != oshape:
-            raise ValueError('out must be a contiguous 64-bit integer array of the shape of the box %s' % (oshape,))
+    b, e, oshape = _box(shape, begin, end)
+    out = _dense_out(out, oshape, on_dev, data, 'int64', 'data')
     lib = L.load()
     L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     n = ctypes.c_uint64(0)
     rc = lib.ctg_threshold_components(_ptr(data), kind, _ptr(mask), _shape_arr(shape), _shape_arr(b), _shape_arr(e),
                                       float(threshold), CC_MODES[mode], int(bool(normalize)), int(connectivity),
-                                      _ptr(out), L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream,
+                                      _ptr(out), _mem(on_dev), _stream(stream, on_dev),
                                       ctypes.byref(n))
     L.check(rc, 'ctg_threshold_components')
     return out, int(n.value)
@@ -1259,30 +1250,16 @@ def merge_assignments(pairs, n_labels, stream=None, out=None):
     n_labels = int(n_labels)
     if n_labels >= 1 << 32:
         raise ValueError('n_labels must stay below 2^32, got %d' % n_labels)
-    if out is not None:
-        if _is_torch(out) != on_dev:
-            raise ValueError('out must be of the same kind as pairs (numpy array or CUDA tensor)')
-        if on_dev:
-            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
-        else:
-            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
-        if not ok or tuple(out.shape) != (n_labels,):
-            raise ValueError('out must be a contiguous 64-bit integer array of n_labels = %d entries' % n_labels)
-    if on_dev:
-        import torch
-        table = torch.empty(n_labels, dtype=torch.int64, device=pairs.device) if out is None else out
-    else:
+    table = _dense_out(out, (n_labels,), on_dev, pairs, 'int64', 'pairs', 'n_labels = %d entries' % n_labels)
+    if not on_dev:
         if pairs.dtype.kind == 'i' and pairs.size and int(pairs.min()) < 0:
             raise ValueError('pairs holds negative values')
         pairs = np.ascontiguousarray(pairs, dtype=np.uint64)
-        table = np.empty(n_labels, dtype=np.uint64) if out is None else out
     lib = L.load()
     L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     max_id = ctypes.c_uint64(0)
     rc = lib.ctg_merge_assignments(_ptr(pairs), int(pairs.shape[0]), n_labels, _ptr(table),
-                                   L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, ctypes.byref(max_id))
+                                   _mem(on_dev), _stream(stream, on_dev), ctypes.byref(max_id))
     L.check(rc, 'ctg_merge_assignments')
     return table, int(max_id.value)
 
@@ -1364,43 +1341,17 @@ def distance_transform(src, pitch=None, threshold=None, label=None, to_backgroun
     if len(shape) != 3:
         raise ValueError('src must be 3-D, got shape %s' % (shape,))
     p = _edt_pitch(pitch)
-    for box in (begin, end):
-        if box is not None and len(box) != 3:
-            raise ValueError('begin / end must have 3 entries')
-    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
-    e = list(shape) if end is None else [int(v) for v in end]
-    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
-        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
-    oshape = tuple(hi - lo for lo, hi in zip(b, e))
-    if out is None:
-        if on_dev:
-            import torch
-            out = torch.empty(oshape, dtype=torch.float64 if squared else torch.float32, device=src.device)
-        else:
-            out = np.empty(oshape, dtype=np.float64 if squared else np.float32)
-    else:
-        if _is_torch(out) != on_dev:
-            raise ValueError('out must be of the same kind as src (numpy array or CUDA tensor)')
-        if on_dev:
-            import torch
-            ok = out.is_cuda and out.is_contiguous() and out.dtype == (torch.float64 if squared else torch.float32)
-        else:
-            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and \
-                out.dtype == (np.float64 if squared else np.float32)
-        if not ok or tuple(out.shape) != oshape:
-            raise ValueError('out must be a contiguous %s array of the shape of the box %s'
-                             % ('float64' if squared else 'float32', oshape))
+    b, e, oshape = _box(shape, begin, end)
+    out = _dense_out(out, oshape, on_dev, src, 'float64' if squared else 'float32', 'src')
     lib = L.load()
     L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     info = (ctypes.c_uint64 * 4)()
     flags = (L.CTG_EDT_TO_BACKGROUND if to_background else 0) | (L.CTG_EDT_2D if two_d else 0) | \
         (L.CTG_EDT_OUT_D2 if squared else 0)
     rc = lib.ctg_distance_transform(_ptr(src), kind, bits, _shape_arr(shape), _shape_arr(b), _shape_arr(e),
                                     float(threshold or 0.0), int(label or 0),
                                     (ctypes.c_double * 3)(*p) if p is not None else None, flags, _ptr(out),
-                                    L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, info)
+                                    _mem(on_dev), _stream(stream, on_dev), info)
     L.check(rc, 'ctg_distance_transform')
     return out, EdtInfo(int(info[0]), int(info[1]), int(info[2]),
                         float(np.array([info[3]], dtype=np.uint64).view(np.float64)[0]))
@@ -1454,14 +1405,7 @@ def seeded_watershed(hmap, seeds, size_filter=0, two_d=False, begin=None, end=No
         raise ValueError('seeds shape %s != hmap shape %s' % (tuple(seeds.shape), shape))
     if not 0 <= int(size_filter) < 1 << 64:
         raise ValueError('size_filter must be a uint64 value, got %r' % (size_filter,))
-    for box in (begin, end):
-        if box is not None and len(box) != 3:
-            raise ValueError('begin / end must have 3 entries')
-    b = [0, 0, 0] if begin is None else [int(v) for v in begin]
-    e = list(shape) if end is None else [int(v) for v in end]
-    if any(not 0 <= lo <= hi <= sh for lo, hi, sh in zip(b, e, shape)):
-        raise ValueError('box [%s, %s) outside the array of shape %s' % (b, e, shape))
-    oshape = tuple(hi - lo for lo, hi in zip(b, e))
+    b, e, oshape = _box(shape, begin, end)
     if oshape[0] * oshape[1] * oshape[2] > WS_MAX_VOXELS:
         raise ValueError('a box holds at most 2^30 voxels, got %s' % (oshape,))
     in_place = out is seeds
@@ -1476,28 +1420,13 @@ def seeded_watershed(hmap, seeds, size_filter=0, two_d=False, begin=None, end=No
         seeds = np.ascontiguousarray(seeds)
         if in_place:
             out = seeds
-    if out is None:
-        if on_dev:
-            out = torch.empty(oshape, dtype=torch.int64, device=hmap.device)
-        else:
-            out = np.empty(oshape, dtype=np.uint64)
-    else:
-        if _is_torch(out) != on_dev:
-            raise ValueError('out must be of the same kind as hmap (numpy array or CUDA tensor)')
-        if on_dev:
-            ok = out.is_cuda and out.is_contiguous() and out.element_size() == 8 and not out.is_floating_point()
-        else:
-            ok = isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype in (np.uint64, np.int64)
-        if not ok or tuple(out.shape) != oshape:
-            raise ValueError('out must be a contiguous 64-bit integer array of the shape of the box %s' % (oshape,))
+    out = _dense_out(out, oshape, on_dev, hmap, 'int64', 'hmap')
     lib = L.load()
     L.init_device()
-    if stream is None:
-        stream = _current_stream(on_dev)
     info = (ctypes.c_uint64 * 4)()
     rc = lib.ctg_seeded_watershed(_ptr(hmap), _ptr(seeds), bits, _shape_arr(shape), _shape_arr(b), _shape_arr(e),
                                   L.CTG_WS_2D if two_d else 0, int(size_filter), _ptr(out),
-                                  L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST, stream, info)
+                                  _mem(on_dev), _stream(stream, on_dev), info)
     L.check(rc, 'ctg_seeded_watershed')
     return out, WsInfo(int(info[0]), int(info[1]), int(info[2]), int(info[3]))
 

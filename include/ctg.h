@@ -112,12 +112,16 @@
  *     (they are serialised per device by a lock).  The library's block pool
  *     knows nothing of streams, so a block returns to it while work that uses
  *     it is queued only inside a call that waits for its stream before it
- *     returns; every call that draws scratch from the pool is of that kind
- *     where it succeeds.  A call that fails with CTG_ERR_HIP after it queued
- *     work (a launch or copy that HIP refused) may return with that work queued
- *     and its scratch back in the pool -- ctg_distance_transform,
- *     ctg_seeded_watershed, ctg_rag_blocks, the adjacency filter and ctg_mgpu_merge wait even then;
- *     after such an error synchronise the stream before the next call.
+ *     returns; every call that draws scratch from the pool is of that kind,
+ *     where it succeeds and where it fails: a scope that owns pool blocks
+ *     holds a guard below them that waits for the stream on every return path
+ *     before a block goes back (csrc/ctg_buffers.h: StreamWait), so a call
+ *     that fails after it queued work (a launch or copy that HIP refused, an
+ *     allocation that failed half way) has waited as well.  The two face-scan
+ *     calls and ctg_mgpu_merge keep the guards they had: ctg_rag_blocks waits
+ *     on every path, ctg_rag_features once its adjacency filter exists and
+ *     ctg_mgpu_merge once its merge scratch does; if one of these two fails
+ *     with CTG_ERR_HIP before that, synchronise the stream before the next call.
  */
 #ifndef CTG_H_
 #define CTG_H_

@@ -221,6 +221,30 @@ def test_call_box(plan):
     assert [int(a.split()[0]) for a in plan(too_large)] == [2, 2]
 
 
+def test_vol_box(plan):
+    """vol_box against numpy: the strides of a C-ordered array of the shape in
+    elements, base the flat index of b, n = e - b; and through them every
+    voxel of the box is the array element numpy's slice holds."""
+    import numpy as np
+    cases = [((3, 5, 7), (0, 0, 0), (3, 5, 7)),      # the whole array
+             ((3, 5, 7), (1, 2, 3), (3, 4, 7)),      # off the origin on all three axes
+             ((3, 5, 7), (2, 4, 6), (3, 5, 7)),      # one voxel, the last
+             ((3, 5, 7), (1, 2, 3), (1, 4, 7)),      # empty
+             ((3, 5, 7), (3, 5, 7), (3, 5, 7)),      # empty at the far corner
+             ((5, 9, 13), (1, 2, 3), (4, 9, 12)),
+             ((1, 1, 1), (0, 0, 0), (1, 1, 1))]
+    got = plan(['volbox %d %d %d %d %d %d %d %d %d' % (s + b + e) for s, b, e in cases])
+    for (shape, b, e), g in zip(cases, got):
+        a = np.arange(shape[0] * shape[1] * shape[2], dtype=np.int64).reshape(shape)
+        s_z, s_y, base, nz, ny, nx = map(int, g.split())
+        assert (s_z, s_y, 1) == tuple(st // a.itemsize for st in a.strides), (shape, g)
+        assert base == sum(x * st // a.itemsize for x, st in zip(b, a.strides)), (shape, b, g)   # b's flat index
+        assert (nz, ny, nx) == tuple(hi - lo for lo, hi in zip(b, e)), (shape, b, e, g)
+        z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing='ij')
+        assert np.array_equal(a.ravel()[base + z * s_z + y * s_y + x] if z.size else np.zeros((nz, ny, nx), np.int64),
+                              a[b[0]:e[0], b[1]:e[1], b[2]:e[2]])
+
+
 MAX_X = 1 << 30     # (the scan's own limit is the caller's: any value above the shapes used here)
 UNIQUE_ROWS = 8
 

@@ -3,7 +3,10 @@ themselves (csrc/ctg_buffers.h) are plain C++ over an allocate / free back
 end; tools/pool_check.cpp runs them on the CPU against a fake back end that
 keeps a ledger and refuses on demand -- built with the host compiler and
 -fsanitize=address,undefined -- so the failure paths that must never be
-provoked on a GPU are pinned here (no GPU, no library)."""
+provoked on a GPU are pinned here (no GPU, no library).  The wait_* cases pin
+StreamWait: with a fake stream_wait that logs into the same list as dev_free,
+every return path of a scope waits for the stream before a block of the scope
+goes back to the pool, unless the guard was disarmed or never armed."""
 import os
 import shutil
 import subprocess
@@ -61,7 +64,8 @@ def test_stream_cases_restates_the_size_classes(report):
 
 
 CASES = ['reuse_bound', 'purge_and_retry', 'purge_and_retry_refused', 'freed_to_allocating_device',
-         'purge_with_refused_free', 'dev_buf', 'grow_buf', 'sort_scratch_growth'] + \
+         'purge_with_refused_free', 'dev_buf', 'wait_before_frees', 'wait_on_early_return', 'wait_disarmed',
+         'wait_without_buffers', 'wait_armed_later', 'grow_buf', 'sort_scratch_growth'] + \
         ['sort_scratch_refused_%d' % k for k in range(9)]
 
 

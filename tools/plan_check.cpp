@@ -10,6 +10,7 @@
 //   range MIN_U MAX_V NB IB                   -> kmin kmax
 //   box SZ SY SX HAS_BEGIN bz by bx HAS_END ez ey ex MAX_VOXELS
 //                                            -> error bz by bx ez ey ex voxels   (error: 0 ok, 1 outside, 2 too large)
+//   volbox SZ SY SX bz by bx ez ey ex        -> s_z s_y base nz ny nx   (vol_box of call_box of the box)
 //   blocks N HAS_DATA N_CHANNELS LABELS_LEN DATA_LEN MAX_X SCAN_ROWS UNIQUE_ROWS TILE_Z_SWITCH
 //          then per block: label_offset data_offset shape[3] own_begin[3] own_end[3] graph_begin[3] graph_end[3]
 //        -> error bad_block   (error: 1 box outside, 2 array outside), or
@@ -110,6 +111,11 @@ int main() {
             const CallBox c = call_box(shape, has_b ? b : nullptr, has_e ? e : nullptr, max_voxels);
             printf("%d %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 " %" PRId64 "\n", (int)c.error,
                    c.b[0], c.b[1], c.b[2], c.e[0], c.e[1], c.e[2], c.voxels);
+        } else if (cmd == "volbox") {
+            int64_t shape[3], b[3], e[3];
+            in >> shape[0] >> shape[1] >> shape[2] >> b[0] >> b[1] >> b[2] >> e[0] >> e[1] >> e[2];
+            const VolBox v = vol_box(shape, call_box(shape, b, e, 0));
+            printf("%" PRId64 " %" PRId64 " %" PRId64 " %u %u %u\n", v.s_z, v.s_y, v.base, v.n[0], v.n[1], v.n[2]);
         } else if (cmd == "blocks") {
             int n, has_data, nch, rows, urows, tz;
             int64_t labels_len, data_len, max_x;

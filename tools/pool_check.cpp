@@ -1,7 +1,8 @@
 // Host check of csrc/ctg_pool.h and csrc/ctg_buffers.h for tests/test_pool.py:
 // the caching allocator and the self-owning buffers over a fake back end --
 // malloc / free with a ledger of live blocks and a switch that refuses chosen
-// allocations or frees.  Prints "class BYTES ROUNDED" lines (the size-class
+// allocations or frees, and a stream_wait that logs into the same event list
+// as dev_free (the order of a StreamWait and the buffers of its scope).  Prints "class BYTES ROUNDED" lines (the size-class
 // table at its edges) and one "ok NAME" line per case that held; the first
 // broken expectation ends the run with its line number.
 //
@@ -10,6 +11,8 @@
 #include <cstdlib>
 #include <map>
 #include <set>
+#include <utility>
+#include <vector>
 
 #include "../cluster_tools_amd/csrc/ctg_buffers.h"
 #include "../cluster_tools_amd/csrc/ctg_pool.h"
@@ -33,6 +36,7 @@ struct Ledger {
     long refuse_alloc = -1, refuse_allocs = 0;   // allocations [refuse_alloc, refuse_alloc + refuse_allocs) fail
     long refuse_free = -1;                       // this free fails
     int bad_frees = 0;                           // frees of a block that is not live (double or foreign)
+    std::vector<std::pair<char, void*>> events;  // ('f', block) of every dev_free, ('w', stream) of every stream_wait
     void refuse_next_allocs(long n) { refuse_alloc = n_alloc, refuse_allocs = n; }
 };
 static Ledger g_led;
@@ -61,7 +65,12 @@ static int fake_free(void* p) {
 static DevicePool* g_pool = nullptr;
 static int g_device = 0;   // the "current device"
 void* ctg::dev_alloc(size_t bytes) { return g_pool->alloc(g_device, bytes); }
-void ctg::dev_free(void* p) { g_pool->free(p); }
+void ctg::dev_free(void* p) {
+    if (p) g_led.events.emplace_back('f', p);
+    g_pool->free(p);
+}
+void ctg::stream_wait(void* stream) { g_led.events.emplace_back('w', stream); }
+using Events = std::vector<std::pair<char, void*>>;
 
 static std::set<void*> cached(DevicePool& pool, int device) {
     std::set<void*> s;
@@ -195,6 +204,78 @@ int main() {
         char* kept = c.release();
         EXPECT(!c.p && cached(pool, 0).size() == 1);
         dev_free(kept);
+    });
+
+    // a StreamWait below the buffers of its scope: the wait, then the frees in reverse order of declaration
+    run_case("wait_before_frees", [](DevicePool&) {
+        int stream = 0;
+        void *pa = nullptr, *pb = nullptr;
+        {
+            DevBuf<char> a(100), b(100);
+            StreamWait wait{&stream};
+            pa = a.p, pb = b.p;
+            EXPECT(pa && pb && g_led.events.empty());
+        }
+        EXPECT(g_led.events == (Events{{'w', &stream}, {'f', pb}, {'f', pa}}));
+    });
+
+    // the same on an early return, and as the last member of a struct
+    run_case("wait_on_early_return", [](DevicePool&) {
+        struct Scratch {
+            DevBuf<char> a, b;
+            StreamWait wait;
+        };
+        int stream = 0;
+        void* pa = nullptr;
+        const auto call = [&](bool fail) {
+            Scratch s{{}, {}, StreamWait{&stream}};
+            pa = s.a.alloc(100);
+            if (fail) return 1;
+            s.b.alloc(100);
+            return 0;
+        };
+        EXPECT(call(true) == 1);
+        EXPECT(g_led.events == (Events{{'w', &stream}, {'f', pa}}));
+    });
+
+    run_case("wait_disarmed", [](DevicePool&) {
+        int stream = 0;
+        void *pa = nullptr, *pb = nullptr;
+        {
+            DevBuf<char> a(100), b(100);
+            StreamWait wait{&stream};
+            pa = a.p, pb = b.p;
+            wait.disarm();   // (the success path has just waited itself)
+        }
+        EXPECT(g_led.events == (Events{{'f', pb}, {'f', pa}}));
+    });
+
+    // armed from construction: the wait does not depend on the buffers (nothing is freed here)
+    run_case("wait_without_buffers", [](DevicePool&) {
+        int stream = 0;
+        {
+            DevBuf<char> a, b;
+            StreamWait wait{&stream};
+        }
+        EXPECT(g_led.events == (Events{{'w', &stream}}));
+    });
+
+    // on = false: no wait until arm()
+    run_case("wait_armed_later", [](DevicePool&) {
+        int stream = 0;
+        void* pa = nullptr;
+        {
+            DevBuf<char> a;
+            StreamWait wait{&stream, false};
+        }
+        EXPECT(g_led.events.empty());
+        {
+            DevBuf<char> a;
+            StreamWait wait{&stream, false};
+            pa = a.alloc(100);
+            wait.arm();
+        }
+        EXPECT(g_led.events == (Events{{'w', &stream}, {'f', pa}}));
     });
 
     run_case("grow_buf", [](DevicePool& pool) {
