@@ -30,7 +30,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import rag
-from .ndist import _grid_positions, _open
+from .ndist import _open, decode_row_chunk, encode_row_chunk, read_chunk_rows, write_block_chunk
 
 REGION_COLS = rag.REGION_COLS
 FEATURE_NAMES = list(rag.REGION_FEATURE_NAMES)
@@ -38,19 +38,12 @@ FEATURE_NAMES = list(rag.REGION_FEATURE_NAMES)
 
 def encode_region_chunk(rows):
     """(n, 5) float64 rows [id, count, sum, min, max] -> the chunk words above."""
-    rows = np.asarray(rows, dtype=np.float64)
-    if rows.size % REGION_COLS or (rows.ndim == 2 and rows.size and rows.shape[1] != REGION_COLS):
-        raise ValueError('region-feature rows have %d columns, got shape %s' % (REGION_COLS, rows.shape))
-    return np.ascontiguousarray(rows).reshape(-1)
+    return encode_row_chunk(rows, REGION_COLS, 'region-feature')
 
 
 def decode_region_chunk(words):
     """Chunk words -> (n, 5) float64 rows in the chunk's order."""
-    w = np.asarray(words, dtype=np.float64).reshape(-1)
-    if w.size % REGION_COLS:
-        raise RuntimeError('region-feature chunk: truncated row (%d words, not a multiple of %d)'
-                           % (w.size, REGION_COLS))
-    return w.reshape(-1, REGION_COLS)
+    return decode_row_chunk(words, REGION_COLS, 'region-feature')
 
 
 def computeAndSerializeRegionFeatures(labels, data, outPath, outKey, chunkId, ignoreLabel=None):  # noqa: N802,N803
@@ -60,20 +53,10 @@ def computeAndSerializeRegionFeatures(labels, data, outPath, outKey, chunkId, ig
     whose label equals ``ignoreLabel`` are not counted.  No chunk is written for
     an empty result; the dataset's ``feature_names`` and ``norm`` are set
     (region_features.py:230-232)."""
-    norm = 255.0 if str(data.dtype).endswith('uint8') else 1.0
-    r = rag.region_features_handle(labels, data, ignore_label=ignoreLabel)
-    try:
+    with rag.region_features_handle(labels, data, ignore_label=ignoreLabel) as r:
         words = encode_region_chunk(r.region_rows('sums')) if r.n_nodes else None
-    finally:
-        r.free()
-    with _open(outPath) as f:
-        ds = f[outKey]
-        if words is not None:
-            ds.write_chunk([int(c) for c in chunkId], words, True)
-        if ds.attrs.get('feature_names') != FEATURE_NAMES:   # (every block writes the same two values)
-            ds.attrs['feature_names'] = FEATURE_NAMES
-        if ds.attrs.get('norm') != norm:
-            ds.attrs['norm'] = norm
+    write_block_chunk(outPath, outKey, chunkId, words,   # (every block writes the same two values)
+                      (('feature_names', FEATURE_NAMES), ('norm', rag.region_norm(data))))
 
 
 def mergeAndSerializeRegionFeatures(inputPath, inputKey, outputPath, outputKey, labelBegin, labelEnd,  # noqa: N802,N803
@@ -90,23 +73,9 @@ def mergeAndSerializeRegionFeatures(inputPath, inputKey, outputPath, outputKey, 
         if name not in FEATURE_NAMES:
             raise ValueError('Invalid feature name %s' % name)   # merge_region_features.py:106
         cols.append(1 + FEATURE_NAMES.index(name))
-    with _open(inputPath, 'r') as f:
-        ds = f[inputKey]
-        norm = float(ds.attrs['norm']) if 'norm' in ds.attrs else 1.0
-        chunks = ds.read_chunks(_grid_positions(ds), numberOfThreads)
-    parts = []
-    for c in chunks:
-        if c is None or not len(c):
-            continue
-        rows = decode_region_chunk(c)
-        sel = (rows[:, 0] >= begin) & (rows[:, 0] < end)
-        if sel.any():
-            parts.append(rows[sel])
-    rows = np.concatenate(parts) if parts else np.zeros((0, REGION_COLS), np.float64)
-    r = rag.merge_region_features_handle(rows)
-    try:
-        out = rag.region_feature_rows(r, begin, end, 'features', norm)
-    finally:
-        r.free()
+    (rows,), attrs = read_chunk_rows(inputPath, inputKey, lambda c: (decode_region_chunk(c),), begin, end,
+                                     numberOfThreads, (np.zeros((0, REGION_COLS), np.float64),))
+    with rag.merge_region_features_handle(rows) as r:
+        out = rag.region_feature_rows(r, begin, end, 'features', float(attrs.get('norm', 1.0)))
     with _open(outputPath) as f:
         f[outputKey][begin:end, :] = out[:, cols].astype(np.float32)

@@ -32,6 +32,7 @@ the reference's retry logic (cluster_tasks.py:114-159) applies unchanged.
 """
 from __future__ import annotations
 
+import itertools
 import os
 import threading
 import time
@@ -928,20 +929,42 @@ def computeAndSerializeLabelOverlaps(labels, values, outPath, outKey, chunkId,  
     ``withIgnoreLabel`` voxels whose *value* is ``ignoreLabel`` are skipped
     (block_node_labels.py:152-156 applies the ignore label to that volume;
     unpinned).  No chunk is written when no voxel counts."""
-    r = rag.label_overlaps_handle(labels, values, ignore_label=int(ignoreLabel) if withIgnoreLabel else None)
-    try:
-        if r.n_edges == 0:
-            return
-        words = encode_overlap_chunk(r.edges(), r.counts())
-    finally:
-        r.free()
-    with _open(outPath) as f:
-        f[outKey].write_chunk([int(c) for c in chunkId], words, True)
+    with rag.label_overlaps_handle(labels, values, ignore_label=int(ignoreLabel) if withIgnoreLabel else None) as r:
+        words = encode_overlap_chunk(r.edges(), r.counts()) if r.n_edges else None
+    write_block_chunk(outPath, outKey, chunkId, words)
 
 
-def _grid_positions(ds):
-    import itertools
-    return list(itertools.product(*[range((int(s) + int(c) - 1) // int(c)) for s, c in zip(ds.shape, ds.chunks)]))
+def write_block_chunk(path, key, chunk_id, words, attrs=()):
+    """A block's ``words`` as the varlen chunk of ``key`` at ``chunk_id`` -- None (the block has no row): no
+    chunk is written -- and the (name, value) pairs ``attrs`` where the dataset does not hold them yet."""
+    with _open(path) as f:
+        ds = f[key]
+        if words is not None:
+            ds.write_chunk([int(c) for c in chunk_id], words, True)
+        for name, value in attrs:
+            if ds.attrs.get(name) != value:
+                ds.attrs[name] = value
+
+
+def read_chunk_rows(path, key, decode, begin, end, n_threads, empty):
+    """Every chunk of the block dataset ``key`` decoded (missing and empty ones skipped) -> the tables of the
+    rows whose id (first column of ``decode``'s first table) is in [begin, end), chunk after chunk, one
+    concatenation per table of ``decode``; ``empty``: those tables without a row.  The dataset's attributes
+    come along."""
+    with _open(path, 'r') as f:
+        ds = f[key]
+        attrs = dict(ds.attrs.items())
+        grid = itertools.product(*[range((int(s) + int(c) - 1) // int(c)) for s, c in zip(ds.shape, ds.chunks)])
+        chunks = ds.read_chunks(list(grid), n_threads)
+    parts = []
+    for c in chunks:
+        if c is None or not len(c):
+            continue
+        tables = decode(c)
+        sel = (tables[0][:, 0] >= begin) & (tables[0][:, 0] < end)
+        if sel.any():
+            parts.append([t[sel] for t in tables])
+    return [np.concatenate(t) for t in zip(*parts)] if parts else list(empty), attrs
 
 
 def mergeAndSerializeOverlaps(inputPath, inputKey, outputPath, outputKey, max_overlap,  # noqa: N802,N803
@@ -958,34 +981,19 @@ def mergeAndSerializeOverlaps(inputPath, inputKey, outputPath, outputKey, max_ov
     has no further effect: the block stage already dropped those pairs, and the
     caller passes 0 both for "none" and for "0" (merge_node_labels.py:154)."""
     begin, end = int(labelBegin), int(labelEnd)
-    with _open(inputPath, 'r') as f:
-        ds = f[inputKey]
-        chunks = ds.read_chunks(_grid_positions(ds), numberOfThreads)
-    parts = []
-    for c in chunks:
-        if c is None or not len(c):
-            continue
-        p, n = decode_overlap_chunk(c)
-        sel = (p[:, 0] >= begin) & (p[:, 0] < end)
-        if sel.any():
-            parts.append((p[sel], n[sel]))
-    pairs = np.concatenate([p for p, _ in parts]) if parts else np.zeros((0, 2), np.uint64)
-    counts = np.concatenate([n for _, n in parts]) if parts else np.zeros(0, np.uint64)
-    r = rag.merge_overlaps_handle(pairs, counts)
-    try:
-        with _open(outputPath) as f:
-            out = f[outputKey]
-            if max_overlap:
-                best, n_best = rag.max_overlaps(r, begin, end)
-                if serializeCount:
-                    out[begin:end, :] = np.stack([best, n_best], axis=1)
-                else:
-                    out[begin:end] = best
-            elif r.n_edges:
-                out.write_chunk([begin // int(out.chunks[0])] + [0] * (out.ndim - 1),
-                                encode_overlap_chunk(r.edges(), r.counts()), True)
-    finally:
-        r.free()
+    (pairs, counts), _ = read_chunk_rows(inputPath, inputKey, decode_overlap_chunk, begin, end, numberOfThreads,
+                                         (np.zeros((0, 2), np.uint64), np.zeros(0, np.uint64)))
+    with rag.merge_overlaps_handle(pairs, counts) as r, _open(outputPath) as f:
+        out = f[outputKey]
+        if max_overlap:
+            best, n_best = rag.max_overlaps(r, begin, end)
+            if serializeCount:
+                out[begin:end, :] = np.stack([best, n_best], axis=1)
+            else:
+                out[begin:end] = best
+        elif r.n_edges:
+            out.write_chunk([begin // int(out.chunks[0])] + [0] * (out.ndim - 1),
+                            encode_overlap_chunk(r.edges(), r.counts()), True)
 
 
 def deserializeOverlapChunk(path, key, chunkId=None):  # noqa: N802,N803
@@ -1024,20 +1032,30 @@ def deserializeOverlapChunk(path, key, chunkId=None):  # noqa: N802,N803
 MORPH_COLS = rag.MORPH_COLS
 
 
+def encode_row_chunk(rows, cols, noun):
+    """(n, cols) float64 rows -> the words of a row chunk: the rows one after the other."""
+    rows = np.asarray(rows, dtype=np.float64)
+    if rows.size % cols or (rows.ndim == 2 and rows.size and rows.shape[1] != cols):
+        raise ValueError('%s rows have %d columns, got shape %s' % (noun, cols, rows.shape))
+    return np.ascontiguousarray(rows).reshape(-1)
+
+
+def decode_row_chunk(words, cols, noun):
+    """The words of a row chunk -> (n, cols) float64 rows in the chunk's order."""
+    w = np.asarray(words, dtype=np.float64).reshape(-1)
+    if w.size % cols:
+        raise RuntimeError('%s chunk: truncated row (%d words, not a multiple of %d)' % (noun, w.size, cols))
+    return w.reshape(-1, cols)
+
+
 def encode_morphology_chunk(rows):
     """(n, 11) float64 rows -> the chunk words above."""
-    rows = np.asarray(rows, dtype=np.float64)
-    if rows.size % MORPH_COLS or (rows.ndim == 2 and rows.size and rows.shape[1] != MORPH_COLS):
-        raise ValueError('morphology rows have %d columns, got shape %s' % (MORPH_COLS, rows.shape))
-    return np.ascontiguousarray(rows).reshape(-1)
+    return encode_row_chunk(rows, MORPH_COLS, 'morphology')
 
 
 def decode_morphology_chunk(words):
     """Chunk words -> (n, 11) float64 rows in the chunk's order."""
-    w = np.asarray(words, dtype=np.float64).reshape(-1)
-    if w.size % MORPH_COLS:
-        raise RuntimeError('morphology chunk: truncated row (%d words, not a multiple of %d)' % (w.size, MORPH_COLS))
-    return w.reshape(-1, MORPH_COLS)
+    return decode_row_chunk(words, MORPH_COLS, 'morphology')
 
 
 def computeAndSerializeMorphology(labels, blockBegin, outPath, outKey, chunkId):  # noqa: N802,N803
@@ -1047,15 +1065,9 @@ def computeAndSerializeMorphology(labels, blockBegin, outPath, outKey, chunkId):
     per label its id, voxel count, centre of mass, and inclusive bounding box in
     volume coordinates.  Label 0 gets a row like any other label.  No chunk is
     written for an empty block."""
-    r = rag.morphology_handle(labels, origin=[int(b) for b in blockBegin])
-    try:
-        if r.n_nodes == 0:
-            return
-        words = encode_morphology_chunk(r.morph_rows())
-    finally:
-        r.free()
-    with _open(outPath) as f:
-        f[outKey].write_chunk([int(c) for c in chunkId], words, True)
+    with rag.morphology_handle(labels, origin=[int(b) for b in blockBegin]) as r:
+        words = encode_morphology_chunk(r.morph_rows()) if r.n_nodes else None
+    write_block_chunk(outPath, outKey, chunkId, words)
 
 
 def mergeAndSerializeMorphology(inputPath, inputKey, outputPath, outputKey, labelBegin, labelEnd,  # noqa: N802,N803
@@ -1066,22 +1078,9 @@ def mergeAndSerializeMorphology(inputPath, inputKey, outputPath, outputKey, labe
     centre of mass is the quotient of the added integer coordinate sums.
     Labels without a row get a row of zeros."""
     begin, end = int(labelBegin), int(labelEnd)
-    with _open(inputPath, 'r') as f:
-        ds = f[inputKey]
-        chunks = ds.read_chunks(_grid_positions(ds), numberOfThreads)
-    parts = []
-    for c in chunks:
-        if c is None or not len(c):
-            continue
-        rows = decode_morphology_chunk(c)
-        sel = (rows[:, 0] >= begin) & (rows[:, 0] < end)
-        if sel.any():
-            parts.append(rows[sel])
-    rows = np.concatenate(parts) if parts else np.zeros((0, MORPH_COLS), np.float64)
-    r = rag.merge_morphology_handle(rows)
-    try:
+    (rows,), _ = read_chunk_rows(inputPath, inputKey, lambda c: (decode_morphology_chunk(c),), begin, end,
+                                 numberOfThreads, (np.zeros((0, MORPH_COLS), np.float64),))
+    with rag.merge_morphology_handle(rows) as r:
         out = rag.morphology_rows(r, begin, end)
-    finally:
-        r.free()
     with _open(outputPath) as f:
         f[outputKey][begin:end, :] = out

@@ -61,11 +61,8 @@ def object_distances(label_id, ds, bb_start, bb_stop, max_distance, resolution):
     if min(face_distances) < max_distance:
         bb = _enlarge_bb(bb, face_distances, resolution, ds.shape, max_distance)
         labels, distances = _labels_and_distances(ds, bb, resolution, label_id)
-    r = rag.region_features_handle(labels, distances)
-    try:
+    with rag.region_features_handle(labels, distances) as r:
         ids, minima = r.nodes(), r.region_moments()[2][:, 0]
-    finally:
-        r.free()
     return {(label_id, int(obj)): np.float32(d) for obj, d in zip(ids, minima)
             if obj != 0 and label_id < obj and d < max_distance}
 

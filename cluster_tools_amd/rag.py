@@ -8,6 +8,7 @@ calls after reading blocks from N5.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import sys
 import threading
@@ -50,7 +51,8 @@ def _ptr(x):
 
 
 def _shape_arr(vals):
-    return (ctypes.c_int64 * 3)(*[int(v) for v in vals])
+    """Three int64 for the library; None stays a null pointer (the library's default)."""
+    return None if vals is None else (ctypes.c_int64 * 3)(*[int(v) for v in vals])
 
 
 def _handle_stream(stream=None):
@@ -65,20 +67,63 @@ def _handle_stream(stream=None):
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class Result:
-    """Owning wrapper around a ``ctg_result*`` handle (device-resident)."""
+def _stream(stream, on_dev):
+    """The stream of a call: ``stream``, else torch's current one for tensor inputs, else the null stream."""
+    if stream is not None or not on_dev:
+        return stream
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _mem(on_dev):
+    return L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST
+
+
+class _Handle:
+    """Owning wrapper around a handle of the library (device-resident): freed
+    by free(), at the end of a ``with`` block, or at the latest with the object."""
+    _free = None   # the name of the library's free function
 
     def __init__(self, handle, device):
         self.handle = handle
         self.device = device
 
-    def __del__(self):
-        self.free()
-
     def free(self):
         if getattr(self, 'handle', None) and L is not None:
-            L.load().ctg_free(self.handle)
+            getattr(L.load(), self._free)(self.handle)
             self.handle = None
+
+    __del__ = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def _create(cls, fn, *args):
+    """lib.<fn>(*args, &handle) on the current device, checked -> cls(handle, device)."""
+    lib = L.load()
+    dev = L.init_device()
+    h = ctypes.c_void_p()
+    L.check(getattr(lib, fn)(*args, ctypes.byref(h)), fn)
+    return cls(h, dev)
+
+
+class Result(_Handle):
+    """Owning wrapper around a ``ctg_result*`` handle (device-resident)."""
+    _free = 'ctg_free'
+    # ctg_result_copy_<name>: the attribute with the number of rows, and per output the rest of its shape and its dtype
+    _TABLES = {
+        'edges': ('n_edges', [((2,), np.uint64)]),
+        'nodes': ('n_nodes', [((), np.uint64)]),
+        'features': ('n_edges', [((N_FEATURES,), np.float64)]),
+        'stats': ('n_edges', [((2,), np.float64), ((WIDE_WORDS,), np.uint32)]),
+        'counts': ('n_edges', [((), np.uint64)]),
+        'moments': ('n_nodes', [((MORPH_WORDS,), np.uint64)]),
+        'region': ('n_nodes', [((), np.uint64), ((), np.float64), ((2,), np.float32)]),
+    }
 
     @property
     def n_edges(self):
@@ -93,101 +138,32 @@ class Result:
         L.check(L.load().ctg_result_info(self.handle, ctypes.byref(a), ctypes.byref(b)), 'ctg_result_info')
         return int(a.value), int(b.value)
 
-    # --- host copies
-    def edges(self):
-        out = np.empty((self.n_edges, 2), dtype=np.uint64)
-        L.check(L.load().ctg_result_copy_edges(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_edges')
-        return out
-
-    def nodes(self):
-        out = np.empty(self.n_nodes, dtype=np.uint64)
-        L.check(L.load().ctg_result_copy_nodes(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_nodes')
-        return out
-
-    def features(self):
-        out = np.empty((self.n_edges, N_FEATURES), dtype=np.float64)
-        L.check(L.load().ctg_result_copy_features(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_features')
-        return out
-
-    def stats(self):
-        """(sums (E,2) float64, records (E,48) uint32) wide statistics."""
-        s = np.empty((self.n_edges, 2), dtype=np.float64)
-        r = np.empty((self.n_edges, WIDE_WORDS), dtype=np.uint32)
-        L.check(L.load().ctg_result_copy_stats(self.handle, _ptr(s), _ptr(r), L.CTG_MEM_HOST), 'copy_stats')
-        return s, r
-
-    def counts(self):
-        """(E,) uint64 voxel counts of an overlaps result."""
-        out = np.empty(self.n_edges, dtype=np.uint64)
-        L.check(L.load().ctg_result_copy_counts(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_counts')
-        return out
-
-    def moments(self):
-        """(N,10) uint64 moments of a morphology result."""
-        out = np.empty((self.n_nodes, MORPH_WORDS), dtype=np.uint64)
-        L.check(L.load().ctg_result_copy_moments(self.handle, _ptr(out), L.CTG_MEM_HOST), 'copy_moments')
-        return out
-
-    def morph_rows(self, stream=None):
-        """(N,11) float64 rows of a morphology result, ids ascending."""
-        out = np.empty((self.n_nodes, MORPH_COLS), dtype=np.float64)
-        L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, _ptr(out), L.CTG_MEM_HOST,
-                                             _handle_stream(stream)),
-                'ctg_morphology_rows')
-        return out
-
-    def region_moments(self):
-        """(counts (N,) uint64, sums (N,) float64, minmax (N,2) float32) of a
-        region-features result."""
-        n = self.n_nodes
-        c, s, m = np.empty(n, np.uint64), np.empty(n, np.float64), np.empty((n, 2), np.float32)
-        L.check(L.load().ctg_result_copy_region(self.handle, _ptr(c), _ptr(s), _ptr(m), L.CTG_MEM_HOST),
-                'copy_region')
-        return c, s, m
-
-    def region_rows(self, form='sums', norm=1.0, stream=None):
-        """(N,5) float64 rows of a region-features result, ids ascending:
-        [id, count, sum, min, max] (``form`` 'sums') or [id, count, mean,
-        minimum, maximum] over ``norm`` ('features')."""
-        out = np.empty((self.n_nodes, REGION_COLS), dtype=np.float64)
-        L.check(L.load().ctg_region_rows(self.handle, 0, 0, _region_form(form), float(norm), None, _ptr(out),
-                                         L.CTG_MEM_HOST, _handle_stream(stream)), 'ctg_region_rows')
-        return out
-
-    # --- device copies (torch)
-    def region_rows_torch(self, form='sums', norm=1.0, stream=None):
-        """(N,5) float64 tensor of the rows of a region-features result."""
+    def _new(self, n, tail, dtype, on_dev):
+        """A new output of ``n`` rows: a numpy array, or with ``on_dev`` a tensor on the handle's device
+        (unsigned words as the signed type of their width)."""
+        if not on_dev:
+            return np.empty((n,) + tail, dtype=dtype)
         import torch
-        t = torch.empty((self.n_nodes, REGION_COLS), dtype=torch.float64, device='cuda:%d' % self.device)
-        L.check(L.load().ctg_region_rows(self.handle, 0, 0, _region_form(form), float(norm), None,
-                                         ctypes.c_void_p(t.data_ptr()), L.CTG_MEM_DEVICE, _handle_stream(stream)),
-                'ctg_region_rows')
-        return t
+        return torch.empty((n,) + tail, dtype=getattr(torch, dtype.__name__.replace('uint', 'int')),
+                           device='cuda:%d' % self.device)
 
-    def moments_torch(self):
-        """(N,10) int64 tensor of the uint64 moments of a morphology result."""
-        import torch
-        return self._torch_copy((self.n_nodes, MORPH_WORDS), torch.int64, L.load().ctg_result_copy_moments)
+    def _copy(self, name, on_dev=False):
+        """The table(s) ``name`` of _TABLES in new host arrays, or with ``on_dev`` in new tensors."""
+        count, specs = self._TABLES[name]
+        n = getattr(self, count)
+        outs = [self._new(n, tail, dtype, on_dev) for tail, dtype in specs]
+        if on_dev:
+            self._before_device_copy()
+        rc = getattr(L.load(), 'ctg_result_copy_' + name)(self.handle, *[_ptr(o) for o in outs], _mem(on_dev))
+        L.check(rc, 'device copy' if on_dev and len(outs) == 1 else 'copy_' + name)
+        return outs[0] if len(outs) == 1 else tuple(outs)
 
-    def morph_rows_torch(self, stream=None):
-        """(N,11) float64 tensor of the rows of a morphology result."""
-        import torch
-        t = torch.empty((self.n_nodes, MORPH_COLS), dtype=torch.float64, device='cuda:%d' % self.device)
-        L.check(L.load().ctg_morphology_rows(self.handle, 0, 0, None, ctypes.c_void_p(t.data_ptr()),
-                                             L.CTG_MEM_DEVICE, _handle_stream(stream)), 'ctg_morphology_rows')
-        return t
-
-    def counts_torch(self):
-        """(E,) int64 tensor of the uint64 counts of an overlaps result."""
-        import torch
-        return self._torch_copy((self.n_edges,), torch.int64, L.load().ctg_result_copy_counts)
-
-    def _torch_copy(self, shape, dtype, fn):
-        import torch
-        t = torch.empty(shape, dtype=dtype, device='cuda:%d' % self.device)
-        self._before_device_copy()
-        L.check(fn(self.handle, ctypes.c_void_p(t.data_ptr()), L.CTG_MEM_DEVICE), 'device copy')
-        return t
+    def _rows(self, fn, cols, args, on_dev, stream):
+        """The float64 rows of every node, ids ascending: lib.<fn>(handle, 0, 0, *args, no dense table, rows, ...)."""
+        out = self._new(self.n_nodes, (cols,), np.float64, on_dev)
+        L.check(getattr(L.load(), fn)(self.handle, 0, 0, *args, None, _ptr(out), _mem(on_dev),
+                                      _handle_stream(stream)), fn)
+        return out
 
     @staticmethod
     def _before_device_copy():
@@ -197,48 +173,77 @@ class Result:
         import torch
         torch.cuda.current_stream().synchronize()
 
+    # --- host copies
+    def edges(self):
+        return self._copy('edges')
+
+    def nodes(self):
+        return self._copy('nodes')
+
+    def features(self):
+        return self._copy('features')
+
+    def stats(self):
+        """(sums (E,2) float64, records (E,48) uint32) wide statistics."""
+        return self._copy('stats')
+
+    def counts(self):
+        """(E,) uint64 voxel counts of an overlaps result."""
+        return self._copy('counts')
+
+    def moments(self):
+        """(N,10) uint64 moments of a morphology result."""
+        return self._copy('moments')
+
+    def morph_rows(self, stream=None):
+        """(N,11) float64 rows of a morphology result, ids ascending."""
+        return self._rows('ctg_morphology_rows', MORPH_COLS, (), False, stream)
+
+    def region_moments(self):
+        """(counts (N,) uint64, sums (N,) float64, minmax (N,2) float32) of a
+        region-features result."""
+        return self._copy('region')
+
+    def region_rows(self, form='sums', norm=1.0, stream=None):
+        """(N,5) float64 rows of a region-features result, ids ascending:
+        [id, count, sum, min, max] (``form`` 'sums') or [id, count, mean,
+        minimum, maximum] over ``norm`` ('features')."""
+        return self._rows('ctg_region_rows', REGION_COLS, (_region_form(form), float(norm)), False, stream)
+
+    # --- device copies (torch); uint64 tables as int64 tensors, the records as int32
+    def region_rows_torch(self, form='sums', norm=1.0, stream=None):
+        """(N,5) float64 tensor of the rows of a region-features result."""
+        return self._rows('ctg_region_rows', REGION_COLS, (_region_form(form), float(norm)), True, stream)
+
+    def moments_torch(self):
+        """(N,10) int64 tensor of the uint64 moments of a morphology result."""
+        return self._copy('moments', True)
+
+    def morph_rows_torch(self, stream=None):
+        """(N,11) float64 tensor of the rows of a morphology result."""
+        return self._rows('ctg_morphology_rows', MORPH_COLS, (), True, stream)
+
+    def counts_torch(self):
+        """(E,) int64 tensor of the uint64 counts of an overlaps result."""
+        return self._copy('counts', True)
+
     def edges_torch(self):
         import torch
-        t = self._torch_copy((self.n_edges, 2), torch.int64, L.load().ctg_result_copy_edges)
+        t = self._copy('edges', True)
         return t.view(torch.uint64) if hasattr(torch, 'uint64') else t
 
     def nodes_torch(self):
-        import torch
-        return self._torch_copy((self.n_nodes,), torch.int64, L.load().ctg_result_copy_nodes)
+        return self._copy('nodes', True)
 
     def edges_torch_i64(self):
         """(E,2) int64 view of the uint64 edge table (labels < 2^63)."""
-        import torch
-        return self._torch_copy((self.n_edges, 2), torch.int64, L.load().ctg_result_copy_edges)
+        return self._copy('edges', True)
 
     def features_torch(self):
-        import torch
-        return self._torch_copy((self.n_edges, N_FEATURES), torch.float64, L.load().ctg_result_copy_features)
+        return self._copy('features', True)
 
     def stats_torch(self):
-        import torch
-        s = torch.empty((self.n_edges, 2), dtype=torch.float64, device='cuda:%d' % self.device)
-        r = torch.empty((self.n_edges, WIDE_WORDS), dtype=torch.int32, device='cuda:%d' % self.device)
-        self._before_device_copy()
-        L.check(L.load().ctg_result_copy_stats(self.handle, ctypes.c_void_p(s.data_ptr()),
-                                               ctypes.c_void_p(r.data_ptr()), L.CTG_MEM_DEVICE), 'copy_stats')
-        return s, r
-
-
-def _current_stream(tensor_input):
-    if not tensor_input:
-        return None
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _stream(stream, on_dev):
-    """The stream of a call: ``stream``, else torch's current one for tensor inputs, else the null stream."""
-    return _current_stream(on_dev) if stream is None else stream
-
-
-def _mem(on_dev):
-    return L.CTG_MEM_DEVICE if on_dev else L.CTG_MEM_HOST
+        return self._copy('stats', True)
 
 
 def _box(shape, begin, end):
@@ -305,8 +310,6 @@ def rag_features_handle(labels, data=None, offsets=None, own_begin=None, own_end
     CTG_DEFER_STATS) writes no statistics rows -- the exchange rebuilds the
     rows it needs from this call's records, valid until the next call.
     """
-    lib = L.load()
-    dev = L.init_device()
     on_dev = _is_torch(labels)
     if on_dev:
         import torch
@@ -352,29 +355,26 @@ def rag_features_handle(labels, data=None, offsets=None, own_begin=None, own_end
             raise ValueError('boundary map shape %s != labels shape %s' % (tuple(data.shape), tuple(shape)))
     flags = ((L.CTG_KEEP_STATS if keep_stats else 0) | (L.CTG_NO_ADJ_FILTER if no_adj_filter else 0) |
              (L.CTG_DEFER_STATS if keep_stats and defer_stats else 0))
-    sh = _shape_arr(shape)
-    ob = _shape_arr(own_begin) if own_begin is not None else None
-    oe = _shape_arr(own_end) if own_end is not None else None
-    h = ctypes.c_void_p()
-    rc = lib.ctg_rag_features(_ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr, sh, ob, oe,
-                              int(bool(ignore_label)), float(hist_range[0]), float(hist_range[1]),
-                              flags, _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_rag_features')
-    return Result(h, dev)
+    return _create(Result, 'ctg_rag_features', _ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr,
+                   _shape_arr(shape), _shape_arr(own_begin), _shape_arr(own_end), int(bool(ignore_label)),
+                   float(hist_range[0]), float(hist_range[1]), flags, _mem(on_dev), _stream(stream, on_dev))
 
 
 def rag_features(labels, data=None, offsets=None, own_begin=None, own_end=None, ignore_label=False,
                  hist_range=(0.0, 1.0), keep_stats=False, no_adj_filter=False):
     """Host convenience: returns dict(edges, nodes, features[, sums, records])."""
-    r = rag_features_handle(labels, data, offsets, own_begin, own_end, ignore_label, hist_range, keep_stats,
-                            no_adj_filter=no_adj_filter)
-    out = dict(edges=r.edges(), nodes=r.nodes())
-    if data is not None:
-        out['features'] = r.features()
-        if keep_stats:
-            out['sums'], out['records'] = r.stats()
+    with rag_features_handle(labels, data, offsets, own_begin, own_end, ignore_label, hist_range, keep_stats,
+                             no_adj_filter=no_adj_filter) as r:
+        out = dict(edges=r.edges(), nodes=r.nodes())
+        if data is not None:
+            out['features'] = r.features()
+            if keep_stats:
+                out['sums'], out['records'] = r.stats()
+        return _with_info(r, out)
+
+
+def _with_info(r, out):
     out['n_records'], out['n_direct'] = r.info()
-    r.free()
     return out
 
 
@@ -471,8 +471,6 @@ def rag_blocks_arena(labels, blocks, data=None, offsets=None, ignore_label=False
     data: None or 1-D float32/uint8 array; blocks: list of dicts with
     label_offset, data_offset, shape, own=(begin, end), graph=(begin, end).
     Returns one dict per block: nodes, edges[, features, sums, records]."""
-    lib = L.load()
-    dev = L.init_device()
     on_dev = _is_torch(labels)
     if on_dev:   # device-resident arenas (torch CUDA tensors, int64/int32 views of the labels)
         import torch
@@ -509,24 +507,18 @@ def rag_blocks_arena(labels, blocks, data=None, offsets=None, ignore_label=False
             off_ptr = off.ctypes.data_as(ctypes.c_void_p)
     desc = _desc(blocks)
     flags = (L.CTG_KEEP_STATS if keep_stats else 0) | (0 if nodes else L.CTG_NO_NODES)
-    h = ctypes.c_void_p()
-    rc = lib.ctg_rag_blocks(_ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr,
-                            ctypes.cast(desc, ctypes.c_void_p), len(blocks), n_lab, n_dat,
-                            int(bool(ignore_label)), float(hist_range[0]), float(hist_range[1]), flags,
-                            _mem(on_dev),
-                            _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_rag_blocks')
-    r = Result(h, dev)
     nb = len(blocks)
     eoff = np.zeros(nb + 1, np.int64)
     noff = np.zeros(nb + 1, np.int64)
-    L.check(lib.ctg_result_block_offsets(r.handle, _ptr(eoff), _ptr(noff)), 'ctg_result_block_offsets')
-    edges, nodes = r.edges(), r.nodes()
-    feats = r.features() if data is not None else None
-    sums = recs = None
-    if keep_stats and data is not None:
-        sums, recs = r.stats()
-    r.free()
+    with _create(Result, 'ctg_rag_blocks', _ptr(labels), label_bits, _ptr(data), kind, n_ch, off_ptr,
+                 ctypes.cast(desc, ctypes.c_void_p), nb, n_lab, n_dat, int(bool(ignore_label)),
+                 float(hist_range[0]), float(hist_range[1]), flags, _mem(on_dev), _stream(stream, on_dev)) as r:
+        L.check(L.load().ctg_result_block_offsets(r.handle, _ptr(eoff), _ptr(noff)), 'ctg_result_block_offsets')
+        edges, nodes = r.edges(), r.nodes()
+        feats = r.features() if data is not None else None
+        sums = recs = None
+        if keep_stats and data is not None:
+            sums, recs = r.stats()
     out = []
     for b in range(nb):
         e0, e1, n0, n1 = eoff[b], eoff[b + 1], noff[b], noff[b + 1]
@@ -564,30 +556,17 @@ def rag_blocks(arrays, own, graph, data=None, offsets=None, ignore_label=False, 
 
 def unique_labels(labels, begin=None, end=None, stream=None):
     """Sorted unique labels of labels[begin:end] (uint64 numpy array)."""
-    lib = L.load()
-    L.init_device()
     on_dev = _is_torch(labels)
     if not on_dev:
         labels = np.ascontiguousarray(np.asarray(labels).astype(np.uint64, copy=False))
-    shape = tuple(labels.shape)
-    h = ctypes.c_void_p()
-    rc = lib.ctg_unique_labels(_ptr(labels), _shape_arr(shape),
-                               _shape_arr(begin) if begin is not None else None,
-                               _shape_arr(end) if end is not None else None,
-                               _mem(on_dev),
-                               _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_unique_labels')
-    r = Result(h, L.init_device())
-    nodes = r.nodes()
-    r.free()
-    return nodes
+    with _create(Result, 'ctg_unique_labels', _ptr(labels), _shape_arr(tuple(labels.shape)), _shape_arr(begin),
+                 _shape_arr(end), _mem(on_dev), _stream(stream, on_dev)) as r:
+        return r.nodes()
 
 
 def merge_stats_handle(keys, sums, records, hist_range=(0.0, 1.0), keep_stats=False, stream=None):
     """Device-resident merge of partial statistics: keys (n,2), sums (n,2)
     float64, records (n,48) 32-bit words; numpy (host) or CUDA tensors."""
-    lib = L.load()
-    dev = L.init_device()
     on_dev = _is_torch(keys)
     if on_dev:
         for t in (keys, sums, records):
@@ -602,37 +581,27 @@ def merge_stats_handle(keys, sums, records, hist_range=(0.0, 1.0), keep_stats=Fa
         records = np.ascontiguousarray(np.asarray(records, dtype=np.uint32).reshape(-1, WIDE_WORDS))
         n = keys.shape[0]
         assert sums.shape[0] == n and records.shape[0] == n
-    h = ctypes.c_void_p()
-    rc = lib.ctg_merge_stats(_ptr(keys), _ptr(sums), _ptr(records), n, float(hist_range[0]),
-                             float(hist_range[1]), int(bool(keep_stats)),
-                             _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_merge_stats')
-    return Result(h, dev)
+    return _create(Result, 'ctg_merge_stats', _ptr(keys), _ptr(sums), _ptr(records), n, float(hist_range[0]),
+                   float(hist_range[1]), int(bool(keep_stats)), _mem(on_dev), _stream(stream, on_dev))
 
 
 def unique_values_handle(values, stream=None):
     """Sorted unique values of a uint64 list (numpy or CUDA int64 tensor) -> Result (nodes)."""
-    lib = L.load()
-    dev = L.init_device()
     on_dev = _is_torch(values)
     if not on_dev:
         values = np.ascontiguousarray(np.asarray(values, dtype=np.uint64).reshape(-1))
     else:
         assert values.is_cuda and values.is_contiguous() and values.element_size() == 8
-    h = ctypes.c_void_p()
-    L.check(lib.ctg_unique_values(_ptr(values), int(values.shape[0]),
-                                  _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h)),
-            'ctg_unique_values')
-    return Result(h, dev)
+    return _create(Result, 'ctg_unique_values', _ptr(values), int(values.shape[0]), _mem(on_dev),
+                   _stream(stream, on_dev))
 
 
 def merge_stats(keys, sums, records, hist_range=(0.0, 1.0), keep_stats=False):
     """Combine partial statistics tables (wide records) -> dict(edges, features[, sums, records])."""
-    r = merge_stats_handle(keys, sums, records, hist_range, keep_stats)
-    out = dict(edges=r.edges(), features=r.features())
-    if keep_stats:
-        out['sums'], out['records'] = r.stats()
-    r.free()
+    with merge_stats_handle(keys, sums, records, hist_range, keep_stats) as r:
+        out = dict(edges=r.edges(), features=r.features())
+        if keep_stats:
+            out['sums'], out['records'] = r.stats()
     return out
 
 
@@ -653,15 +622,9 @@ def merge_feature_rows(ids, rows, id_begin, id_end, stream=None):
 
 def unique_pairs(pairs, stream=None):
     """Sorted unique rows of an (n,2) uint64 pair list -> (edges, nodes)."""
-    lib = L.load()
-    dev = L.init_device()
     p = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint64).reshape(-1, 2))
-    h = ctypes.c_void_p()
-    L.check(lib.ctg_unique_pairs(_ptr(p), p.shape[0], L.CTG_MEM_HOST, stream, ctypes.byref(h)), 'ctg_unique_pairs')
-    r = Result(h, dev)
-    out = r.edges(), r.nodes()
-    r.free()
-    return out
+    with _create(Result, 'ctg_unique_pairs', _ptr(p), p.shape[0], L.CTG_MEM_HOST, stream) as r:
+        return r.edges(), r.nodes()
 
 
 def map_edge_ids(global_edges, query, stream=None):
@@ -691,6 +654,46 @@ def _label_volume(x, name):
     return np.ascontiguousarray(x), x.dtype.itemsize * 8
 
 
+def _data_volume(x, on_dev):
+    """A data volume argument (of the caller's kind: ``on_dev``) -> (array, CTG_DATA_*): float32 or uint8."""
+    if on_dev:
+        import torch
+        if not (x.is_cuda and x.is_contiguous()) or x.dtype not in (torch.float32, torch.uint8):
+            raise ValueError('data must be a contiguous float32 or uint8 CUDA tensor')
+        return x, L.CTG_DATA_U8 if x.dtype == torch.uint8 else L.CTG_DATA_F32
+    x = np.asarray(x)
+    if x.dtype not in (np.float32, np.uint8):
+        raise TypeError('data must be float32 or uint8, got %s' % x.dtype)
+    return np.ascontiguousarray(x), L.CTG_DATA_U8 if x.dtype == np.uint8 else L.CTG_DATA_F32
+
+
+def _volume_call(fn, labels, second, name, triples, ignore_label, stream):
+    """The three calls that scan a label volume -> their ``Result``: lib.<fn>(labels, bits[, second, its code],
+    shape, *triples[, whether to ignore, ignore_label], mem, stream).  ``second``: the ``values`` to overlap
+    with, the ``data`` to accumulate, or no second volume (``name`` None, and no ignore label then).  A triple
+    that is None stays a null pointer: the library does the defaulting and the range check."""
+    if name and _is_torch(labels) != _is_torch(second):
+        raise ValueError('labels and %s must both be numpy arrays or both CUDA tensors' % name)
+    labels, bits = _label_volume(labels, 'labels')
+    on_dev = _is_torch(labels)
+    args = [_ptr(labels), bits]
+    if name:
+        second, code = _label_volume(second, name) if name == 'values' else _data_volume(second, on_dev)
+        args += [_ptr(second), code]
+    shape = tuple(labels.shape)
+    if len(shape) != 3:
+        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
+    if name and tuple(second.shape) != shape:
+        raise ValueError('%s shape %s != labels shape %s' % (name, tuple(second.shape), shape))
+    if any(t is not None and len(t) != 3 for t in triples):
+        raise ValueError('%s must have 3 entries' % ' / '.join(('begin', 'end', 'origin')[:len(triples)]))
+    if ignore_label is not None and not 0 <= int(ignore_label) < 1 << 64:
+        raise ValueError('ignore_label must be a uint64 value or None, got %r' % (ignore_label,))
+    ignore = [int(ignore_label is not None), int(ignore_label or 0)] if name else []
+    return _create(Result, fn, *args, _shape_arr(shape), *[_shape_arr(t) for t in triples], *ignore, _mem(on_dev),
+                   _stream(stream, on_dev))
+
+
 def label_overlaps_handle(labels, values, begin=None, end=None, ignore_label=None, stream=None):
     """ctg_label_overlaps -> the device-resident ``Result``: edges() = the
     distinct (labels[p], values[p]) pairs of the box [begin, end), sorted;
@@ -698,31 +701,7 @@ def label_overlaps_handle(labels, values, begin=None, end=None, ignore_label=Non
     *value* equals ``ignore_label`` are skipped (None: every voxel counts,
     zeros included).  Both volumes numpy arrays or both CUDA tensors, (Z,Y,X),
     32- or 64-bit integers."""
-    if _is_torch(labels) != _is_torch(values):
-        raise ValueError('labels and values must both be numpy arrays or both CUDA tensors')
-    labels, lbits = _label_volume(labels, 'labels')
-    values, vbits = _label_volume(values, 'values')
-    shape = tuple(labels.shape)
-    if len(shape) != 3:
-        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
-    if tuple(values.shape) != shape:
-        raise ValueError('values shape %s != labels shape %s' % (tuple(values.shape), shape))
-    for box in (begin, end):
-        if box is not None and len(box) != 3:
-            raise ValueError('begin / end must have 3 entries')
-    if ignore_label is not None and not 0 <= int(ignore_label) < 1 << 64:
-        raise ValueError('ignore_label must be a uint64 value or None, got %r' % (ignore_label,))
-    lib = L.load()
-    dev = L.init_device()
-    on_dev = _is_torch(labels)
-    h = ctypes.c_void_p()
-    rc = lib.ctg_label_overlaps(_ptr(labels), lbits, _ptr(values), vbits, _shape_arr(shape),
-                                _shape_arr(begin) if begin is not None else None,
-                                _shape_arr(end) if end is not None else None,
-                                int(ignore_label is not None), int(ignore_label or 0),
-                                _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_label_overlaps')
-    return Result(h, dev)
+    return _volume_call('ctg_label_overlaps', labels, values, 'values', (begin, end), ignore_label, stream)
 
 
 def _overlap_tables(r):
@@ -732,11 +711,8 @@ def _overlap_tables(r):
 def label_overlaps(labels, values, begin=None, end=None, ignore_label=None):
     """Host convenience of label_overlaps_handle: dict(pairs (E,2), counts (E,),
     nodes (N,)) as uint64 numpy arrays (+ n_records, n_direct)."""
-    r = label_overlaps_handle(labels, values, begin, end, ignore_label)
-    out = _overlap_tables(r)
-    out['n_records'], out['n_direct'] = r.info()
-    r.free()
-    return out
+    with label_overlaps_handle(labels, values, begin, end, ignore_label) as r:
+        return _with_info(r, _overlap_tables(r))
 
 
 def merge_overlaps_handle(pairs, counts, stream=None):
@@ -758,21 +734,31 @@ def merge_overlaps_handle(pairs, counts, stream=None):
         n = counts.shape[0]
         if pairs.shape[0] != n:
             raise ValueError('%d pairs for %d counts' % (pairs.shape[0], n))
-    lib = L.load()
-    dev = L.init_device()
-    h = ctypes.c_void_p()
-    rc = lib.ctg_merge_overlaps(_ptr(pairs), _ptr(counts), n, _mem(on_dev), _stream(stream, on_dev),
-                                ctypes.byref(h))
-    L.check(rc, 'ctg_merge_overlaps')
-    return Result(h, dev)
+    return _create(Result, 'ctg_merge_overlaps', _ptr(pairs), _ptr(counts), n, _mem(on_dev), _stream(stream, on_dev))
 
 
 def merge_overlaps(pairs, counts):
     """Host convenience of merge_overlaps_handle: dict(pairs, counts, nodes)."""
-    r = merge_overlaps_handle(pairs, counts)
-    out = _overlap_tables(r)
-    r.free()
-    return out
+    with merge_overlaps_handle(pairs, counts) as r:
+        return _overlap_tables(r)
+
+
+def _label_range(label_begin, label_end):
+    lb, le = int(label_begin), int(label_end)
+    if lb < 0 or le < lb:
+        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
+    return lb, le
+
+
+def _read_dense(handle_or_tables, merge, keys, stream, fn, *args):
+    """The dense-table readers: lib.<fn>(handle, *args, host memory, stream) on ``handle_or_tables`` -- a
+    ``Result`` as it is, or a dict whose ``keys`` go through ``merge`` first; that handle ends here."""
+    if isinstance(handle_or_tables, Result):
+        scope = contextlib.nullcontext(handle_or_tables)
+    else:
+        scope = merge(*[handle_or_tables[k] for k in keys], stream)
+    with scope as r:
+        L.check(getattr(L.load(), fn)(r.handle, *args, L.CTG_MEM_HOST, _handle_stream(stream)), fn)
 
 
 def max_overlaps(handle_or_tables, label_begin, label_end, stream=None):
@@ -781,20 +767,11 @@ def max_overlaps(handle_or_tables, label_begin, label_end, stream=None):
     entries, 0 / 0 for labels without a row; equal counts go to the smallest
     value.  ``handle_or_tables``: a ``Result`` of label_overlaps_handle /
     merge_overlaps_handle, or a dict with 'pairs' and 'counts' (merged first)."""
-    lb, le = int(label_begin), int(label_end)
-    if lb < 0 or le < lb:
-        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
-    own = not isinstance(handle_or_tables, Result)
-    r = merge_overlaps_handle(handle_or_tables['pairs'], handle_or_tables['counts'], stream) if own \
-        else handle_or_tables
+    lb, le = _label_range(label_begin, label_end)
     out_l = np.zeros(le - lb, dtype=np.uint64)
     out_c = np.zeros(le - lb, dtype=np.uint64)
-    try:
-        L.check(L.load().ctg_max_overlaps(r.handle, lb, le, _ptr(out_l), _ptr(out_c), L.CTG_MEM_HOST,
-                                          _handle_stream(stream)), 'ctg_max_overlaps')
-    finally:
-        if own:
-            r.free()
+    _read_dense(handle_or_tables, merge_overlaps_handle, ('pairs', 'counts'), stream, 'ctg_max_overlaps', lb, le,
+                _ptr(out_l), _ptr(out_c))
     return out_l, out_c
 
 
@@ -806,24 +783,7 @@ def morphology_handle(labels, begin=None, end=None, origin=None, stream=None):
     coordinate of the voxel at array index p is p + ``origin`` (the block's
     begin when ``labels`` is one block of a volume).  A numpy array or a CUDA
     tensor, (Z,Y,X), 32- or 64-bit integers; label 0 is a label like any other."""
-    labels, bits = _label_volume(labels, 'labels')
-    shape = tuple(labels.shape)
-    if len(shape) != 3:
-        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
-    for box in (begin, end, origin):
-        if box is not None and len(box) != 3:
-            raise ValueError('begin / end / origin must have 3 entries')
-    lib = L.load()
-    dev = L.init_device()
-    on_dev = _is_torch(labels)
-    h = ctypes.c_void_p()
-    rc = lib.ctg_morphology(_ptr(labels), bits, _shape_arr(shape),
-                            _shape_arr(begin) if begin is not None else None,
-                            _shape_arr(end) if end is not None else None,
-                            _shape_arr(origin) if origin is not None else None,
-                            _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_morphology')
-    return Result(h, dev)
+    return _volume_call('ctg_morphology', labels, None, None, (begin, end, origin), None, stream)
 
 
 def _morphology_tables(r):
@@ -835,21 +795,12 @@ def morphology(labels, begin=None, end=None, origin=None):
     (N,10) uint64, rows (N,11) float64, n_records, n_direct).  A label of 2^53
     or more does not fit the rows' id column: use the handle's nodes() and
     moments() for such volumes."""
-    r = morphology_handle(labels, begin, end, origin)
-    try:
-        out = _morphology_tables(r)
-        out['n_records'], out['n_direct'] = r.info()
-    finally:
-        r.free()
-    return out
+    with morphology_handle(labels, begin, end, origin) as r:
+        return _with_info(r, _morphology_tables(r))
 
 
-def merge_morphology_handle(rows, stream=None):
-    """ctg_merge_morphology: (n,11) float64 rows of partial tables, in any
-    order -> the table in which the rows of one id are combined (``Result``):
-    sizes add, boxes fold, and the coordinate sums add as integers, so the
-    result equals one morphology call over the whole volume while every row's
-    sum is below 2^51."""
+def _merge_rows(fn, rows, cols, noun, stream):
+    """The two merges of float64 row tables -> their ``Result``: lib.<fn>(rows, their number, mem, stream)."""
     on_dev = _is_torch(rows)
     if on_dev:
         if not (rows.is_cuda and rows.is_contiguous()) or rows.element_size() != 8 or not rows.is_floating_point():
@@ -858,24 +809,24 @@ def merge_morphology_handle(rows, stream=None):
     else:
         rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
         size = rows.size
-    if size % MORPH_COLS or (size and rows.ndim == 2 and rows.shape[1] != MORPH_COLS):
-        raise ValueError('morphology rows have %d columns, got %s' % (MORPH_COLS, tuple(rows.shape)))
-    lib = L.load()
-    dev = L.init_device()
-    h = ctypes.c_void_p()
-    rc = lib.ctg_merge_morphology(_ptr(rows), size // MORPH_COLS, _mem(on_dev),
-                                  _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_merge_morphology')
-    return Result(h, dev)
+    if size % cols or (size and rows.ndim == 2 and rows.shape[1] != cols):
+        raise ValueError('%s rows have %d columns, got %s' % (noun, cols, tuple(rows.shape)))
+    return _create(Result, fn, _ptr(rows), size // cols, _mem(on_dev), _stream(stream, on_dev))
+
+
+def merge_morphology_handle(rows, stream=None):
+    """ctg_merge_morphology: (n,11) float64 rows of partial tables, in any
+    order -> the table in which the rows of one id are combined (``Result``):
+    sizes add, boxes fold, and the coordinate sums add as integers, so the
+    result equals one morphology call over the whole volume while every row's
+    sum is below 2^51."""
+    return _merge_rows('ctg_merge_morphology', rows, MORPH_COLS, 'morphology', stream)
 
 
 def merge_morphology(rows):
     """Host convenience of merge_morphology_handle: dict(nodes, moments, rows)."""
-    r = merge_morphology_handle(rows)
-    try:
+    with merge_morphology_handle(rows) as r:
         return _morphology_tables(r)
-    finally:
-        r.free()
 
 
 def morphology_rows(handle_or_tables, label_begin, label_end, stream=None):
@@ -883,34 +834,11 @@ def morphology_rows(handle_or_tables, label_begin, label_end, stream=None):
     [label_begin, label_end): the row of label a at a - label_begin, zeros for
     absent labels.  ``handle_or_tables``: a ``Result`` of morphology_handle /
     merge_morphology_handle, or a dict with 'rows' (merged first)."""
-    lb, le = int(label_begin), int(label_end)
-    if lb < 0 or le < lb:
-        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
-    own = not isinstance(handle_or_tables, Result)
-    r = merge_morphology_handle(handle_or_tables['rows'], stream) if own else handle_or_tables
+    lb, le = _label_range(label_begin, label_end)
     out = np.zeros((le - lb, MORPH_COLS), dtype=np.float64)
-    try:
-        L.check(L.load().ctg_morphology_rows(r.handle, lb, le, _ptr(out), None, L.CTG_MEM_HOST,
-                                             _handle_stream(stream)), 'ctg_morphology_rows')
-    finally:
-        if own:
-            r.free()
+    _read_dense(handle_or_tables, merge_morphology_handle, ('rows',), stream, 'ctg_morphology_rows', lb, le,
+                _ptr(out), None)
     return out
-
-
-def _data_volume(x, on_dev):
-    """A region-features data argument -> (array, CTG_DATA_*): float32 or uint8."""
-    if _is_torch(x) != on_dev:
-        raise ValueError('labels and data must both be numpy arrays or both CUDA tensors')
-    if on_dev:
-        import torch
-        if not (x.is_cuda and x.is_contiguous()) or x.dtype not in (torch.float32, torch.uint8):
-            raise ValueError('data must be a contiguous float32 or uint8 CUDA tensor')
-        return x, L.CTG_DATA_U8 if x.dtype == torch.uint8 else L.CTG_DATA_F32
-    x = np.asarray(x)
-    if x.dtype not in (np.float32, np.uint8):
-        raise TypeError('data must be float32 or uint8, got %s' % x.dtype)
-    return np.ascontiguousarray(x), L.CTG_DATA_U8 if x.dtype == np.uint8 else L.CTG_DATA_F32
 
 
 def region_features_handle(labels, data, begin=None, end=None, ignore_label=None, stream=None):
@@ -922,35 +850,19 @@ def region_features_handle(labels, data, begin=None, end=None, ignore_label=None
     every voxel counts, label 0 included).  Both volumes numpy arrays or both
     CUDA tensors, (Z,Y,X); labels 32- or 64-bit integers, data float32 or uint8
     (a channel of a 4-D input: pass ``data[channel]``)."""
-    labels, bits = _label_volume(labels, 'labels')
-    on_dev = _is_torch(labels)
-    data, kind = _data_volume(data, on_dev)
-    shape = tuple(labels.shape)
-    if len(shape) != 3:
-        raise ValueError('labels must be 3-D, got shape %s' % (shape,))
-    if tuple(data.shape) != shape:
-        raise ValueError('data shape %s != labels shape %s' % (tuple(data.shape), shape))
-    for box in (begin, end):
-        if box is not None and len(box) != 3:
-            raise ValueError('begin / end must have 3 entries')
-    if ignore_label is not None and not 0 <= int(ignore_label) < 1 << 64:
-        raise ValueError('ignore_label must be a uint64 value or None, got %r' % (ignore_label,))
-    lib = L.load()
-    dev = L.init_device()
-    h = ctypes.c_void_p()
-    rc = lib.ctg_region_features(_ptr(labels), bits, _ptr(data), kind, _shape_arr(shape),
-                                 _shape_arr(begin) if begin is not None else None,
-                                 _shape_arr(end) if end is not None else None,
-                                 int(ignore_label is not None), int(ignore_label or 0),
-                                 _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_region_features')
-    return Result(h, dev)
+    return _volume_call('ctg_region_features', labels, data, 'data', (begin, end), ignore_label, stream)
 
 
 def _region_tables(r, norm):
     counts, sums, minmax = r.region_moments()
     return dict(nodes=r.nodes(), counts=counts, sums=sums, minmax=minmax, rows=r.region_rows('sums'),
                 features=r.region_rows('features', norm))
+
+
+def region_norm(data):
+    """What the samples of ``data`` are divided by unless the caller says otherwise: 255 for uint8, else 1
+    (region_features.py:151-157)."""
+    return 255.0 if str(data.dtype).endswith('uint8') else 1.0
 
 
 def region_features(labels, data, begin=None, end=None, ignore_label=None, norm=None):
@@ -961,47 +873,22 @@ def region_features(labels, data, begin=None, end=None, ignore_label=None, norm=
     n_direct).  A label of 2^53 or more does not fit the rows' id column: use
     the handle's nodes() and region_moments() for such volumes."""
     if norm is None:
-        dt = data.dtype
-        norm = 255.0 if str(dt).endswith('uint8') else 1.0
-    r = region_features_handle(labels, data, begin, end, ignore_label)
-    try:
-        out = _region_tables(r, norm)
-        out['n_records'], out['n_direct'] = r.info()
-    finally:
-        r.free()
-    return out
+        norm = region_norm(data)
+    with region_features_handle(labels, data, begin, end, ignore_label) as r:
+        return _with_info(r, _region_tables(r, norm))
 
 
 def merge_region_features_handle(rows, stream=None):
     """ctg_merge_region_features: (n,5) float64 rows [id, count, sum, min, max]
     of partial tables, in any order -> the table in which the rows of one id
     are combined (``Result``): counts and sums add, min and max fold."""
-    on_dev = _is_torch(rows)
-    if on_dev:
-        if not (rows.is_cuda and rows.is_contiguous()) or rows.element_size() != 8 or not rows.is_floating_point():
-            raise ValueError('rows must be a contiguous float64 CUDA tensor')
-        size = int(rows.numel())
-    else:
-        rows = np.ascontiguousarray(np.asarray(rows, dtype=np.float64))
-        size = rows.size
-    if size % REGION_COLS or (size and rows.ndim == 2 and rows.shape[1] != REGION_COLS):
-        raise ValueError('region-feature rows have %d columns, got %s' % (REGION_COLS, tuple(rows.shape)))
-    lib = L.load()
-    dev = L.init_device()
-    h = ctypes.c_void_p()
-    rc = lib.ctg_merge_region_features(_ptr(rows), size // REGION_COLS,
-                                       _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_merge_region_features')
-    return Result(h, dev)
+    return _merge_rows('ctg_merge_region_features', rows, REGION_COLS, 'region-feature', stream)
 
 
 def merge_region_features(rows, norm=1.0):
     """Host convenience of merge_region_features_handle: the dict of region_features."""
-    r = merge_region_features_handle(rows)
-    try:
+    with merge_region_features_handle(rows) as r:
         return _region_tables(r, norm)
-    finally:
-        r.free()
 
 
 def region_feature_rows(handle_or_tables, label_begin, label_end, form='features', norm=1.0, stream=None):
@@ -1011,46 +898,30 @@ def region_feature_rows(handle_or_tables, label_begin, label_end, form='features
     label a at a - label_begin, zeros for absent labels.  ``handle_or_tables``:
     a ``Result`` of region_features_handle / merge_region_features_handle, or a
     dict with 'rows' in the sum form (merged first)."""
-    lb, le = int(label_begin), int(label_end)
-    if lb < 0 or le < lb:
-        raise ValueError('need 0 <= label_begin <= label_end, got [%d, %d)' % (lb, le))
+    lb, le = _label_range(label_begin, label_end)
     code = _region_form(form)
     if not (float(norm) > 0.0 and float(norm) < float('inf')):
         raise ValueError('norm must be finite and positive, got %r' % (norm,))
-    own = not isinstance(handle_or_tables, Result)
-    r = merge_region_features_handle(handle_or_tables['rows'], stream) if own else handle_or_tables
     out = np.zeros((le - lb, REGION_COLS), dtype=np.float64)
-    try:
-        L.check(L.load().ctg_region_rows(r.handle, lb, le, code, float(norm), _ptr(out), None, L.CTG_MEM_HOST,
-                                         _handle_stream(stream)), 'ctg_region_rows')
-    finally:
-        if own:
-            r.free()
+    _read_dense(handle_or_tables, merge_region_features_handle, ('rows',), stream, 'ctg_region_rows', lb, le, code,
+                float(norm), _ptr(out), None)
     return out
 
 
-class Assignment:
+class Assignment(_Handle):
     """Owning wrapper around a ``ctg_assignment*`` handle: a node assignment in
     device memory (assignment_dense, assignment_sparse), uploaded once and
     applied to any number of label arrays (apply_assignment)."""
+    _free = 'ctg_assignment_free'
 
     def __init__(self, handle, device):
-        self.handle = handle
-        self.device = device
+        super().__init__(handle, device)
         n, mx, kind = ctypes.c_int64(), ctypes.c_uint64(), ctypes.c_int()
         L.check(L.load().ctg_assignment_info(handle, ctypes.byref(n), ctypes.byref(mx), ctypes.byref(kind)),
                 'ctg_assignment_info')
         self.n = int(n.value)                   # entries of a dense table / pairs of a sparse one
         self.max_value = int(mx.value)          # the largest value (0: empty)
         self.kind = 'sparse' if kind.value == L.CTG_ASSIGN_SPARSE else 'dense'
-
-    def __del__(self):
-        self.free()
-
-    def free(self):
-        if getattr(self, 'handle', None) and L is not None:
-            L.load().ctg_assignment_free(self.handle)
-            self.handle = None
 
 
 def _u64_vector(x, name):
@@ -1074,13 +945,8 @@ def assignment_dense(table, stream=None):
     """ctg_assignment_dense: A(l) = table[l] (what nifty.tools.take indexes);
     labels of len(table) and above are out of range."""
     table, on_dev = _u64_vector(table, 'table')
-    lib = L.load()
-    dev = L.init_device()
-    h = ctypes.c_void_p()
-    rc = lib.ctg_assignment_dense(_ptr(table), int(table.shape[0]), _mem(on_dev),
-                                  _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_assignment_dense')
-    return Assignment(h, dev)
+    return _create(Assignment, 'ctg_assignment_dense', _ptr(table), int(table.shape[0]), _mem(on_dev),
+                   _stream(stream, on_dev))
 
 
 def assignment_sparse(keys, values, stream=None):
@@ -1093,13 +959,8 @@ def assignment_sparse(keys, values, stream=None):
         raise ValueError('keys and values must both be numpy arrays or both CUDA tensors')
     if keys.shape[0] != values.shape[0]:
         raise ValueError('%d keys for %d values' % (keys.shape[0], values.shape[0]))
-    lib = L.load()
-    dev = L.init_device()
-    h = ctypes.c_void_p()
-    rc = lib.ctg_assignment_sparse(_ptr(keys), _ptr(values), int(keys.shape[0]),
-                                   _mem(on_dev), _stream(stream, on_dev), ctypes.byref(h))
-    L.check(rc, 'ctg_assignment_sparse')
-    return Assignment(h, dev)
+    return _create(Assignment, 'ctg_assignment_sparse', _ptr(keys), _ptr(values), int(keys.shape[0]), _mem(on_dev),
+                   _stream(stream, on_dev))
 
 
 def apply_assignment(a, labels, offset=0, segments=None, allow_missing=False, out=None, check_only=False, stream=None):
@@ -1439,9 +1300,8 @@ def synth_volume(shape, cell=10, seed=0, z_offset=0, global_shape=None, label_of
     dev = L.init_device(device)
     labels = torch.empty(tuple(shape), dtype=torch.int64, device='cuda:%d' % dev)
     bnd = torch.empty(tuple(shape), dtype=torch.float32, device='cuda:%d' % dev) if with_boundary else None
-    gs = _shape_arr(global_shape) if global_shape is not None else None
-    rc = lib.ctg_synth_volume(_ptr(labels), _ptr(bnd), _shape_arr(shape), int(z_offset), gs, int(cell),
-                              int(seed), int(label_offset), float(noise_amp),
+    rc = lib.ctg_synth_volume(_ptr(labels), _ptr(bnd), _shape_arr(shape), int(z_offset), _shape_arr(global_shape),
+                              int(cell), int(seed), int(label_offset), float(noise_amp),
                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     L.check(rc, 'ctg_synth_volume')
     return labels, bnd

@@ -44,11 +44,8 @@ def take(relabeling, toRelabel):
     if table.dtype.kind == 'i' and table.size and int(table.min()) < 0:
         raise OverflowError('relabeling holds negative values: they do not fit the uint64 table')
     x = _labels(toRelabel)
-    a = rag.assignment_dense(table.astype(np.uint64, copy=False))
-    try:
+    with rag.assignment_dense(table.astype(np.uint64, copy=False)) as a:
         out, _ = rag.apply_assignment(a, x)
-    finally:
-        a.free()
     return out.reshape(x.shape).astype(table.dtype, copy=False)   # (values of the table: they fit its dtype)
 
 
@@ -68,9 +65,6 @@ def takeDict(relabeling, toRelabel):
         raise OverflowError('the keys and values of relabeling must be integers in [0, 2^64)') from None
     if n:
         _fits(int(values.max()), x.dtype, 'the value')
-    a = rag.assignment_sparse(keys, values)
-    try:
+    with rag.assignment_sparse(keys, values) as a:
         out, _ = rag.apply_assignment(a, x)
-    finally:
-        a.free()
     return out.reshape(x.shape).astype(x.dtype, copy=False)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from cluster_tools_amd import n5, ndist, rag
+from tests import chunk_cases as K
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -161,3 +162,59 @@ def test_morphology_argument_checks():
         rag.morphology_rows(dict(rows=np.zeros((0, 11))), 5, 4)
     with pytest.raises(ValueError, match='label_begin'):
         rag.morphology_rows(dict(rows=np.zeros((0, 11))), -1, 4)
+
+
+# ------------------------------------------------- the chunk loop of the merge
+def _rows_of(ids):
+    """One row per id, told apart by its size column."""
+    rows = np.zeros((len(ids), 11), np.float64)
+    rows[:, 0] = ids
+    rows[:, 1] = 100 + np.arange(len(ids))
+    return rows
+
+
+@pytest.fixture
+def morph_chunks(tmp_path):
+    path = str(tmp_path / 'm.n5')
+    K.block_dataset(path, 'blocks', 'float64', lambda ids: ndist.encode_morphology_chunk(_rows_of(ids)))
+    K.output_dataset(path, 'out', (K.N_OUT, 11), 'float64')
+    return path
+
+
+def test_merge_reads_the_rows_of_its_range_and_writes_the_slice(morph_chunks, monkeypatch):
+    handle = K.Handle()
+    merged = K.capture(monkeypatch, rag, 'merge_morphology_handle', handle)
+    dense = np.arange(4 * 11, dtype=np.float64).reshape(4, 11) + 0.5
+    read = K.capture(monkeypatch, rag, 'morphology_rows', dense)
+    ndist.mergeAndSerializeMorphology(morph_chunks, 'blocks', morph_chunks, 'out', K.BEGIN, K.END, numberOfThreads=2)
+    ((rows,), kw), = merged
+    mixed = _rows_of(K.MIXED_IDS)
+    assert not kw and rows.dtype == np.float64
+    np.testing.assert_array_equal(rows, mixed[[K.MIXED_IDS.index(a) for a in K.IN_RANGE]])
+    assert read == [((handle, K.BEGIN, K.END), {})] and handle.freed == 1
+    out = np.zeros((K.N_OUT, 11))
+    out[K.BEGIN:K.END] = dense
+    np.testing.assert_array_equal(K.read_output(morph_chunks, 'out'), out)
+
+
+def test_merge_of_an_empty_range_gets_an_empty_table(morph_chunks, monkeypatch):
+    handle = K.Handle()
+    merged = K.capture(monkeypatch, rag, 'merge_morphology_handle', handle)
+    K.capture(monkeypatch, rag, 'morphology_rows', np.zeros((0, 11)))
+    ndist.mergeAndSerializeMorphology(morph_chunks, 'blocks', morph_chunks, 'out', 12, 12)
+    ((rows,), _), = merged
+    assert rows.shape == (0, 11) and rows.dtype == np.float64 and handle.freed == 1
+
+
+def test_block_morphology_writes_its_chunk_unless_empty(tmp_path, monkeypatch):
+    path = str(tmp_path / 'b.n5')
+    K.output_dataset(path, 'blocks', (1, 1, 3), 'float64', chunks=(1, 1, 1))
+    rows = _rows_of([4, 5])
+    lab = np.zeros((1, 1, 2), np.uint64)
+    for handle, pos in ((K.Handle(n_nodes=2, morph_rows=rows), (0, 0, 1)), (K.Handle(n_nodes=0), (0, 0, 2))):
+        made = K.capture(monkeypatch, rag, 'morphology_handle', handle)
+        ndist.computeAndSerializeMorphology(lab, np.array([3, 4, 5]), path, 'blocks', pos)
+        (args, kw), = made
+        assert args[0] is lab and list(args[1:]) + list(kw.values()) == [[3, 4, 5]] and handle.freed == 1
+    np.testing.assert_array_equal(K.chunk_of(path, 'blocks', (0, 0, 1)), rows.reshape(-1))
+    assert K.chunk_of(path, 'blocks', (0, 0, 2)) is None

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from cluster_tools_amd import n5, ndist, rag
+from tests import chunk_cases as K
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -152,3 +153,97 @@ def test_merge_and_max_overlaps_argument_checks():
         rag.max_overlaps(tables, 5, 4)
     with pytest.raises(ValueError, match='label_begin'):
         rag.max_overlaps(tables, -1, 4)
+
+
+# ------------------------------------------------- the chunk loop of the merge
+def _overlap_rows(ids):
+    """Two rows per node: (node, 10 + node) once and (node, 20 + node) twice."""
+    pairs = np.array([[a, k + a] for a in ids for k in (10, 20)], np.uint64).reshape(-1, 2)
+    return pairs, np.array([1, 2] * len(ids), np.uint64)
+
+
+def _overlap_words(ids):
+    return np.array([w for a in ids for w in (a, 2, 10 + a, 1, 20 + a, 2)], np.uint64)
+
+
+@pytest.fixture
+def overlap_chunks(tmp_path):
+    path = str(tmp_path / 'ol.n5')
+    K.block_dataset(path, 'blocks', 'uint64', _overlap_words)
+    p, c = ndist.decode_overlap_chunk(_overlap_words(K.MIXED_IDS))
+    np.testing.assert_array_equal(p, _overlap_rows(K.MIXED_IDS)[0])
+    np.testing.assert_array_equal(c, _overlap_rows(K.MIXED_IDS)[1])
+    return path
+
+
+def _merged_inputs(calls):
+    (args, kw), = calls
+    assert not kw and len(args) == 2
+    return args
+
+
+@pytest.mark.parametrize('serialize_count', [False, True])
+def test_merge_reads_the_rows_of_its_range_and_writes_the_maxima(overlap_chunks, monkeypatch, serialize_count):
+    handle = K.Handle()
+    merged = K.capture(monkeypatch, rag, 'merge_overlaps_handle', handle)
+    best, n_best = np.arange(40, 44, dtype=np.uint64), np.arange(50, 54, dtype=np.uint64)
+    read = K.capture(monkeypatch, rag, 'max_overlaps', (best, n_best))
+    shape = (K.N_OUT, 2) if serialize_count else (K.N_OUT,)
+    K.output_dataset(overlap_chunks, 'out', shape, 'uint64')
+    ndist.mergeAndSerializeOverlaps(overlap_chunks, 'blocks', overlap_chunks, 'out', True, K.BEGIN, K.END,
+                                    numberOfThreads=2, serializeCount=serialize_count)
+    pairs, counts = _merged_inputs(merged)
+    want = _overlap_rows(K.IN_RANGE)
+    assert pairs.dtype == counts.dtype == np.uint64
+    np.testing.assert_array_equal(pairs, want[0])
+    np.testing.assert_array_equal(counts, want[1])
+    assert read == [((handle, K.BEGIN, K.END), {})] and handle.freed == 1
+    out = np.zeros(shape, np.uint64)
+    out[K.BEGIN:K.END] = np.stack([best, n_best], axis=1) if serialize_count else best
+    np.testing.assert_array_equal(K.read_output(overlap_chunks, 'out'), out)
+
+
+def test_merge_of_an_empty_range_gets_empty_tables(overlap_chunks, monkeypatch):
+    handle = K.Handle()
+    merged = K.capture(monkeypatch, rag, 'merge_overlaps_handle', handle)
+    K.capture(monkeypatch, rag, 'max_overlaps', (np.zeros(2, np.uint64), np.zeros(2, np.uint64)))
+    K.output_dataset(overlap_chunks, 'out', (16,), 'uint64')
+    ndist.mergeAndSerializeOverlaps(overlap_chunks, 'blocks', overlap_chunks, 'out', True, 12, 14)
+    pairs, counts = _merged_inputs(merged)
+    assert (pairs.shape, pairs.dtype, counts.shape, counts.dtype) == ((0, 2), np.uint64, (0,), np.uint64)
+    assert handle.freed == 1
+
+
+def test_merge_without_max_overlap_writes_the_merged_chunk(overlap_chunks, monkeypatch):
+    pairs, counts = _overlap_rows([4, 5])
+    handle = K.Handle(n_edges=4, edges=pairs, counts=counts)
+    merged = K.capture(monkeypatch, rag, 'merge_overlaps_handle', handle)
+    read = K.capture(monkeypatch, rag, 'max_overlaps', None)
+    K.output_dataset(overlap_chunks, 'out', (K.N_OUT,), 'uint64', chunks=(4,))
+    ndist.mergeAndSerializeOverlaps(overlap_chunks, 'blocks', overlap_chunks, 'out', False, K.BEGIN, K.END)
+    np.testing.assert_array_equal(_merged_inputs(merged)[0], _overlap_rows(K.IN_RANGE)[0])
+    assert read == [] and handle.freed == 1
+    np.testing.assert_array_equal(K.chunk_of(overlap_chunks, 'out', (1,)), ndist.encode_overlap_chunk(pairs, counts))
+    assert K.chunk_of(overlap_chunks, 'out', (0,)) is None and K.chunk_of(overlap_chunks, 'out', (2,)) is None
+    # an empty merged table writes no chunk
+    empty = K.Handle(n_edges=0)
+    monkeypatch.setattr(rag, 'merge_overlaps_handle', lambda *a: empty)
+    ndist.mergeAndSerializeOverlaps(overlap_chunks, 'blocks', overlap_chunks, 'out', False, 8, 12)
+    assert K.chunk_of(overlap_chunks, 'out', (2,)) is None and empty.freed == 1
+
+
+def test_block_overlaps_write_their_chunk_unless_empty(tmp_path, monkeypatch):
+    path = str(tmp_path / 'b.n5')
+    K.output_dataset(path, 'blocks', (1, 1, 3), 'uint64', chunks=(1, 1, 1))
+    pairs, counts = _overlap_rows([4, 5])
+    lab = np.zeros((1, 1, 2), np.uint64)
+    for handle, ignore, want in ((K.Handle(n_edges=4, edges=pairs, counts=counts), (True, 7), 7),
+                                 (K.Handle(n_edges=0), (False, 7), None)):
+        made = K.capture(monkeypatch, rag, 'label_overlaps_handle', handle)
+        pos = (0, 0, 1) if handle.n_edges else (0, 0, 2)
+        ndist.computeAndSerializeLabelOverlaps(lab, lab, path, 'blocks', pos, *ignore)
+        (args, kw), = made
+        assert args[0] is lab and args[1] is lab and list(args[2:]) + list(kw.values()) == [want]
+        assert handle.freed == 1
+    np.testing.assert_array_equal(K.chunk_of(path, 'blocks', (0, 0, 1)), ndist.encode_overlap_chunk(pairs, counts))
+    assert K.chunk_of(path, 'blocks', (0, 0, 2)) is None

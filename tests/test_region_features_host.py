@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from cluster_tools_amd import _lib, features, n5, rag
+from tests import chunk_cases as K
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 U = 2.0 ** -53
@@ -293,3 +294,77 @@ def test_python_argument_checks():
         rag.region_feature_rows(dict(rows=np.zeros((0, 5))), 0, 4, norm=0.0)
     with pytest.raises(ValueError, match='Invalid feature name'):
         features.mergeAndSerializeRegionFeatures('x', 'y', 'z', 'w', 0, 4, featureNames=('count', 'variance'))
+
+
+# ------------------------------------------------- the chunk loop of the merge
+def _rows_of(ids):
+    """One row per id, told apart by its count column."""
+    rows = np.zeros((len(ids), 5), np.float64)
+    rows[:, 0] = ids
+    rows[:, 1] = 100 + np.arange(len(ids))
+    return rows
+
+
+@pytest.fixture
+def region_chunks(tmp_path):
+    path = str(tmp_path / 'r.n5')
+    K.block_dataset(path, 'blocks', 'float64', lambda ids: features.encode_region_chunk(_rows_of(ids)))
+    K.output_dataset(path, 'out', (K.N_OUT, 2), 'float32')
+    return path
+
+
+@pytest.mark.parametrize('norm', [None, 255.0])
+def test_merge_reads_the_rows_of_its_range_and_writes_the_slice(region_chunks, monkeypatch, norm):
+    if norm is not None:
+        with n5.file_reader(region_chunks) as f:
+            f['blocks'].attrs['norm'] = norm
+    handle = K.Handle()
+    merged = K.capture(monkeypatch, rag, 'merge_region_features_handle', handle)
+    dense = np.arange(4 * 5, dtype=np.float64).reshape(4, 5) + 0.5
+    read = K.capture(monkeypatch, rag, 'region_feature_rows', dense)
+    features.mergeAndSerializeRegionFeatures(region_chunks, 'blocks', region_chunks, 'out', K.BEGIN, K.END,
+                                             featureNames=('maximum', 'count'), numberOfThreads=2)
+    ((rows,), kw), = merged
+    mixed = _rows_of(K.MIXED_IDS)
+    assert not kw and rows.dtype == np.float64
+    np.testing.assert_array_equal(rows, mixed[[K.MIXED_IDS.index(a) for a in K.IN_RANGE]])
+    (args, kw), = read
+    assert args[0] is handle and list(args[1:]) + list(kw.values()) == [K.BEGIN, K.END, 'features', norm or 1.0]
+    assert handle.freed == 1
+    out = np.zeros((K.N_OUT, 2), np.float32)
+    out[K.BEGIN:K.END] = dense[:, [4, 1]].astype(np.float32)
+    got = K.read_output(region_chunks, 'out')
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, out)
+
+
+def test_merge_of_an_empty_range_gets_an_empty_table(region_chunks, monkeypatch):
+    handle = K.Handle()
+    merged = K.capture(monkeypatch, rag, 'merge_region_features_handle', handle)
+    K.capture(monkeypatch, rag, 'region_feature_rows', np.zeros((0, 5)))
+    features.mergeAndSerializeRegionFeatures(region_chunks, 'blocks', region_chunks, 'out', 12, 12)
+    ((rows,), _), = merged
+    assert rows.shape == (0, 5) and rows.dtype == np.float64 and handle.freed == 1
+
+
+def test_block_features_write_their_chunk_unless_empty_and_always_the_attributes(tmp_path, monkeypatch):
+    rows = _rows_of([4, 5])
+    lab = np.zeros((1, 1, 2), np.uint64)
+    for k, (handle, data, norm, ignore) in enumerate((
+            (K.Handle(n_nodes=2, region_rows=rows), np.zeros((1, 1, 2), np.uint8), 255.0, 0),
+            (K.Handle(n_nodes=0), np.zeros((1, 1, 2), np.uint8), 255.0, None),
+            (K.Handle(n_nodes=0), np.zeros((1, 1, 2), np.float32), 1.0, None))):
+        path = str(tmp_path / ('b%d.n5' % k))
+        K.output_dataset(path, 'blocks', (1, 1, 3), 'float64', chunks=(1, 1, 1))
+        made = K.capture(monkeypatch, rag, 'region_features_handle', handle)
+        features.computeAndSerializeRegionFeatures(lab, data, path, 'blocks', (0, 0, 1), ignoreLabel=ignore)
+        (args, kw), = made
+        assert args[0] is lab and args[1] is data and list(args[2:]) + list(kw.values()) == [ignore]
+        assert handle.freed == 1
+        with n5.file_reader(path, 'r') as f:
+            assert f['blocks'].attrs['feature_names'] == features.FEATURE_NAMES and f['blocks'].attrs['norm'] == norm
+        got = K.chunk_of(path, 'blocks', (0, 0, 1))
+        if handle.n_nodes:
+            np.testing.assert_array_equal(got, rows.reshape(-1))
+        else:
+            assert got is None
