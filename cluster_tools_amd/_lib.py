@@ -57,6 +57,7 @@ CTG_IO_GZIP = 1
 CTG_IO_ZLIB = 2
 CTG_SORT_WORDS = 12
 CTG_SORT_PATH_GROUP = 5
+CTG_SCAN_WORDS = 4
 
 _lock = threading.Lock()
 _lib = None
@@ -159,6 +160,7 @@ PROTOTYPES = {
     'ctg_set_profiling': (ctypes.c_int, [ctypes.c_int]),
     'ctg_last_timings': (ctypes.c_int, [c_dblp, ctypes.c_int]),
     'ctg_last_sort': (ctypes.c_int, [c_i64p, ctypes.c_int]),
+    'ctg_last_scan': (ctypes.c_int, [c_i64p, ctypes.c_int]),
     'ctg_diag_bounds': (ctypes.c_int, [c_vp]),
 }
 

@@ -233,6 +233,21 @@ int ctg_last_sort(int64_t* out, int n) {
     return CTG_OK;
 }
 
+int ctg_last_scan(int64_t* out, int n) {
+    if (!out || n < 0) {
+        set_error("ctg_last_scan: null buffer or negative count");
+        return CTG_ERR_ARG;
+    }
+    const ScanReport& r = ws(current_device()).last_scan;
+    int64_t v[CTG_SCAN_WORDS];
+    v[CTG_SCAN_WAVES] = r.waves[0];
+    v[CTG_SCAN_INTERIOR_WAVES] = r.interior[0];
+    v[CTG_SCAN_NARROW_WAVES] = r.waves[1];
+    v[CTG_SCAN_NARROW_INTERIOR_WAVES] = r.interior[1];
+    for (int i = 0; i < n && i < CTG_SCAN_WORDS; ++i) out[i] = v[i];
+    return CTG_OK;
+}
+
 int ctg_result_num_blocks(const ctg_result* r) { return r ? (int)std::max<size_t>(r->edge_off.size(), 1) - 1 : -1; }
 
 int ctg_result_block_offsets(const ctg_result* r, int64_t* edge_off, int64_t* node_off) {

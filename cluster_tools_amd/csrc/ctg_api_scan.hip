@@ -34,6 +34,7 @@ struct ScanSwitches {
     int narrow_rows = -1;    // CTG_NARROW_ROWS=0/1 forces a tile width (boundary maps); -1: unset
     bool skip_adj = true;    // CTG_SKIP_ADJ=0 keeps the adjacency markers
     bool nn3 = true;         // CTG_NN3=0 keeps the channel loop
+    bool interior = true;    // CTG_SCAN_INTERIOR=0: every wave takes the general plane loop (A/B, tests)
     int ablate = 0;          // CTG_ABLATE: scan ablations (CTG_DIAG builds only)
 };
 
@@ -48,6 +49,7 @@ static ScanSwitches scan_switches(bool whole_array, bool boundary_map) {
         if (const char* t = getenv("CTG_NARROW_ROWS")) sw.narrow_rows = atoi(t) ? 1 : 0;
     if (const char* t = getenv("CTG_SKIP_ADJ")) sw.skip_adj = atoi(t) != 0;
     if (const char* t = getenv("CTG_NN3")) sw.nn3 = t[0] != '0';
+    if (const char* t = getenv("CTG_SCAN_INTERIOR")) sw.interior = t[0] != '0';
 #ifdef CTG_DIAG
     if (const char* t = getenv("CTG_ABLATE")) sw.ablate = atoi(t);
 #endif
@@ -119,7 +121,7 @@ static int scan_records(Workspace& w, const ScanParams& P, int64_t V, hipStream_
         CTG_CHECK(ensure_records(w, need, 0));
         CTG_CHECK(hipMemsetAsync(w.counters, 0, sizeof(Counters), s));
         ev.mark(0);   // (re-recorded here: the scan phase brackets the scan launch alone)
-        CTG_CHECK(launch_face_scan(PW, w.rec, w.counters, s));
+        CTG_CHECK(launch_face_scan(PW, w.rec, w.counters, s, &w.last_scan));
         ev.mark(1);
         CTG_CHECK(hipMemcpyAsync(w.counters_host, w.counters, sizeof(Counters), hipMemcpyDeviceToHost, s));
         CTG_CHECK(hipStreamSynchronize(s));
@@ -291,6 +293,7 @@ static void plan_whole_tiles(ScanParams& P, const int64_t* shape, const int64_t*
     if (sw.tile_z_narrow) P.tile_z_narrow = sw.tile_z_narrow;
     P.ablate = sw.ablate;
     P.tail_tiles = sw.tail_tiles;
+    P.interior = sw.interior;
 }
 
 // density probe: the tile width of a boundary map (narrow_rows_mode) -- where
@@ -620,6 +623,7 @@ int ctg_rag_blocks(const void* labels, int label_bits, const void* data, int dat
     RegionPrefix pre{};
     bool overflow = false;
     const bool scanned = P.batch_tiles > 0;
+    if (!scanned) w.last_scan = ScanReport{};   // (ctg_last_scan: no launch)
     if (scanned && (rc = scan_records(w, P, plan.voxels, s, sw, ev, pre, &overflow, who)) != CTG_OK) return rc;
     if (overflow)
         return blocks_dense_reentry(dl, label_bits, dd, data_kind, n_channels, offsets, blocks, n_blocks, labels_len,

@@ -238,6 +238,10 @@ struct ScanParams {
     int tail_tiles;            // host switch (CTG_TAIL_TILES)
     int64_t main_tiles;
     int tail_z0, tile_z_tail;
+    // host switch (CTG_SCAN_INTERIOR, whole arrays): the face kernels' interior
+    // waves (scan_wave_interior, ctg_plan.h) walk their planes without ownership
+    // masks; 0: every wave takes the general plane loop
+    int interior;
 };
 
 struct Counters {               // device-side counters, zeroed per call
@@ -345,6 +349,7 @@ struct Workspace {
     double last_ms[8] = {0};   // scan, pack, sort, segment, reduce, nodes, total, narrow (always 0: no such pass)
     int64_t last_records = 0, last_direct = 0;
     SortReport last_sort;   // the last record sort (ctg_last_sort); host values, a few stores per call
+    ScanReport last_scan;   // the last whole-array face scan (ctg_last_scan); host values
     int profiling = 0;
 };
 
@@ -392,7 +397,9 @@ struct Ev {   // phase marks of a profiled call
 // launchers (one declaration each; the definitions name their file)
 // ---------------------------------------------------------------------------
 // ctg_scan.hip
-hipError_t launch_face_scan(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s);
+// rep: null, or receives the waves of the launch(es) and how many are interior
+hipError_t launch_face_scan(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s,
+                            ScanReport* rep = nullptr);
 int64_t scan_max_x();   // widest array (along x) the face scan takes
 int scan_tile_rows();
 int scan_tile_rows_narrow();

@@ -134,6 +134,65 @@ inline int narrow_rows_mode(bool boundary_map, int64_t V, int nr_switch) {
 }
 
 // ---------------------------------------------------------------------------
+// face-scan interior waves (whole arrays)
+// ---------------------------------------------------------------------------
+// One axis of a wave's reach: voxels [a, b) and, at b, the upper neighbour of
+// the last one.  Interior: every voxel is owned, and b exists and is owned.
+CTG_HD constexpr bool scan_axis_interior(int64_t n, int64_t ob, int64_t oe, int64_t a, int64_t b) {
+    return ob <= a && b < oe && b < n;
+}
+// A wave of the face scan holds rows [yw, yw + rows) (+ the halo row) of the
+// columns [x0, x0 + TILE_X) (+ the halo column) and walks the planes [z0, z1)
+// (+ the prefetched plane z1).  It is interior when all of that lies in the
+// owned box [own_begin, own_end) of the array: then every ownership mask of the
+// plane loop is full -- each lane, row and plane, and the x, y and z face above
+// each -- and no load offset is clamped, so the loop may drop the masks and the
+// clamps (ctg_scan.hip).  A wave that merely fills its tile is not interior:
+// its last lane, row or plane may be the array's, with no neighbour above.
+CTG_HD constexpr bool scan_wave_interior(const int64_t* shape, const int64_t* own_begin, const int64_t* own_end,
+                                         int64_t x0, int64_t yw, int64_t rows, int64_t z0, int64_t z1) {
+    return scan_axis_interior(shape[2], own_begin[2], own_end[2], x0, x0 + TILE_X) &&
+           scan_axis_interior(shape[1], own_begin[1], own_end[1], yw, yw + rows) &&
+           scan_axis_interior(shape[0], own_begin[0], own_end[0], z0, z1);
+}
+
+// The tiles of one whole-array launch (ctg_scan.hip: launch_scan_r): ntx x nty
+// tiles of TILE_X columns and waves x rows rows a layer; main_layers layers of
+// tile_z planes from plane 0, cut off at tail_z0, then tail_layers layers of
+// tile_z_tail planes from tail_z0 (none: tail_z0 = Z).
+struct ScanTilePlan {
+    int64_t ntx, nty, rows, waves;
+    int64_t tile_z, main_layers, tail_z0, tile_z_tail, tail_layers;
+    constexpr int64_t n_waves() const { return ntx * nty * waves * (main_layers + tail_layers); }
+};
+// Interior waves of such a launch.  scan_wave_interior is a conjunction over
+// the axes, so the count is the product of the per-axis counts.
+inline int64_t scan_interior_waves(const int64_t* shape, const int64_t* own_begin, const int64_t* own_end,
+                                   const ScanTilePlan& t) {
+    int64_t nx = 0, ny = 0, nz = 0;
+    for (int64_t tx = 0; tx < t.ntx; ++tx)
+        nx += scan_axis_interior(shape[2], own_begin[2], own_end[2], tx * TILE_X, tx * TILE_X + TILE_X);
+    for (int64_t w = 0; w < t.nty * t.waves; ++w)
+        ny += scan_axis_interior(shape[1], own_begin[1], own_end[1], w * t.rows, w * t.rows + t.rows);
+    const int64_t zlim = std::min(shape[0], t.tail_z0);
+    for (int64_t tz = 0; tz < t.main_layers; ++tz)
+        nz += scan_axis_interior(shape[0], own_begin[0], own_end[0], tz * t.tile_z,
+                                 std::min(tz * t.tile_z + t.tile_z, zlim));
+    for (int64_t tz = 0; tz < t.tail_layers; ++tz)
+        nz += scan_axis_interior(shape[0], own_begin[0], own_end[0], t.tail_z0 + tz * t.tile_z_tail,
+                                 std::min(t.tail_z0 + tz * t.tile_z_tail + t.tile_z_tail, shape[0]));
+    return nx * ny * nz;
+}
+
+// What ctg_last_scan reports of a workspace's last whole-array face scan
+// (ctg.h: the CTG_SCAN_* words): per tile width, the waves launched and how
+// many of them take the interior plane loop.  Host values only.
+struct ScanReport {
+    int64_t waves[2] = {0, 0};      // [0] wide tiles, [1] narrow tiles; 0: no such launch
+    int64_t interior[2] = {0, 0};
+};
+
+// ---------------------------------------------------------------------------
 // batched blocks (ctg_rag_blocks)
 // ---------------------------------------------------------------------------
 // one array of a batched call: the host's ctg_block_desc in device memory plus

@@ -863,25 +863,26 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
     constexpr int ablate = 0;      // product kernels carry no diagnostic branches
 #endif
     const uint32_t hi_mask = BATCH ? P.label_hi_mask : 0u;
+    // The wave's ownership masks and load geometry are set by wave_geometry
+    // below, which each body of the plane loop calls in front of its planes:
+    // an interior wave (every lane, row and plane and the face above each
+    // owned: scan_wave_interior, ctg_plan.h) gets them as constants -- masks
+    // all ones, no clamp -- and computes none of the general ones.
     // lane masks (x is per lane): faces are owned by their upper voxel
     const bool inx = x < X;
-    const bool own_x_lo = x >= obx && x < oex;
-    const bool lane_xf = inx && x + 1 < X && x + 1 >= obx && x + 1 < oex;   // x face (x, x+1)
-    const bool lane_yz = inx && own_x_lo;                                    // y / z faces, samples at p
+    bool lane_xf, lane_yz;   // x face (x, x+1); y / z faces, samples at p
     // graph membership (batched): both voxels inside the graph box
     const bool g_x_lo = batch && inx && x >= gbx && x < gex;
     const bool glane_xf = g_x_lo && x + 1 < gex;
     const bool glane_yz = g_x_lo;
     // the same lane sets as wave masks (uniform)
-    const uint64_t m_xf = __builtin_amdgcn_ballot_w64(lane_xf), m_yz = __builtin_amdgcn_ballot_w64(lane_yz);
+    uint64_t m_xf, m_yz;
     const uint64_t m_gxf = __builtin_amdgcn_ballot_w64(glane_xf), m_gyz = __builtin_amdgcn_ballot_w64(glane_yz);
     // row masks (uniform): bit r for row y = yw + r
-    uint32_t row_x = 0, row_y = 0, grow_x = 0, grow_y = 0;
+    uint32_t row_x, row_y, grow_x = 0, grow_y = 0;
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
         const int y = yw + r;
-        if (y < Y && y >= oby && y < oey) row_x |= 1u << r;
-        if (y + 1 < Y && y + 1 >= oby && y + 1 < oey) row_y |= 1u << r;
         if (batch && y < Y && y >= gby && y < gey) grow_x |= 1u << r;
         if (batch && y + 1 < gey && y >= gby) grow_y |= 1u << r;
     }
@@ -889,8 +890,6 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
     // with scalar selects, not a v_cndmask + v_readfirstlane per mask and plane
     // (the channel-loop kernels keep their code as it was, see scalar_loads)
     if constexpr (scalar_loads(MODE)) {
-        row_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_x);
-        row_y = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_y);
         grow_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)grow_x);
         grow_y = (uint32_t)__builtin_amdgcn_readfirstlane((int)grow_y);
     }
@@ -925,8 +924,7 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
     // row / column (valid memory; every face and sample of such a row or lane
     // is masked by row_x / row_y / lane_xf / lane_yz), so no exec-mask
     // branches and no default moves sit between the loads.
-    const int xcl = min(x, X - 1);
-    const int xhc = min(xh, X - 1);
+    int xcl, xhc;
     const int64_t csz = (int64_t)Z * sz;   // channel stride (NN3)
     // scalar_loads(): the same clamped addresses as (uniform base) + (uniform
     // row offset) + (per-lane offset).  The base is the wave's first row,
@@ -934,25 +932,78 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
     // min(r, rmax) < 0 makes them below); l_off / d_off and the NN3 channel
     // strides are part of it.  Row r sits rofs[r] elements on, the lane at
     // xcl, the x-halo lane at its row's start + xhc.
-    const int ywc = min(yw, Y - 1);
-    const int rmaxc = Y - 1 - ywc;   // >= 0
-    const uint64_t lbase = scalar_loads(MODE) ? uniform64((uint64_t)(L + (int64_t)ywc * X)) : 0;
-    const uint64_t dbase = scalar_loads(MODE) && (BND || NN3)
-                               ? uniform64((uint64_t)(D + (NN3 ? (int64_t)P.nn_ch[2] * csz : 0) + (int64_t)ywc * X))
-                               : 0;
-    const uint64_t aybase = scalar_loads(MODE) && NN3 ? uniform64((uint64_t)(D + (int64_t)P.nn_ch[1] * csz + (int64_t)ywc * X)) : 0;
-    const uint64_t azbase = scalar_loads(MODE) && NN3 ? uniform64((uint64_t)(D + (int64_t)P.nn_ch[0] * csz + (int64_t)ywc * X)) : 0;
-    const uint32_t win = (uint32_t)__builtin_amdgcn_readfirstlane((min(ROWS, rmaxc) + 1) * X);   // elements a wave reads of a plane
-    const uint32_t xh_el = (uint32_t)(min(min(lane, ROWS - 1), rmaxc) * X + xhc);                // x-halo lane's element
+    uint32_t win;      // elements a wave reads of a plane
+    uint32_t xh_el;    // x-halo lane's element
     uint32_t rofs[ROWS + 1];
+    // Whole arrays (RUNNING): the bases of the plane load_plane reads next are
+    // carried in SGPRs from plane to plane -- next_plane adds the plane stride
+    // in bytes (one add and one carry a base), so no z * Y * X in 64 bits per
+    // plane.  The batched kernels keep the product: they sit at their SGPR limit.
+    constexpr bool RUNNING = scalar_loads(MODE) && !BATCH;
+    const uint64_t lstep = (uint64_t)sz * sizeof(LabelT), dstep = (uint64_t)sz * sizeof(DataT);
+    uint64_t lbase, dbase, aybase, azbase;   // the bases at plane 0 ...
+    uint64_t lcur = 0, dcur = 0, aycur = 0, azcur = 0;   // ... and (RUNNING) at the plane read next
+    auto wave_geometry = [&](bool inner) {   // inner: a constant at both calls
+        if (inner) {
+            lane_xf = lane_yz = true;
+            m_xf = m_yz = ~0ull;
+            row_x = row_y = (1u << ROWS) - 1u;
+        } else {
+            const bool own_x_lo = x >= obx && x < oex;
+            lane_xf = inx && x + 1 < X && x + 1 >= obx && x + 1 < oex;
+            lane_yz = inx && own_x_lo;
+            m_xf = __builtin_amdgcn_ballot_w64(lane_xf);
+            m_yz = __builtin_amdgcn_ballot_w64(lane_yz);
+            row_x = row_y = 0;
 #pragma unroll
-    for (int r = 0; r <= ROWS; ++r) rofs[r] = (uint32_t)__builtin_amdgcn_readfirstlane(min(r, rmaxc) * X);
+            for (int r = 0; r < ROWS; ++r) {
+                const int y = yw + r;
+                if (y < Y && y >= oby && y < oey) row_x |= 1u << r;
+                if (y + 1 < Y && y + 1 >= oby && y + 1 < oey) row_y |= 1u << r;
+            }
+            if constexpr (scalar_loads(MODE)) {
+                row_x = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_x);
+                row_y = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_y);
+            }
+        }
+        xcl = inner ? x : min(x, X - 1);
+        xhc = inner ? xh : min(xh, X - 1);
+        const int ywc = inner ? yw : min(yw, Y - 1);
+        const int rmaxc = inner ? ROWS : Y - 1 - ywc;   // >= 0
+        lbase = scalar_loads(MODE) ? uniform64((uint64_t)(L + (int64_t)ywc * X)) : 0;
+        dbase = scalar_loads(MODE) && (BND || NN3)
+                    ? uniform64((uint64_t)(D + (NN3 ? (int64_t)P.nn_ch[2] * csz : 0) + (int64_t)ywc * X))
+                    : 0;
+        aybase = scalar_loads(MODE) && NN3 ? uniform64((uint64_t)(D + (int64_t)P.nn_ch[1] * csz + (int64_t)ywc * X)) : 0;
+        azbase = scalar_loads(MODE) && NN3 ? uniform64((uint64_t)(D + (int64_t)P.nn_ch[0] * csz + (int64_t)ywc * X)) : 0;
+        win = inner ? (uint32_t)((ROWS + 1) * X)
+                    : (uint32_t)__builtin_amdgcn_readfirstlane((min(ROWS, rmaxc) + 1) * X);
+        xh_el = (uint32_t)(min(min(lane, ROWS - 1), rmaxc) * X + xhc);
+#pragma unroll
+        for (int r = 0; r <= ROWS; ++r)
+            rofs[r] = inner ? (uint32_t)(r * X) : (uint32_t)__builtin_amdgcn_readfirstlane(min(r, rmaxc) * X);
+        if constexpr (RUNNING) {
+            lcur = lbase + (uint64_t)z0 * lstep;
+            dcur = dbase + (uint64_t)z0 * dstep;
+            aycur = aybase + (uint64_t)z0 * dstep;
+            azcur = azbase + (uint64_t)z0 * dstep;
+        }
+    };
+    auto next_plane = [&](bool step) {   // step (uniform): false re-reads the plane
+        lcur += step ? lstep : 0;
+        if constexpr (BND || NN3) dcur += step ? dstep : 0;
+        if constexpr (NN3) {
+            aycur += step ? dstep : 0;
+            azcur += step ? dstep : 0;
+        }
+    };
+    // (z: the plane; with RUNNING the plane is the one the bases stand at)
     auto load_plane = [&](int z, LabelT (&Lb)[ROWS + 1], float (&Db)[ROWS + 1], LabelT& XL, float& XD,
                           float (&Dyb)[ROWS + 1], float (&Dzb)[ROWS], bool with_z) {
         if constexpr (scalar_loads(MODE)) {
-            const uint64_t pz = (uint64_t)z * (uint64_t)sz;   // plane offset in elements (uniform)
-            const BufRsrc Lr = buf_rsrc(lbase + pz * sizeof(LabelT), win * (uint32_t)sizeof(LabelT));
-            const BufRsrc Dr = buf_rsrc(dbase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
+            const uint64_t pz = RUNNING ? 0 : (uint64_t)z * (uint64_t)sz;   // plane offset in elements (uniform)
+            const BufRsrc Lr = buf_rsrc(RUNNING ? lcur : lbase + pz * sizeof(LabelT), win * (uint32_t)sizeof(LabelT));
+            const BufRsrc Dr = buf_rsrc(RUNNING ? dcur : dbase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
             const uint32_t xl = (uint32_t)xcl * (uint32_t)sizeof(LabelT), xd = (uint32_t)xcl * (uint32_t)sizeof(DataT);
 #pragma unroll
             for (int r = 0; r <= ROWS; ++r) {
@@ -961,12 +1012,12 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
                 else Db[r] = 0.f;
             }
             if constexpr (NN3) {
-                const BufRsrc Yr = buf_rsrc(aybase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
+                const BufRsrc Yr = buf_rsrc(RUNNING ? aycur : aybase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
 #pragma unroll
                 for (int r = 1; r <= ROWS; ++r)
                     Dyb[r] = buf_val<DataT, true>(Yr, xd, rofs[r] * (uint32_t)sizeof(DataT));
                 if (with_z) {
-                    const BufRsrc Zr = buf_rsrc(azbase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
+                    const BufRsrc Zr = buf_rsrc(RUNNING ? azcur : azbase + pz * sizeof(DataT), win * (uint32_t)sizeof(DataT));
 #pragma unroll
                     for (int r = 0; r < ROWS; ++r)
                         Dzb[r] = buf_val<DataT, true>(Zr, xd, rofs[r] * (uint32_t)sizeof(DataT));
@@ -1096,226 +1147,25 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
         push_m(__builtin_amdgcn_ballot_w64(c_) & (lanes), c_ && (member), __VA_ARGS__); \
     } while (0)
 
-    if (z0 < z1) {
-        load_plane(z0, Ln, Dc, XLn, XDc, Dyc, Dzn, false);
-#pragma unroll
-        for (int r = 0; r <= ROWS; ++r) Lc[r] = narrow(Ln[r]);
-        XLc = narrow(XLn);
-    }
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): nothing in flight when the plane loop starts
-    for (int z = z0; z < z1; ++z) {
-        const bool hz = z + 1 < Z;
-        // prefetch of plane z + 1, unconditional (the last plane re-reads
-        // itself; its z faces are masked by hz): in flight during the x / y
-        // faces, consumed by the z faces (z, z+1) at the end of the plane.
-        // (Tried: z faces (z-1, z) against the previous plane, so nothing in
-        // a plane waits for the prefetch -- 0.006 ms faster at 512^3, but the
-        // changed face order raised records by 23 % at cell 5.)
-        load_plane(hz ? z + 1 : z, Ln, Dn, XLn, XDn, Dyn, Dzn, true);
-        const bool zlo = z >= obz && z < oez;
-        const bool zup = hz && z + 1 >= obz && z + 1 < oez;      // face (z, z+1): upper voxel in the own box
-        const bool zg = batch && z >= gbz && z < gez;            // graph box planes (batched)
-        const bool gzup = zg && z + 1 < gez;
-        // this plane's face sites as scalar bit masks (bit r = row r): owned x /
-        // y / z faces and (batched) graph-box faces -- tested with scalar bit
-        // tests, not carried as per-lane booleans
-        const uint32_t s_xo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(zlo ? row_x : 0u));
-        const uint32_t s_yo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(zlo ? row_y : 0u));
-        const uint32_t s_zo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(zup ? row_x : 0u));
-        const uint32_t s_xg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(zg ? grow_x : 0u));
-        const uint32_t s_yg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(zg ? grow_y : 0u));
-        const uint32_t s_zg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(gzup ? grow_x : 0u));
-        if constexpr (MIX) {
-            // the channel loop holds most registers: the nearest-neighbour
-            // channels of this plane are loaded here, not prefetched with the
-            // labels, and die before the loop (x channel rows + x-halo, y
-            // channel rows 1..ROWS); the z channel is loaded before the z faces
-            const int rmax = Y - 1 - yw;
-            const DataT* Ax = D + (int64_t)P.nn_ch[2] * csz + (int64_t)z * sz + (int64_t)yw * X;
-            const DataT* Ay = D + (int64_t)P.nn_ch[1] * csz + (int64_t)z * sz + (int64_t)yw * X;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) Dc[r] = load_val_stream<DataT>(Ax, (int64_t)min(r, rmax) * X + xcl);
-            XDc = load_val<DataT>(Ax, (int64_t)min(min(lane, ROWS - 1), rmax) * X + xhc);
-#pragma unroll
-            for (int r = 1; r <= ROWS; ++r) Dyc[r] = load_val_stream<DataT>(Ay, (int64_t)min(r, rmax) * X + xcl);
-        }
-        if (ablate & 8) {   // diagnostic: loads only
-            uint32_t chk = 0;
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) chk ^= Lc[r] ^ (uint32_t)Ln[r] ^ __float_as_uint(Dc[r] + Dn[r]);
-            if (chk == 0x9E3779B9u && XLc == 7u) atomicAdd(&C->pad[0], 1ull);
+    // The wave's planes (ctg_scan_planes.inc: geometry, first plane, plane
+    // loop), compiled once per body.  The face kernels on whole arrays have
+    // two: an interior wave walks its planes without ownership masks, every
+    // other wave takes the general body, which is all the other kernels have.
+    // One wave-uniform branch in front; both bodies join below.  (What only
+    // the general body needs is computed inside it: the branch is laid out as
+    // one body after the other, and a value made in front of it for the
+    // second would stay live, in SGPRs, through the first.)
+    if constexpr (scalar_loads(MODE) && !BATCH) {
+        if (P.interior && scan_wave_interior(P.shape, P.own_begin, P.own_end, x0, yw, ROWS, z0, z1)) {
+            constexpr bool INTERIOR = true;
+#include "ctg_scan_planes.inc"
         } else {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) {
-                const uint32_t lc = Lc[r];
-                // x face (x, x+1); lane 63 takes its neighbour from the x-halo
-                const uint32_t lx = shl1(lc, (uint32_t)__builtin_amdgcn_readlane((int)XLc, r));
-                // owned faces carry samples; (batched) sub-graph faces the block
-                // does not own go in as adjacency-only entries
-                const bool xo = (s_xo >> r) & 1u, xg = BATCH && ((s_xg >> r) & 1u);
-                if ((xo || xg) && (!AFF || adj_marks || NNF)) {
-                    const float dx = (BND || NNF) ? __uint_as_float(shl1(__float_as_uint(Dc[r]),
-                                                                         (uint32_t)__builtin_amdgcn_readlane(
-                                                                             (int)__float_as_uint(XDc), r)))
-                                                  : 0.f;
-                    const bool own = xo && lane_xf;
-                    if constexpr (NNF) {   // aff[x channel] of the upper voxel x + 1
-                        PUSH(lc != lx, m_xf, own, lc, lx, __float_as_uint(dx), NN_MARK);
-                    } else {
-                        PUSH(lc != lx, (xo ? m_xf : 0ull) | (xg ? m_gxf : 0ull), own || (xg && glane_xf), lc, lx,
-                             (own || !BATCH) ? __float_as_uint(Dc[r]) : MARK_ADJ,
-                             (AFF || (BATCH && !own)) ? MARK_ADJ : __float_as_uint(dx));
-                    }
-                }
-                // y face (y, y+1)
-                const bool yo = (s_yo >> r) & 1u, yg = BATCH && ((s_yg >> r) & 1u);
-                if ((yo || yg) && (!AFF || adj_marks || NNF)) {
-                    const bool own = yo && lane_yz;
-                    if constexpr (NNF) {   // aff[y channel] of the upper voxel, row r + 1
-                        PUSH(lc != Lc[r + 1], m_yz, own, lc, Lc[r + 1], __float_as_uint(Dyc[r + 1]), NN_MARK);
-                    } else {
-                        PUSH(lc != Lc[r + 1], (yo ? m_yz : 0ull) | (yg ? m_gyz : 0ull), own || (yg && glane_yz), lc,
-                             Lc[r + 1],
-                             (own || !BATCH) ? __float_as_uint(Dc[r]) : MARK_ADJ,
-                             (AFF || (BATCH && !own)) ? MARK_ADJ : __float_as_uint(Dc[r + 1]));
-                    }
-                }
-            }
-            // affinity samples aff[c, p] for q = p + o_c, p in the owned box:
-            // per channel, the gathers / sample loads of all ROWS rows are in
-            // flight together, then their Bloom probes (long-range channels)
-            if constexpr (AFF) {
-                if (zlo && row_x) {
-                    const int64_t iz = (int64_t)z * sz + (int64_t)yw * X + x;
-                    const int n_loop = MIX ? P.n_loop : P.n_channels;
-                    for (int c0 = 0; c0 < n_loop; c0 += AFF_G) {
-                        constexpr int K = AFF_G * ROWS;   // (channel, row) sites of the group
-                        uint32_t lq[K];
-                        float av[K];
-                        bool act[K];
-#pragma unroll
-                        for (int j = 0; j < AFF_G; ++j) {
-                            const bool has = c0 + j < n_loop;
-                            const int c = MIX ? (has ? P.loop_ch[c0 + j] : 0) : c0 + j;
-                            const int qz = has ? z + P.offsets[c][0] : -1, oy = has ? P.offsets[c][1] : 0;
-                            const int qx = has ? x + P.offsets[c][2] : -1;
-                            const bool okzx = lane_yz && qz >= 0 && qz < Z && qx >= 0 && qx < X;
-#pragma unroll
-                            for (int r = 0; r < ROWS; ++r) {
-                                const int k = j * ROWS + r;
-                                const int qy = yw + r + oy;
-                                act[k] = (row_x >> r & 1u) && okzx && qy >= 0 && qy < Y;
-                                lq[k] = Lc[r];
-                                av[k] = 0.f;
-                                if (act[k]) {
-                                    // the low half only: every label's high half is
-                                    // checked where its own tile loads it
-                                    lq[k] = load_lo(L, (int64_t)qz * sz + (int64_t)qy * X + qx);
-                                    av[k] = load_val_stream<DataT>(D, (int64_t)c * Z * sz + iz + (int64_t)r * X);
-                                }
-                            }
-                        }
-#pragma unroll
-                        for (int k = 0; k < K; ++k) act[k] = act[k] && lq[k] != Lc[k % ROWS];
-                        // long-range channels: only pairs that are RAG edges
-                        // (MIX: every loop channel is long-range)
-                        const uint32_t glr = MIX ? (1u << AFF_G) - 1u : (P.lr_mask >> c0) & ((1u << AFF_G) - 1u);
-                        if (glr && P.bloom != nullptr && !(ablate & 512)) {
-                            uint64_t hb[K];
-                            unsigned long long wb[K];
-                            uint32_t blk[ROWS];   // the own label's block (owner-blocked filter)
-#pragma unroll
-                            for (int r = 0; r < ROWS; ++r) blk[r] = bloom_block(Lc[r], P.bloom_mask);
-#pragma unroll
-                            for (int k = 0; k < K; ++k) {
-                                hb[k] = bloom_hash(((uint64_t)Lc[k % ROWS] << 32) | lq[k]);
-                                wb[k] = (act[k] && (glr >> (k / ROWS) & 1u)) ? P.bloom[bloom_word(blk[k % ROWS], hb[k])]
-                                                                             : ~0ull;
-                            }
-#pragma unroll
-                            for (int k = 0; k < K; ++k)
-                                act[k] = act[k] && (wb[k] & bloom_bits(hb[k])) == bloom_bits(hb[k]);
-                        }
-#pragma unroll
-                        for (int j = 0; j < AFF_G; ++j) {
-                            if (c0 + j >= n_loop) break;
-                            const uint32_t mk = (P.bloom != nullptr && !(glr >> j & 1u)) ? MARK_ONE_ADJ : MARK_ONE;
-                            // (nearest-neighbour channels unpaired: A/B nn1024 scan 8.6 -> 9.4 ms paired)
-                            if (mk == MARK_ONE && P.bloom != nullptr) {
-                                // long-range (or unfiltered) channel: lanes 2i, 2i+1 with the
-                                // same key fold as one two-sample entry (along x a cell pair
-                                // spans runs of lanes), ~halving this channel's fold work
-#pragma unroll
-                                for (int r = 0; r < ROWS; ++r) {
-                                    const int k = j * ROWS + r;
-                                    const uint32_t sv = __float_as_uint(av[k]);
-                                    const uint32_t nq = swap1(lq[k]), ns = swap1(sv), nact = swap1(act[k] ? 1u : 0u);
-                                    const bool pair = act[k] && nact && nq == lq[k] && ns < MARK_ONE_ADJ &&
-                                                      sv < MARK_ONE_ADJ;   // Lc[r] is equal on the pair unless a face
-                                    const bool lead = (lane & 1) == 0;
-                                    const bool same_c = swap1(Lc[r]) == Lc[r];
-                                    const bool pr = pair && same_c;
-                                    PUSH(act[k] && !(pr && !lead), ~0ull, true, Lc[r], lq[k], sv,
-                                         (pr && lead) ? ns : MARK_ONE);
-                                }
-                            } else {
-#pragma unroll
-                                for (int r = 0; r < ROWS; ++r)
-                                    PUSH(act[j * ROWS + r], ~0ull, true, Lc[r], lq[j * ROWS + r],
-                                         __float_as_uint(av[j * ROWS + r]), mk);
-                            }
-                        }
-                    }
-                }
-            }
-            if constexpr (MIX) {   // the z channel of plane z + 1 (upper voxels of the z faces)
-                const int rmax = Y - 1 - yw;
-                const DataT* Az = D + (int64_t)P.nn_ch[0] * csz + (int64_t)(hz ? z + 1 : z) * sz + (int64_t)yw * X;
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) Dzn[r] = load_val_stream<DataT>(Az, (int64_t)min(r, rmax) * X + xcl);
-            }
-            // z faces (z, z+1): plane z against the prefetched plane
-            if (stamps) {   // diagnostic: how long the prefetched plane keeps this wave waiting
-                const uint64_t tw = stamp_now();
-                __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-                t_wait += stamp_now() - tw;
-            }
-            if ((s_zo | s_zg) && (!AFF || adj_marks || NNF)) {
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) {
-                    const bool zo = (s_zo >> r) & 1u, zgr = BATCH && ((s_zg >> r) & 1u);
-                    if (zo || zgr) {
-                        const bool own = zo && lane_yz;
-                        const uint32_t ln = (uint32_t)Ln[r];
-                        if constexpr (NNF) {   // aff[z channel] of the upper voxel, plane z + 1
-                            PUSH(Lc[r] != ln, m_yz, own, Lc[r], ln, __float_as_uint(Dzn[r]), NN_MARK);
-                        } else {
-                            PUSH(Lc[r] != ln, (zo ? m_yz : 0ull) | (zgr ? m_gyz : 0ull), own || (zgr && glane_yz),
-                                 Lc[r], ln, (own || !BATCH) ? __float_as_uint(Dc[r]) : MARK_ADJ,
-                                 (AFF || (BATCH && !own)) ? MARK_ADJ : __float_as_uint(Dn[r]));
-                        }
-                    }
-                }
-            }
+            constexpr bool INTERIOR = false;
+#include "ctg_scan_planes.inc"
         }
-        // staged entries stay staged across planes (raw faces are valid for
-        // whatever table they are folded into later)
-        poll();
-        // the prefetched plane has landed by now (it had the whole plane's work
-        // to do so): wait for it here, before the next plane's loads are
-        // issued -- a wait placed after them (where the compiler would put it
-        // on first use) would drain the new prefetch too
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-#pragma unroll
-        for (int r = 0; r <= ROWS; ++r) {
-            Lc[r] = narrow(Ln[r]);
-            Dc[r] = Dn[r];
-            if constexpr (NN3) {
-                if (r >= 1) Dyc[r] = Dyn[r];   // (row 0 of the y channel is never a sample)
-            }
-        }
-        XLc = narrow(XLn);
-        XDc = XDn;
+    } else {
+        constexpr bool INTERIOR = false;
+#include "ctg_scan_planes.inc"
     }
 #undef PUSH
     if (__ballot(ovf != 0) && lane == 0) atomicAdd(&C->label_overflow, 1ull);
@@ -1357,7 +1207,8 @@ __global__ __launch_bounds__(SCAN_THREADS, CTG_SCAN_MIN_WAVES) void k_face_scan(
 // launcher
 // ---------------------------------------------------------------------------
 template <typename LabelT, typename DataT, int MODE, int NR>
-static hipError_t launch_scan_r(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s) {
+static hipError_t launch_scan_r(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s,
+                                ScanReport* rep) {
     ScanParams Q = P;
     int64_t nwg = P.batch_tiles;
     if (!P.blocks) {
@@ -1391,6 +1242,14 @@ static hipError_t launch_scan_r(const ScanParams& P, const RecordBuf& R, Counter
                 nwg = Q.main_tiles + layer * ((P.shape[0] - zt0 + tzt - 1) / tzt);
             }
         }
+        if (rep && layer > 0) {   // which plane loop the waves of this launch take (ctg_last_scan)
+            const ScanTilePlan tp{Q.ntiles[0], Q.ntiles[1], NR, WAVES, Q.tile_z, Q.main_tiles / layer,
+                                  Q.tail_z0, Q.tile_z_tail, (nwg - Q.main_tiles) / layer};
+            const int width = NR == ROWS_NARROW && ROWS_NARROW != ROWS_WIDE ? 1 : 0;
+            rep->waves[width] = tp.n_waves();
+            rep->interior[width] =
+                scalar_loads(MODE) && P.interior ? scan_interior_waves(P.shape, P.own_begin, P.own_end, tp) : 0;
+        }
     } else {
         Q.main_tiles = nwg;
     }
@@ -1419,41 +1278,45 @@ static hipError_t launch_scan_r(const ScanParams& P, const RecordBuf& R, Counter
 // the narrow-tile kernel exists for whole-array boundary maps (the
 // fragmentation-bound configs[4] path); every other mode uses the wide one
 template <typename LabelT, typename DataT, int MODE>
-static hipError_t launch_scan_t(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s) {
+static hipError_t launch_scan_t(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s,
+                                ScanReport* rep) {
     if constexpr (MODE == MODE_BOUNDARY) {
         if (P.narrow_rows == 2 && !P.blocks) {
-            const hipError_t e = launch_scan_r<LabelT, DataT, MODE, ROWS_WIDE>(P, R, C, s);
-            return e != hipSuccess ? e : launch_scan_r<LabelT, DataT, MODE, ROWS_NARROW>(P, R, C, s);
+            const hipError_t e = launch_scan_r<LabelT, DataT, MODE, ROWS_WIDE>(P, R, C, s, rep);
+            return e != hipSuccess ? e : launch_scan_r<LabelT, DataT, MODE, ROWS_NARROW>(P, R, C, s, rep);
         }
-        if (P.narrow_rows == 1 && !P.blocks) return launch_scan_r<LabelT, DataT, MODE, ROWS_NARROW>(P, R, C, s);
+        if (P.narrow_rows == 1 && !P.blocks)
+            return launch_scan_r<LabelT, DataT, MODE, ROWS_NARROW>(P, R, C, s, rep);
     }
     // (batched blocks keep the wide tile: their tile counts come from scan_tile_rows())
     if constexpr (MODE == MODE_AFFINITY || MODE == MODE_AFF_MIX)
-        if (!P.blocks) return launch_scan_r<LabelT, DataT, MODE, ROWS_AFF>(P, R, C, s);
-    return launch_scan_r<LabelT, DataT, MODE, ROWS_WIDE>(P, R, C, s);
+        if (!P.blocks) return launch_scan_r<LabelT, DataT, MODE, ROWS_AFF>(P, R, C, s, rep);
+    return launch_scan_r<LabelT, DataT, MODE, ROWS_WIDE>(P, R, C, s, rep);
 }
 
 template <typename LabelT>
-static hipError_t launch_scan_l(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s) {
+static hipError_t launch_scan_l(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s,
+                                ScanReport* rep) {
     if (P.data_kind == CTG_DATA_NONE || P.data == nullptr)
-        return launch_scan_t<LabelT, float, MODE_GRAPH>(P, R, C, s);
+        return launch_scan_t<LabelT, float, MODE_GRAPH>(P, R, C, s, rep);
     const bool aff = P.n_channels > 0;
     const bool nn3 = aff && P.nn3 && !P.blocks;
     const bool mix = aff && P.nn_mix && !P.blocks;
     if (P.data_kind == CTG_DATA_U8)
-        return nn3 ? launch_scan_t<LabelT, uint8_t, MODE_AFF_NN>(P, R, C, s)
-               : mix ? launch_scan_t<LabelT, uint8_t, MODE_AFF_MIX>(P, R, C, s)
-               : aff ? launch_scan_t<LabelT, uint8_t, MODE_AFFINITY>(P, R, C, s)
-                     : launch_scan_t<LabelT, uint8_t, MODE_BOUNDARY>(P, R, C, s);
-    return nn3 ? launch_scan_t<LabelT, float, MODE_AFF_NN>(P, R, C, s)
-           : mix ? launch_scan_t<LabelT, float, MODE_AFF_MIX>(P, R, C, s)
-           : aff ? launch_scan_t<LabelT, float, MODE_AFFINITY>(P, R, C, s)
-                 : launch_scan_t<LabelT, float, MODE_BOUNDARY>(P, R, C, s);
+        return nn3 ? launch_scan_t<LabelT, uint8_t, MODE_AFF_NN>(P, R, C, s, rep)
+               : mix ? launch_scan_t<LabelT, uint8_t, MODE_AFF_MIX>(P, R, C, s, rep)
+               : aff ? launch_scan_t<LabelT, uint8_t, MODE_AFFINITY>(P, R, C, s, rep)
+                     : launch_scan_t<LabelT, uint8_t, MODE_BOUNDARY>(P, R, C, s, rep);
+    return nn3 ? launch_scan_t<LabelT, float, MODE_AFF_NN>(P, R, C, s, rep)
+           : mix ? launch_scan_t<LabelT, float, MODE_AFF_MIX>(P, R, C, s, rep)
+           : aff ? launch_scan_t<LabelT, float, MODE_AFFINITY>(P, R, C, s, rep)
+                 : launch_scan_t<LabelT, float, MODE_BOUNDARY>(P, R, C, s, rep);
 }
 
-hipError_t launch_face_scan(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s) {
-    if (P.label_bits == 32) return launch_scan_l<uint32_t>(P, R, C, s);
-    return launch_scan_l<uint64_t>(P, R, C, s);
+hipError_t launch_face_scan(const ScanParams& P, const RecordBuf& R, Counters* C, hipStream_t s, ScanReport* rep) {
+    if (rep) *rep = ScanReport{};
+    if (P.label_bits == 32) return launch_scan_l<uint32_t>(P, R, C, s, rep);
+    return launch_scan_l<uint64_t>(P, R, C, s, rep);
 }
 
 // Fragmentation probe: label changes along x on a sample of rows (a boundary

@@ -1353,3 +1353,12 @@ def last_sort():
     return dict(path=SORT_PATHS[v[0]] if v[0] >= 0 else None, packed=v[1], group_tried=v[2], group_done=v[3],
                 group_decline=SORT_DECLINES[v[4]], group_shift=v[5], group_buckets=v[6], largest_bucket=v[7],
                 ib=v[8], nb=v[9], ub=v[10], n=v[11])
+
+
+def last_scan():
+    """Which plane loop the waves of the last whole-array face scan of the current device took
+    (ctg_last_scan, include/ctg.h): waves and interior_waves of the launch of wide tiles, narrow_waves and
+    narrow_interior_waves of the launch of narrow tiles (0: no such launch)."""
+    buf = (ctypes.c_int64 * L.CTG_SCAN_WORDS)()
+    L.check(L.load().ctg_last_scan(buf, L.CTG_SCAN_WORDS), 'ctg_last_scan')
+    return dict(zip(['waves', 'interior_waves', 'narrow_waves', 'narrow_interior_waves'], list(buf)))

@@ -863,6 +863,27 @@ int ctg_last_timings(double* ms, int n);
 #define CTG_SORT_PATH_GROUP 5
 int ctg_last_sort(int64_t* out, int n);
 
+/* Which plane loop the waves of the last face scan of this thread's device
+ * took (ctg_rag_features; a ctg_rag_blocks call reports zeros): the first n
+ * (<= CTG_SCAN_WORDS) of
+ *   [CTG_SCAN_WAVES]          waves of the launch of wide tiles (0: no such launch)
+ *   [CTG_SCAN_INTERIOR_WAVES] those of them whose columns, rows and planes, and the
+ *                             neighbour above each, all lie in the owned box: they walk
+ *                             their planes without ownership masks (0 with
+ *                             CTG_SCAN_INTERIOR=0 in the environment, and for the
+ *                             channel-loop kernels of affinity maps, which have one loop)
+ *   [CTG_SCAN_NARROW_WAVES], [CTG_SCAN_NARROW_INTERIOR_WAVES] the same of the launch of
+ *                             narrow tiles (boundary maps of fragmented volumes; where the
+ *                             device picks the width, both launches are reported and one
+ *                             of them exits at once)
+ * Host values the call held anyway: no device read, no synchronisation. */
+#define CTG_SCAN_WAVES 0
+#define CTG_SCAN_INTERIOR_WAVES 1
+#define CTG_SCAN_NARROW_WAVES 2
+#define CTG_SCAN_NARROW_INTERIOR_WAVES 3
+#define CTG_SCAN_WORDS 4
+int ctg_last_scan(int64_t* out, int n);
+
 /* bounds checks of CTG_DIAG builds (no reference counterpart: hardening): the
  * first index into a call-sized workspace buffer (records, sorted positions,
  * run tables, permutations, node bitmaps, exchange rows) that reached past
